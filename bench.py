@@ -2,14 +2,21 @@
 """bench.py -- training images/s of CRNN + 1-D CTC (BASELINE.json configs[1]) on N MI355X GPUs.
 
     python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One "step" = zero_grad + forward + CTC loss + backward (+ RCCL gradient all-reduce for N>1) + fused Adam on a
 device-resident synthetic batch of 256 crops of 32x128 per GPU (weak scaling: global batch = 256*N).
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0, the last line of stdout.  A plain run only sets up, warms up and times the steps of
+the headline workload.  With --full the line also carries
   roofline      -- the dominant MFMA kernel: algorithmic FLOPs of its launches / their HIP-event durations
+  kernels       -- per-kernel HIP-event times of the same eager pass
   cpu_baseline  -- the oracle (reference restatement, oracle/crnn.py) timed on this box's host cores (rank 0, N=1)
+  secondaries   -- the other published configurations (default single-GPU CRNN run)
+  strong        -- the strong-scaling measurement (N > 1, weak scaling)
+--dump-outputs DIR: after the timed steps the model is put back to its seeded starting state and the timed step is replayed
+once; what it computed (loss, sampled parameters and gradients) is written as .npy files.
 """
 import argparse
 import ctypes
@@ -254,6 +261,59 @@ def cpu_baseline(workload="crnn", budget_s=20.0, crop=None):
                       (steps, what, torch.__version__, threads, avail, dt, warm)}
 
 
+DUMP_SAMPLE = 1 << 22     # elements per sampled array: 2 x 16 MB of float32 at most
+
+
+def seeded_state(model, opt):
+    """--dump-outputs: the seeded starting point of the run (taken before the first step): the flat fp32 parameters of every
+    optimizer group and the model's buffers.  The moments and the step counter are zero at that point."""
+    return ([f['p'].clone() if f is not None else None for f in opt._flat], [b.detach().clone() for b in model.buffers()])
+
+
+def restore_seeded_state(model, opt, state):
+    """Put the model and its fused optimizer back to `state` IN PLACE (a captured step keeps reading the same buffers):
+    parameters and buffers copied back, moments zeroed, the compute-dtype operand images regenerated from the restored
+    parameters, and the device step counter (hyper[5], completed steps) back to zero -- the update of the next step is then
+    the first one again, bias correction included."""
+    from megreader_amd.nn import prep
+    flat_p, bufs = state
+    for f, p0 in zip(opt._flat, flat_p):
+        if f is None:
+            continue
+        f['p'].copy_(p0)
+        f['s1'].zero_()
+        f['s2'].zero_()
+        prep.refresh(f['params'], f, tick=f['hyper'])      # regenerates the images; advances the counter ...
+        f['hyper'][5:6].zero_()                            # ... which is reset behind it
+    for b, b0 in zip(model.buffers(), bufs):
+        b.copy_(b0)
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what one step of the timed path handed its caller, as .npy files in `out_dir`: the step's loss
+    (float64) and the model after the step -- its parameters and their gradients, each flattened in `model.parameters()`
+    order and, when longer than DUMP_SAMPLE, reduced to a fixed sample (sorted indices drawn with seed 0).
+    The step is the timed path (the captured graph, or the eager step with --no-graph) replayed once after the timed steps
+    from the seeded starting state (restore_seeded_state): its inputs are then the same in every run.  The inputs of the
+    last TIMED step are not: they are the product of all the updates before it, and the step is not bit-repeatable (float
+    atomics in split reductions and BatchNorm statistics), a difference of rounding that Adam's normalised update turns into
+    different weights within tens of steps."""
+    import numpy as np
+    params = [p for p in model.parameters()]
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([p.grad.detach().reshape(-1).float() if p.grad is not None
+                        else torch.zeros(p.numel(), device=p.device) for p in params])
+    n = flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        sel = torch.from_numpy(idx).to(flat_p.device)
+        flat_p, flat_g = flat_p[sel], flat_g[sel]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "params.npy"), flat_p.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "grads.npy"), flat_g.cpu().numpy().astype(np.float32))
+
+
 def quiet_native_stdout():
     """Ranks other than 0 print nothing of their own, but RCCL writes a version banner through C stdio into THEIR stdout, which
     torch.distributed.run forwards to the launcher's: send file descriptor 1 of those ranks to stderr for the whole run."""
@@ -323,7 +383,19 @@ def main():
                          "GPU (256 global on 8 GPUs), gt_as_output fixed for determinism; db = configs[4]: the DB detector "
                          "(deformable ResNet-50 with 13 DCNv2 layers + SegDetector + L1BalanceCELoss, SGD) on 640x640 "
                          "images, batch 2 per GPU (16 global on 8 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the eager kernel-timer pass (roofline, kernels), "
+                         "the CPU baselines, the secondary configurations and, for N > 1, the strong-scaling line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, replay the timed step once from the seeded starting state and write what "
+                         "it computed as DIR/<name>.npy: loss (float64), and a fixed, seeded sample of the updated parameters "
+                         "and of their gradients (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.shape_table and not args.full:
+        ap.error("--shape-table needs --full (it is written from the eager kernel-timer pass)")
+    kernel_timer = args.full and not args.no_kernel_timer
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -353,8 +425,9 @@ def main():
     if args.gpus != world:
         print("warning: --gpus %d but WORLD_SIZE %d (using WORLD_SIZE)" % (args.gpus, world), file=sys.stderr)
 
-    def measure(workload, steps, warmup, with_cpu, scaling=None, crop=None, coins=None):
-        """One workload: build, warm up, time `steps` steps; returns the result dict on rank 0 (None elsewhere)."""
+    def measure(workload, steps, warmup, with_cpu, scaling=None, crop=None, coins=None, dump_dir=""):
+        """One workload: build, warm up, time `steps` steps; returns the result dict on rank 0 (None elsewhere).  With a
+        `dump_dir`, rank 0 writes what the last timed step computed there (dump_outputs)."""
         scaling = scaling or args.scaling
         random_coins = (coins or args.teacher_forcing) == "random"
         if crop is None and args.crop and workload == "res50ppm":
@@ -450,6 +523,7 @@ def main():
             from megreader_amd.apex.parallel import DistributedDataParallel
             ddp_shim = DistributedDataParallel(model)
             ddp_shim.fold_average_into(opt)
+        seeded = seeded_state(model, opt) if dump_dir else None    # before the first step
         bsz = args.batch
         if scaling == "strong":
             # the reference shards ONE global batch: per-rank batch = global // world (data/data_loader.py:40-48)
@@ -536,7 +610,7 @@ def main():
         else:
             run = step
         timer = None
-        if not args.no_kernel_timer and not use_graph:
+        if kernel_timer and not use_graph:
             timer = _lib.KernelTimer(CONV_CALLS)
             _lib.TIMER = timer
         barrier()
@@ -564,7 +638,17 @@ def main():
             raise RuntimeError("bench.py: invalid step on some rank -- %s%s (rank %d: final loss %r, LSTM status words %r)" %
                                ("non-finite loss " if bad & 1 else "", "persistent-kernel (LSTM / decode) timeout" if bad & 2 else "", rank,
                                 final_loss, lstm_words))
-        if use_graph and not args.no_kernel_timer:
+        if dump_dir:
+            # one more step of the timed path, untimed, from the seeded starting state (every rank: the step may hold
+            # collectives); written before the kernel-timer pass below runs further steps
+            restore_seeded_state(model, opt, seeded)
+            dump_loss = float(run().detach())
+            barrier()
+            if not math.isfinite(dump_loss):
+                raise RuntimeError("bench.py: non-finite loss in the step replayed for --dump-outputs (%r)" % dump_loss)
+            if rank == 0:
+                dump_outputs(dump_dir, dump_loss, model)
+        if use_graph and kernel_timer:
             # HIP events cannot bracket kernels inside a graph replay: measure the dominant kernel's launch durations
             # on the same stream with the same tensors in an eager pass right after the timed region
             # (deferred weight-gradient problems are launched grouped, from mr_tn_flush: an event bracket around the recording
@@ -741,8 +825,8 @@ def main():
             out = None
         return out
 
-    out = measure(args.workload, args.steps, args.warmup, not args.no_cpu_baseline)
-    if out is not None and world == 1 and not distributed and args.workload == "crnn" and not args.no_secondary:
+    out = measure(args.workload, args.steps, args.warmup, args.full and not args.no_cpu_baseline, dump_dir=args.dump_outputs)
+    if args.full and out is not None and world == 1 and not distributed and args.workload == "crnn" and not args.no_secondary:
         # the other three published configurations ride along in the default single-GPU line: BASELINE.json north_star
         # target #2 (configs[2], also kept under the round-1..3 key `secondary`), configs[3] and configs[4]; each with its own
         # roofline block and CPU baseline
@@ -756,7 +840,7 @@ def main():
             sec["workload"] = (wl if crop is None else "%s_%dx%d" % (wl, crop[0], crop[1])) + ("_random_coins" if coins == "random" else "")
             out["secondaries"].append(sec)
         out["secondary"] = out["secondaries"][0]
-    if world > 1 and args.scaling == "weak" and not args.no_strong:
+    if args.full and world > 1 and args.scaling == "weak" and not args.no_strong:
         # N > 1: the same line also carries the STRONG-scaling measurement -- the workload's global batch (256 crops) sharded
         # over the ranks as the reference's loader does (data/data_loader.py:40-48) -- whichever --scaling the driver passed
         # (VERDICT r4 item 9).  A second model / optimizer / captured step in the same process; a failure is reported, not fatal.

@@ -52,6 +52,7 @@ def test_yaml_to_trainer_train_step_reaches_the_hip_op(tmp_path):
                         'length': torch.tensor(5, dtype=torch.int32)}
     '''))
     out = _run('''
+        import os
         import megreader_amd.dropin as dropin
         installed = dropin.install(%r)
         assert "crnn_backbone" in installed["backbones"] and "CRNNDecoder" in installed["decoders"]
@@ -67,6 +68,8 @@ def test_yaml_to_trainer_train_step_reaches_the_hip_op(tmp_path):
                                       'dataset': {'class': 'b6_synth.SyntheticRecognitionDataset', 'size': 8}}
         ea['validation'] = None
         ea['evaluation'] = None
+        # concern/log.py:37 stores the logs under config.db_path (/data/workspace); keep them in the test's own directory
+        ea['logger']['database_dir'] = os.path.join(os.getcwd(), 'log_storage')
         ea.update(cmd={'distributed': False, 'local_rank': 0, 'debug': False, 'validate': False, 'visualize': False,
                        'verbose': False, 'batch_size': 4, 'num_workers': 0})
         experiment = Configurable.construct_class_from_config(ea)                             # train.py:60

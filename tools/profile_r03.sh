@@ -4,7 +4,7 @@
 # Outputs: gpurun_out/r03p/ (copy what should be judged into profiles/).   usage: bash tools/profile_r03.sh [quick]
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r03p; mkdir -p $O
-timeout 600 python bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/bench_default.json; cut -c1-260 $O/bench_default.json
+timeout 600 python bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/bench_default.json; cut -c1-260 $O/bench_default.json
 for w in crnn res50ppm fpn_attention db; do
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_$w -- python bench.py --workload $w --no-cpu-baseline --no-secondary --no-kernel-timer --steps 10 --warmup 3 > $O/trace_$w.log 2>&1
   db=$(find $O/trace_$w -name "*.db" | head -1)
@@ -24,7 +24,7 @@ for w in crnn res50ppm; do
 done
 fi
 for w in fpn_attention db; do
-  timeout 400 python bench.py --workload $w --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_$w.log 2>&1; tail -1 $O/bench_$w.log > $O/bench_$w.json; cut -c1-200 $O/bench_$w.json
+  timeout 400 python bench.py --full --workload $w --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_$w.log 2>&1; tail -1 $O/bench_$w.log > $O/bench_$w.json; cut -c1-200 $O/bench_$w.json
 done
 timeout 300 python tools/microbench_dcn.py --batch 16 2>&1 | grep -v amdgpu.ids > $O/dcn_microbench_b16.txt; tail -1 $O/dcn_microbench_b16.txt
 timeout 300 python tools/microbench_dcn.py --batch 2 2>&1 | grep -v amdgpu.ids > $O/dcn_microbench_b2.txt; tail -1 $O/dcn_microbench_b2.txt

@@ -8,7 +8,7 @@
 # usage: bash tools/profile_r04.sh [quick]      (quick: no PMC passes)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04p; mkdir -p $O
-timeout 900 python bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/bench_default.json; cut -c1-200 $O/bench_default.json
+timeout 900 python bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/bench_default.json; cut -c1-200 $O/bench_default.json
 trace() {   # name, bench args...
   local name=$1; shift
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_$name -- python bench.py "$@" --no-cpu-baseline --no-secondary --no-kernel-timer --steps 10 --warmup 3 > $O/trace_$name.log 2>&1
@@ -20,7 +20,7 @@ trace() {   # name, bench args...
 for w in crnn res50ppm fpn_attention db; do trace $w --workload $w; done
 for b in 128 64 32; do
   trace crnn_b$b --workload crnn --batch $b
-  timeout 200 python bench.py --workload crnn --batch $b --no-cpu-baseline --no-secondary --steps 40 --warmup 5 > $O/bench_crnn_b$b.log 2>&1; tail -1 $O/bench_crnn_b$b.log > $O/bench_crnn_b$b.json; cut -c1-160 $O/bench_crnn_b$b.json
+  timeout 200 python bench.py --full --workload crnn --batch $b --no-cpu-baseline --no-secondary --steps 40 --warmup 5 > $O/bench_crnn_b$b.log 2>&1; tail -1 $O/bench_crnn_b$b.log > $O/bench_crnn_b$b.json; cut -c1-160 $O/bench_crnn_b$b.json
 done
 if [ "$1" != "quick" ]; then
 for w in crnn res50ppm; do

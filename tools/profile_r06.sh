@@ -65,9 +65,9 @@ for wl in "crnn" "crnn --batch 32" "res50ppm" "fpn_attention" "db"; do
   done
 done
 } > $O/ab_world_gt1_configuration.txt 2>&1
-RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 timeout 300 python bench.py --force-ddp --ddp-mode capture --no-cpu-baseline --no-secondary --steps 20 --warmup 5 > $O/bench_force_ddp_capture.json 2> $O/bench_force_ddp_capture.err
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --steps 20 --warmup 5 --no-secondary --no-cpu-baseline > $O/bench_torchrun_n1.json 2> $O/bench_torchrun_n1.err
-timeout 300 python bench.py --workload res50ppm --dtype f32 --no-secondary --steps 10 --warmup 3 > $O/bench_res50ppm_f32.json 2> $O/bench_res50ppm_f32.err
+RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 timeout 300 python bench.py --full --force-ddp --ddp-mode capture --no-cpu-baseline --no-secondary --steps 20 --warmup 5 > $O/bench_force_ddp_capture.json 2> $O/bench_force_ddp_capture.err
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-secondary --no-cpu-baseline > $O/bench_torchrun_n1.json 2> $O/bench_torchrun_n1.err
+timeout 300 python bench.py --full --workload res50ppm --dtype f32 --no-secondary --steps 10 --warmup 3 > $O/bench_res50ppm_f32.json 2> $O/bench_res50ppm_f32.err
 tools/mfma_ceiling > $O/mfma_ceiling.txt 2>&1
 timeout 300 python tools/microbench_lstm.py --phases 2>&1 | grep -v amdgpu.ids > $O/lstm_phases.txt
 # the persistent decode kernels beside the per-step launches they replace, with the kernels' own phase clock
@@ -87,5 +87,5 @@ for tf in "" "--teacher-forcing random"; do
   done
 done
 } > $O/decode_persist_microbench.txt 2>&1
-python bench.py > $O/bench_default_final.json 2> $O/bench_default_final.err
+python bench.py --full > $O/bench_default_final.json 2> $O/bench_default_final.err
 echo extras done
