@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 3   /* 3 (round 6): mr_tuning grew (nt_m32, nt_m32_opt, reserved[6]).  2 (round 5): mr_ctc_fwd gained log_probs_f64; mr_tuning.tn_defer; mr_tn_defer / mr_tn_flush;
+#define MR_ABI_VERSION 3   /* 3 (round 6): mr_tuning grew (nt_m32, nt_m32_opt, reserved[3]).  2 (round 5): mr_ctc_fwd gained log_probs_f64; mr_tuning.tn_defer; mr_tn_defer / mr_tn_flush;
                               the 26 mr_set_* setters of version 1 are gone (mr_tuning) */
 #define MR_DTYPE_F32 0
 #define MR_DTYPE_BF16 1

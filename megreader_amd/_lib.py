@@ -16,127 +16,76 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "megreader_hip.h")
 
 MR_F32 = 0
 MR_BF16 = 1
-ABI_VERSION = 3     # include/megreader_hip.h: MR_ABI_VERSION
 
-_P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double
-_CODES = {"p": _P, "i": _I, "l": _L, "f": _F, "d": _D, "s": _P}
+# The binding is DERIVED from the header: the closed tables below are all this file knows about C.  A type that is not in them
+# raises -- a silent default (ctypes' own is `int`) would turn a new `long long` into a truncated size.
+_PARAM_TYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
+                "hipStream_t": ctypes.c_void_p}
+_RETURN_TYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "const char*": ctypes.c_char_p}
 
-# name -> argument codes (p pointer, i int, l long long, f float, s hipStream_t)
-SIGNATURES = {
-    "mr_gemm_nt": "iplpiplpiiiis",
-    "mr_gemm_tn": "iplplpiiiiips",
-    "mr_gemm_tn2": "iplplpiiiiipps",
-    "mr_conv2d_fwd": "ipppp" + "i" * 18 + "s",
-    "mr_conv2d_fwd_pool": "ippppp" + "i" * 25 + "s",
-    "mr_conv2d_fwd_stats": "ippppp" + "i" * 16 + "s",
-    "mr_bn_stats": "ipplis",
-    "mr_conv2d_dgrad": "ippp" + "i" * 17 + "s",
-    "mr_conv2d_dgrad_add": "ipppp" + "i" * 17 + "s",
-    "mr_conv2d_dgrad_bnb": "ippppppppp" + "p" + "i" * 17 + "s",
-    "mr_conv2d_wgrad": "ipppp" + "i" * 17 + "s",
-    "mr_conv2d_wgrad_tab": "ipppp" + "i" * 17 + "pis",
-    "mr_nchw_to_nhwc": "ippiiiiis",
-    "mr_nhwc_to_nchw": "ippiiiiis",
-    "mr_cast": "ipipls",
-    "mr_relu_bwd": "ipppls".replace(" ", ""),
-    "mr_add": "ippplis",
-    "mr_colsum": "ippiilis",
-    "mr_permute_021": "ippiiis",
-    "mr_prep_conv_weight": "ipllllppiiiiiis",
-    "mr_prep_matrix": "ipipipiiiis",
-    "mr_prep_bias": "pppiis",
-    "mr_prep_batch": "ipilps",
-    "mr_opt_tick": "ps",
-    "mr_accumulate_multi": "ippps",
-    "mr_zero_multi": "ipps",
-    "mr_adaptive_avgpool_multi_fwd": "ippppiiiiis",
-    "mr_adaptive_avgpool_multi_bwd": "ipppipiiiis",
-    "mr_adam_step": "pppplps",
-    "mr_sgd_step": "ppplps",
-    "mr_bn_fwd_train": "ipppppppppp" + "iliffps",
-    "mr_bn_fwd_eval": "ippppppppp" + "ilifs",
-    "mr_bn_bwd": "ipppppppppp" + "pilis",
-    "mr_stem_pack": "pllllpis",
-    "mr_stem_fwd": "ippllllppppiiiis",
-    "mr_stem_bwd": "ipppppllllpiiiis",
-    "mr_maxpool_fwd": "ippp" + "i" * 12 + "s",
-    "mr_maxpool_bwd": "ipppp" + "i" * 12 + "s",
-    "mr_lstm_fwd": "ipppppiiipls",
-    "mr_lstm_bwd": "ipppppiiipls",
-    "mr_ctc_fwd": "ipipippiiiiiiipppppps",
-    "mr_ctc_bwd": "ipppppippipiiiiiipis",
-    "mr_softmax_nc1t": "ipipiiis",
-    "mr_adaptive_avgpool_fwd": "ippiiiiiis",
-    "mr_adaptive_avgpool_bwd": "ippiiiiiis",
-    "mr_bilinear_fwd": "ipp" + "i" * 9 + "s",
-    "mr_bilinear_bwd": "ipp" + "i" * 8 + "s",
-    "mr_nearest_up_fwd": "ippp" + "i" * 7 + "s",
-    "mr_nearest_up_bwd": "ipp" + "i" * 7 + "s",
-    "mr_copy_channels": "ipiipiilis",
-    "mr_deconv2x2_d2s": "ipippiiiis",
-    "mr_deconv2x2_s2d": "ippiiiiis",
-    "mr_scale_channels": "ipppilis",
-    "mr_ctc2d_head_fwd": "ipipipppiiiifs",
-    "mr_ctc2d_head_bwd": "ippppipiiiiifs",
-    "mr_dcn2_im2col": "ipplplp" + "i" * 11 + "s",
-    "mr_dcn2_coord_grad": "ippplplpp" + "i" * 11 + "s",
-    "mr_dcn2_col2im": "ipplplp" + "i" * 11 + "s",
-    "mr_dcn2_fwd": "ippp" + "plpl" + "pp" + "i" * 12 + "s",
-    "mr_dcn2_bwd": "ippp" + "plpl" + "pppppp" + "i" * 12 + "s",
-    "mr_dcn2_bwd2": "ippp" + "plpl" + "pppi" + "pppp" + "i" * 12 + "s",
-    "mr_dcn2_bwd3": "ippp" + "plpl" + "pppi" + "pppp" + "p" + "i" * 12 + "s",
-    "mr_dcn_unpack": "ipippiiiis",
-    "mr_dcn_pack_grad": "ippppiiiiis",
-    "mr_db_components": "pfpppiiii" + "s",
-    "mr_db_box_scores": "pppiiii" + "s",
-    "mr_deform_psroi_fwd": "ppppp" + "iiiiiii" + "f" + "iiiii" + "f" + "s",
-    "mr_deform_psroi_bwd": "ppppppp" + "iiiiiii" + "f" + "iiiii" + "f" + "s",
-    "mr_attn_step_fwd": "ipppppp" + "iiii" + "s",
-    "mr_attn_step_bwd": "ippppppppppp" + "iiii" + "s",
-    "mr_gru_gates_fwd": "ippppppiis",
-    "mr_gru_gates_bwd": "ipppppppiis",
-    "mr_embed_rows_fwd": "ipppiiiis",
-    "mr_embed_rows_bwd": "ipppiiiis",
-    "mr_attn_fwd2": "iplpppppiiiis",
-    "mr_attn_bwd2": "ipplplppppplppiiiis",
-    "mr_attn_denc": "ipppiiiis",
-    "mr_gru_fwd2": "iplppplpppiis",
-    "mr_gru_bwd2": "ippppplppplpiis",
-    "mr_rows_scatter_add": "ipplpiiis",
-    "mr_scatter_strided": "ippiiiiiiiis",
-    "mr_gemm_gru_fwd": "iplplplpplpppiiis",
-    "mr_gemm_gru_bwd": "iplplpppplppplpiiis",
-    "mr_decode_persist_fwd": "ppp" + "l" + "p" + "l" + "pppp" + "i" + "p" * 9 + "l" + "iiii" + "s",
-    "mr_decode_persist_bwd": "pp" + "l" + "p" * 9 + "l" + "p" * 7 + "l" + "iiii" + "s",
-    "mr_out_nll_fwd": "iplplpplpppppp" + "iiiis",
-    "mr_nll_step_fwd": "ipiplppppiiiis",
-    "mr_nll_step_feed_fwd": "ipiplpppppp" + "iiis",
-    "mr_nll_step_bwd": "ippplppiiis",
-    "mr_ctc_greedy_decode": "iplll" + "iiiii" + "pps",
-    "mr_ctc2d_greedy_decode": "pllllplll" + "iiiiii" + "pps",
-    "mr_seq_measure": "pipiiiippppps",
-    "mr_resize_normalize": "ppiiidddps",
-    "mr_encode_labels": "ppiippiipps",
-    "mr_ctc2d_fwd": "ippppiiiiiipps",
-    "mr_ctc2d_bwd": "ippppppppp" + "iiiiiis",
-    "mr_tn_flush": "s",
-    "mr_tn_flush_beside": "s",
-    "mr_db_loss_fwd": "pppppppppp" + "ilffffs",
-    "mr_db_head_tail_fwd": "ippppplfs",
-    "mr_db_head_tail_bwd": "i" + "pppppppp" + "lfs",
-    "mr_db_loss_bwd": "pppppppppppp" + "ilffs",
-}
+
+def _ctype(decl, context, array_ok=False):
+    """(name, ctypes type, is a hipStream_t) of one parameter `TYPE name` or struct field `TYPE name` / `TYPE name[N]`."""
+    m = re.fullmatch(r"(.*?)(\w+)(?:\[(\d+)\])?", decl.strip(), re.S)
+    base = " ".join(m.group(1).split()) if m else ""
+    ctype = ctypes.c_void_p if "*" in base else _PARAM_TYPES.get(base)
+    if ctype is None or (m.group(3) and not array_ok):
+        raise TypeError("cannot bind %r in `%s`: no ctypes mapping for that type" % (decl.strip(), " ".join(context.split())))
+    return m.group(2), ctype * int(m.group(3)) if m.group(3) else ctype, base == "hipStream_t"
+
+
+def parse_header(text):
+    """Read a C-ABI header of this project: ({function: (restype, [argtypes], takes a trailing hipStream_t)},
+    {struct: [(field, ctypes type)]}, {integer #define: value}).  Everything that is not a comment, a preprocessor line, the
+    extern "C" bracket, a `typedef struct X {...} X;` or a declaration `RET mr_name(PARAMS);` over the closed type tables raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M).replace('extern "C" {', "")
+    structs = {}
+
+    def struct(m):
+        fields = structs[m.group(1)] = []
+        for stmt in filter(None, (s.strip() for s in m.group(2).split(";"))):
+            where = "struct %s { %s; }" % (m.group(1), stmt)
+            first, *more = stmt.split(",")                                   # `long long s0, s1, s2, s3`
+            name, ctype, _ = _ctype(first, where, True)
+            fields.append((name, ctype))
+            fields.extend(_ctype(first[:first.rindex(name)] + item, where, True)[:2] for item in more)
+        return ""
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", struct, text, flags=re.S)
+    functions = {}
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        if stmt == "}":                                                      # closes extern "C"
+            continue
+        m = re.fullmatch(r"(.*?)\b(mr_\w+)\s*\((.*)\)", stmt, re.S)
+        ret = re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())) if m else None
+        if ret not in _RETURN_TYPES or m.group(2) in functions:
+            raise TypeError("cannot bind `%s`: not a declaration `int | long long | const char* mr_name(...)`"
+                            % " ".join(stmt.split()))
+        params = [] if m.group(3).strip() in ("", "void") else [_ctype(p, stmt) for p in m.group(3).split(",")]
+        functions[m.group(2)] = (_RETURN_TYPES[ret], [p[1] for p in params], bool(params) and params[-1][2])
+    return functions, structs, defines
+
+
+def _read_header(path):
+    if not os.path.exists(path):
+        raise RuntimeError("C ABI header not found at %s -- the ctypes binding is derived from it (there is no fallback table)"
+                           % path)
+    with open(path) as f:
+        return parse_header(f.read())
+
+
+FUNCTIONS, STRUCTS, _DEFINES = _read_header(HEADER_PATH)
+ABI_VERSION = _DEFINES["MR_ABI_VERSION"]
+TUNING_FIELDS = tuple(name for name, _ in STRUCTS["mr_tuning"] if name != "reserved")
+_STREAMED = frozenset(name for name, (_, _, streamed) in FUNCTIONS.items() if streamed)     # what call() may launch
 
 _lib = None
-
-TUNING_FIELDS = ("nt_variant", "nt_deep", "nt_big", "nt_p8", "nt_force_bm", "nt_force_bn", "gemm_skinny", "tn_big", "tn_buf",
-                 "tn_taps", "tn_taps_group", "tn_group", "tn_fin", "tn_taps_fin", "tn_taps_w8", "tn_model", "tn_splits",
-                 "bn_fused", "lstm_persist", "lstm_fwd_bn", "lstm_bwd_bn", "dcn_fused", "dcn_v1_bwd", "bn_onepass", "skinny_depth", "nt_big_min_k", "tn_taps_min_p", "tn_defer", "pool_fixed", "ctc_linear", "nt_wide8", "nt_ksplit", "nt_m32", "nt_m32_opt", "dcn_gcol", "dcn_col_fwd", "decode_persist")
 
 
 class Tuning(ctypes.Structure):
     """struct mr_tuning (include/megreader_hip.h): the library's only process-wide switches."""
-    _fields_ = [(name, ctypes.c_int) for name in TUNING_FIELDS] + [("reserved", ctypes.c_int * 3)]
+    _fields_ = STRUCTS["mr_tuning"]
 
 
 def get_tuning():
@@ -217,14 +166,20 @@ def _install_setter_shims(lib):
 
 
 def header_symbols():
-    """Names of all `int mr_*(...)` entry points declared in include/megreader_hip.h."""
-    with open(HEADER_PATH) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"\bint\s+(mr_\w+)\s*\(", text)))
+    """Names of all entry points declared in include/megreader_hip.h."""
+    return sorted(FUNCTIONS)
+
+
+def _bind(lib, functions, optional=False):
+    for name, (restype, argtypes, _) in functions.items():
+        if optional and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
 
 
 def load():
-    """Load the shared library (once) and attach argument types.  Raises if it has not been built."""
+    """Load the shared library (once) and attach the argument types the header declares.  Raises if it has not been built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -233,77 +188,12 @@ def load():
             "libmegreader_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C megreader_amd/csrc` (there is no CPU fallback)" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    lib.mr_last_error.restype = ctypes.c_char_p
-    lib.mr_last_error.argtypes = []
-    lib.mr_abi_version.restype = ctypes.c_int
-    lib.mr_abi_version.argtypes = []
-    if lib.mr_abi_version() != ABI_VERSION:
+    if lib.mr_abi_version() != ABI_VERSION:             # int mr_abi_version(void): ctypes' defaults are its signature
         raise RuntimeError("%s implements C ABI version %d, this binding expects %d -- rebuild it (`make -C megreader_amd/csrc`)"
                            % (LIB_PATH, lib.mr_abi_version(), ABI_VERSION))
-    lib.mr_init.restype = ctypes.c_int
-    lib.mr_init.argtypes = []
-    lib.mr_nt_tile_code.restype = ctypes.c_int
-    lib.mr_nt_tile_code.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.mr_sizeof_prep_job.restype = ctypes.c_int
-    lib.mr_sizeof_prep_job.argtypes = []
-    lib.mr_nt_kernel_code.restype = ctypes.c_int
-    lib.mr_nt_kernel_code.argtypes = [ctypes.c_int] * 5
-    lib.mr_bn_scratch_doubles.restype = ctypes.c_longlong
-    lib.mr_bn_scratch_doubles.argtypes = [ctypes.c_int]
-    lib.mr_dcn2_ws_bytes.restype = ctypes.c_longlong
-    lib.mr_dcn2_ws_bytes.argtypes = [ctypes.c_int] * 11
-    lib.mr_dcn2_dx_direct.restype = ctypes.c_int
-    lib.mr_dcn2_dx_direct.argtypes = [ctypes.c_int] * 8
-    lib.mr_db_loss_ws_bytes.restype = ctypes.c_longlong
-    lib.mr_db_loss_ws_bytes.argtypes = []
-    lib.mr_dcn2_fused.restype = ctypes.c_int
-    lib.mr_dcn2_fused.argtypes = [ctypes.c_int] * 7
-    if hasattr(lib, "mr_set_tn_abl"):      # only libmegreader_hip_abl.so (tools build, include/megreader_hip_ablation.h)
-        lib.mr_set_tn_abl.restype = ctypes.c_int
-        lib.mr_set_tn_abl.argtypes = [ctypes.c_int]
-        lib.mr_set_tn_taps_abl.restype = ctypes.c_int
-        lib.mr_set_tn_taps_abl.argtypes = [ctypes.c_int]
-    lib.mr_set_tn_taps_workspace.restype = ctypes.c_int
-    lib.mr_set_tn_taps_workspace.argtypes = [ctypes.c_void_p, ctypes.c_longlong]
-    lib.mr_tn_taps_would_run.restype = ctypes.c_int
-    lib.mr_tn_taps_would_run.argtypes = [ctypes.c_int] * 17
-    lib.mr_lstm_debug_buffer.restype = ctypes.c_int
-    lib.mr_lstm_debug_buffer.argtypes = [ctypes.c_void_p]
-    lib.mr_lstm_ws_bytes.restype = ctypes.c_longlong
-    lib.mr_lstm_ws_bytes.argtypes = [ctypes.c_int] * 4
-    lib.mr_decode_persist_ok.restype = ctypes.c_int
-    lib.mr_decode_persist_ok.argtypes = [ctypes.c_int] * 5
-    lib.mr_decode_persist_ws_bytes.restype = ctypes.c_longlong
-    lib.mr_decode_persist_ws_bytes.argtypes = [ctypes.c_int]
-    lib.mr_decode_persist_bwd_ok.restype = ctypes.c_int
-    lib.mr_decode_persist_bwd_ok.argtypes = [ctypes.c_int] * 5
-    lib.mr_decode_persist_bwd_ws_bytes.restype = ctypes.c_longlong
-    lib.mr_decode_persist_bwd_ws_bytes.argtypes = [ctypes.c_int]
-    lib.mr_sizeof_img_desc.restype = ctypes.c_int
-    lib.mr_sizeof_img_desc.argtypes = []
-    lib.mr_tn_defer.restype = ctypes.c_int
-    lib.mr_tn_defer.argtypes = [ctypes.c_int]
-    lib.mr_tn_pending.restype = ctypes.c_int
-    lib.mr_tn_pending.argtypes = []
-    lib.mr_tn_discard.restype = ctypes.c_int
-    lib.mr_tn_discard.argtypes = []
-    lib.mr_dcn2_col_saved.restype = ctypes.c_int
-    lib.mr_dcn2_col_saved.argtypes = [ctypes.c_int] * 7
-    lib.mr_conv2d_fwd_pool_ok.restype = ctypes.c_int
-    lib.mr_conv2d_fwd_pool_ok.argtypes = [ctypes.c_int] * 23
-    lib.mr_phase_timer.restype = ctypes.c_int
-    lib.mr_phase_timer.argtypes = [ctypes.c_int]
-    lib.mr_phase_read.restype = ctypes.c_int
-    lib.mr_phase_read.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-    lib.mr_stem_bwd_workspace.restype = ctypes.c_longlong
-    lib.mr_stem_bwd_workspace.argtypes = [ctypes.c_int]
-    for name, codes in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = ctypes.c_int
-        fn.argtypes = [_CODES[c] for c in codes]
-    for name in ("mr_tuning_get", "mr_tuning_set", "mr_tuning_defaults"):
-        getattr(lib, name).restype = ctypes.c_int
-        getattr(lib, name).argtypes = [ctypes.POINTER(Tuning)]
+    _bind(lib, FUNCTIONS)
+    # only libmegreader_hip_abl.so (tools build) exports what include/megreader_hip_ablation.h declares
+    _bind(lib, _read_header(os.path.join(os.path.dirname(HEADER_PATH), "megreader_hip_ablation.h"))[0], optional=True)
     _install_setter_shims(lib)
     _lib = lib
     if torch.cuda.is_available():
@@ -316,13 +206,6 @@ def load():
         if "MEGREADER_TUNING" in err:
             raise RuntimeError("mr_init failed: %s" % err)
     return lib
-
-
-HOST_ONLY = ("mr_abi_version", "mr_nt_tile_code", "mr_init", "mr_tuning_get", "mr_tuning_set", "mr_tuning_defaults",
-             "mr_stem_bwd_workspace", "mr_lstm_ws_bytes", "mr_lstm_debug_buffer", "mr_dcn2_ws_bytes", "mr_bn_scratch_doubles",
-             "mr_sizeof_img_desc", "mr_nt_kernel_code", "mr_tn_taps_would_run", "mr_set_tn_taps_workspace",
-             "mr_sizeof_prep_job", "mr_tn_defer", "mr_tn_pending", "mr_tn_discard", "mr_phase_timer", "mr_phase_read", "mr_conv2d_fwd_pool_ok", "mr_dcn2_col_saved", "mr_dcn2_dx_direct", "mr_dcn2_fused", "mr_db_loss_ws_bytes", "mr_decode_persist_ok", "mr_decode_persist_ws_bytes", "mr_decode_persist_bwd_ok",
-             "mr_decode_persist_bwd_ws_bytes")  # entry points that take no stream and launch nothing
 
 
 def dtype_code(dtype):
@@ -392,36 +275,39 @@ def ensure_tn_workspace(device=None):
         if rc != 0:
             raise RuntimeError("mr_set_tn_taps_workspace failed: %s" % lib.mr_last_error().decode())
         if os.environ.get("MEGREADER_FAN", "0") == "1" or os.environ.get("MEGREADER_OVERLAP", "0") == "1":
-            lib.mr_set_tn_group(1)
-            lib.mr_set_tn_taps_group(1)
-            set_tuning(nt_ksplit=0)      # GEMMs of one layer on several streams: nobody may use the shared slabs / tickets
+            set_tuning(tn_group=1, tn_taps_group=1, nt_ksplit=0)      # GEMMs of one layer on several streams: nobody may use the shared slabs / tickets
     return ws
+
+
+def _bracketed(fn, args):
+    """fn(*args, stream) between two timing events on the current stream: (return code, start event, end event)."""
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    rc = fn(*args, stream_ptr())
+    e1.record()
+    return rc, e0, e1
 
 
 def call(name, *args):
     """Invoke a C entry point on torch's current HIP stream; raise RuntimeError on a non-zero return code."""
+    if name not in _STREAMED:
+        raise TypeError("%s is not an entry point with a trailing hipStream_t (include/megreader_hip.h): call() appends the "
+                        "stream; call host-only functions as load().%s(...)" % (name, name))
     lib = load()
     if name in _TN_WS_CALLS and torch.cuda.current_device() not in _TN_WS:
         ensure_tn_workspace()
     timer = TIMER
     if timer is not None and name in timer.names:
         pend = lib.mr_tn_pending() if timer.track_deferred else 0
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = getattr(lib, name)(*args, stream_ptr())
-        e1.record()
+        rc, e0, e1 = _bracketed(getattr(lib, name), args)
         if timer.track_deferred and lib.mr_tn_pending() > pend:
             timer.deferred.append((name, args))          # recorded, not launched: its time is the flush's
         else:
             timer.records.append((name, args, e0, e1))
     elif timer is not None and timer.track_deferred and name in ("mr_tn_flush", "mr_tn_flush_beside") and timer.deferred:
         group, timer.deferred = timer.deferred, []
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        rc = getattr(lib, name)(*args, stream_ptr())
-        e1.record()
+        rc, e0, e1 = _bracketed(getattr(lib, name), args)
         timer.records.append(("mr_tn_flush", group, e0, e1))
     else:
         rc = getattr(lib, name)(*args, stream_ptr())

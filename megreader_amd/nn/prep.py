@@ -20,20 +20,14 @@ import ctypes
 
 import torch
 
-from .._lib import call, dtype_code, ptr
+from .._lib import STRUCTS, call, dtype_code, ptr
 
 KIND_CONV, KIND_MATRIX, KIND_BIAS, KIND_STEM = 0, 1, 2, 3
 
 
 class PrepJob(ctypes.Structure):
-    """struct mr_prep_job (include/megreader_hip.h)."""
-    _fields_ = [("src", ctypes.c_void_p), ("src2", ctypes.c_void_p), ("dst_a", ctypes.c_void_p),
-                ("dst_b", ctypes.c_void_p), ("s0", ctypes.c_longlong), ("s1", ctypes.c_longlong),
-                ("s2", ctypes.c_longlong), ("s3", ctypes.c_longlong), ("kind", ctypes.c_int), ("d0", ctypes.c_int),
-                ("d1", ctypes.c_int), ("d2", ctypes.c_int), ("d3", ctypes.c_int), ("pad", ctypes.c_int),
-                ("ld_b", ctypes.c_int), ("perm_h", ctypes.c_int), ("block_start", ctypes.c_int),
-                ("reserved", ctypes.c_int)]
-
+    """struct mr_prep_job, field for field as include/megreader_hip.h declares it."""
+    _fields_ = STRUCTS["mr_prep_job"]
 
 
 def job_blocks(j):

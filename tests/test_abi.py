@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every symbol the header declares,
-the ctypes signature table is complete, module parameters mirror the reference's state_dict, and the product path
-refuses CPU tensors instead of silently falling back."""
+the ctypes binding derived from the header agrees with it position by position, module parameters mirror the
+reference's state_dict, and the product path refuses CPU tensors instead of silently falling back."""
+import ctypes
 import os
 import re
 
@@ -10,39 +11,120 @@ import torch
 from megreader_amd import _lib
 
 
+I, L, P, F, D = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
+
+
+def _header_code():
+    """The header without comments and struct bodies -- this file's own reading, independent of _lib.parse_header."""
+    with open(_lib.HEADER_PATH) as f:
+        code = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", code, flags=re.S)
+
+
 def test_library_exports_every_header_symbol():
     lib = _lib.load()
     syms = _lib.header_symbols()
-    assert len(syms) >= 25
+    # no declaration is skipped, whatever it returns: one name per `mr_xxx(` of the header
+    assert len(syms) == len(set(syms)) == len(re.findall(r"mr_\w+\s*\(", _header_code())) >= 130
     for s in syms:
         assert hasattr(lib, s), "libmegreader_hip.so does not export %s" % s
     assert lib.mr_abi_version() == 3 == _lib.ABI_VERSION
 
 
-def test_signature_table_matches_header():
-    with open(_lib.HEADER_PATH) as f:
-        text = f.read()
+LONG_LONG_FUNCTIONS = {"mr_db_loss_ws_bytes", "mr_bn_scratch_doubles", "mr_stem_bwd_workspace", "mr_lstm_ws_bytes",
+                       "mr_dcn2_ws_bytes", "mr_decode_persist_ws_bytes", "mr_decode_persist_bwd_ws_bytes"}
+
+
+def test_bound_signatures_match_header():
+    """restype and argtypes of EVERY entry point of the loaded library, host-only ones included, against the declaration text."""
+    lib = _lib.load()
+    code = _header_code()
+    seen_long_long = set()
     for name in _lib.header_symbols():
-        if name in _lib.HOST_ONLY:
-            continue
-        assert name in _lib.SIGNATURES, name
-        decl = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, text, re.S).group(1)
-        nargs = len([a for a in decl.split(",") if a.strip()])
-        assert nargs == len(_lib.SIGNATURES[name]), (name, nargs, len(_lib.SIGNATURES[name]))
+        found = re.findall(r"\b(int|long long|const char\s*\*)\s*%s\s*\(([^;]*?)\)\s*;" % name, code, re.S)
+        assert len(found) == 1, name
+        ret, decl = found[0]
+        fn = getattr(lib, name)
+        if ret == "long long":
+            seen_long_long.add(name)
+            assert fn.restype is L, name
+        else:
+            assert fn.restype is (I if ret == "int" else ctypes.c_char_p), name
+        params = [] if decl.strip() in ("", "void") else [a.strip() for a in decl.split(",")]
+        assert len(params) == len(fn.argtypes), (name, len(params), len(fn.argtypes))
         # pointer / integer / float kinds agree position by position
-        for code, arg in zip(_lib.SIGNATURES[name], [a.strip() for a in decl.split(",")]):
-            if code == "p":
-                assert "*" in arg, (name, arg)
-            elif code == "s":
-                assert "hipStream_t" in arg, (name, arg)
-            elif code == "l":
-                assert "long long" in arg and "*" not in arg, (name, arg)
-            elif code == "f":
-                assert arg.startswith("float") and "*" not in arg, (name, arg)
-            elif code == "d":
-                assert arg.startswith("double") and "*" not in arg, (name, arg)
+        for bound, arg in zip(fn.argtypes, params):
+            if "*" in arg or arg.startswith("hipStream_t"):
+                assert bound is P, (name, arg)
+            elif arg.startswith("long long"):
+                assert bound is L, (name, arg)
+            elif arg.startswith("float"):
+                assert bound is F, (name, arg)
+            elif arg.startswith("double"):
+                assert bound is D, (name, arg)
             else:
-                assert arg.startswith("int") and "*" not in arg, (name, arg)
+                assert arg.startswith("int ") and bound is I, (name, arg)
+    assert seen_long_long == LONG_LONG_FUNCTIONS
+    assert lib.mr_last_error.restype is ctypes.c_char_p
+
+
+# full signatures written out by hand: every parameter type, the longest declarations, every formerly unchecked class
+PINNED = {
+    "mr_gemm_nt": (I, [I, P, L, P, I, P, L, P, I, I, I, I, P]),
+    "mr_dcn2_bwd3": (I, [I, P, P, P, P, L, P, L, P, P, P, I, P, P, P, P, P] + [I] * 12 + [P]),
+    "mr_decode_persist_fwd": (I, [P, P, P, L, P, L, P, P, P, P, I] + [P] * 9 + [L, I, I, I, I, P]),
+    "mr_resize_normalize": (I, [P, P, I, I, I, D, D, D, P, P]),
+    "mr_db_loss_fwd": (I, [P] * 10 + [I, L, F, F, F, F, P]),
+    "mr_dcn2_ws_bytes": (L, [I] * 11),
+    "mr_conv2d_fwd_pool_ok": (I, [I] * 23),
+    "mr_phase_read": (I, [I, P, P]),
+    "mr_tn_pending": (I, []),
+    "mr_last_error": (ctypes.c_char_p, []),
+    "mr_tuning_set": (I, [P]),
+    "mr_set_tn_taps_workspace": (I, [P, L]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED))
+def test_pinned_signature(name):
+    fn = getattr(_lib.load(), name)
+    restype, argtypes = PINNED[name]
+    assert fn.restype is restype
+    assert list(fn.argtypes) == argtypes
+
+
+def test_reader_refuses_what_it_does_not_know():
+    ok = _lib.parse_header("int mr_x(int v, hipStream_t stream);\nlong long mr_y(void);")[0]
+    assert ok == {"mr_x": (I, [I, P], True), "mr_y": (L, [], False)}
+    for bad in ("int mr_x(unsigned short v, hipStream_t stream);",      # unknown parameter type
+                "float mr_x(int v);",                                   # unknown return type
+                "int mr_x(int);",                                       # no parameter name: nothing says `int` is the type
+                "int mr_x(int v[4]);",                                  # arrays only in structs
+                "typedef struct mr_s { short a; } mr_s;",               # unknown field type
+                "int mr_x(int v); int mr_x(long long v);",              # declared twice
+                "static int helper(int v);"):                           # not an entry point
+        with pytest.raises(TypeError) as e:
+            _lib.parse_header(bad)
+        assert "mr_" in str(e.value) or "helper" in str(e.value)        # the declaration is in the message
+
+
+def test_call_refuses_entry_points_without_a_stream(monkeypatch):
+    monkeypatch.setattr(_lib, "load", lambda: pytest.fail("call() reached the library"))
+    for name in ("mr_tn_pending", "mr_dcn2_ws_bytes", "mr_no_such_function"):
+        with pytest.raises(TypeError):
+            _lib.call(name)
+
+
+def test_pointer_parameters_take_byref_and_integers_refuse_floats():
+    lib = _lib.load()
+    ms, work = ctypes.c_double(-1.0), ctypes.c_double(-1.0)
+    assert lib.mr_phase_timer(0) in (0, 1)
+    assert lib.mr_phase_read(0, ctypes.byref(ms), ctypes.byref(work)) == 0     # timer off: no records
+    assert (ms.value, work.value) == (0.0, 0.0)
+    t = _lib.Tuning()
+    assert lib.mr_tuning_get(ctypes.byref(t)) == 0 and t.nt_variant in (1, 2)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.mr_nt_tile_code(128.0, 128)
 
 
 def test_no_torch_types_in_header():

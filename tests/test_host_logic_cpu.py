@@ -17,6 +17,10 @@ def test_prep_job_struct_mirror_matches_the_library():
     from megreader_amd.nn import prep
     lib = _lib.load()
     assert ctypes.sizeof(prep.PrepJob) == lib.mr_sizeof_prep_job()
+    assert [n for n, _ in prep.PrepJob._fields_] == [
+        "src", "src2", "dst_a", "dst_b", "s0", "s1", "s2", "s3", "kind", "d0", "d1", "d2", "d3", "pad", "ld_b", "perm_h",
+        "block_start", "reserved"]
+    assert [t for _, t in prep.PrepJob._fields_] == [ctypes.c_void_p] * 4 + [ctypes.c_longlong] * 4 + [ctypes.c_int] * 10
     # every key a job description carries is a struct field (or the host-only element count)
     for job in (prep.conv_job(1, (27, 1, 9, 3), 2, 3, 64, 3, 3, 3, 8, 64),
                 prep.matrix_job(1, 512, 2, 512, 3, 1024, 1024, 512, 256),

@@ -27,6 +27,12 @@ def test_struct_layout_matches_the_header():
     import ctypes
     assert ctypes.sizeof(_lib.Tuning) == 4 * n_ints
     assert fields[-1][0] == "reserved"
+    assert _lib.Tuning._fields_[-1][0] == "reserved" and len(_lib.Tuning._fields_) == len(fields)
+    # written out by hand, independent of any reading of the header
+    assert len(_lib.TUNING_FIELDS) == 37
+    assert _lib.TUNING_FIELDS[:3] == ("nt_variant", "nt_deep", "nt_big")
+    assert _lib.TUNING_FIELDS[-3:] == ("dcn_gcol", "dcn_col_fwd", "decode_persist")
+    assert ctypes.sizeof(_lib.Tuning) == 160 and _lib.Tuning.reserved.offset == 148
 
 
 def test_defaults_set_get_and_range_errors():
