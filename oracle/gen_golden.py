@@ -20,7 +20,7 @@ from oracle import refimport  # noqa: E402
 from oracle.crnn import CRNNOracle, synthetic_batch  # noqa: E402
 from oracle.decode import greedy_decode  # noqa: E402
 
-GOLDEN = os.path.join(REPO, "tests", "golden")
+GOLDEN = os.environ.get("MEGREADER_GOLDEN_OUT") or os.path.join(REPO, "tests", "golden")   # (another directory: a dry run)
 WEIGHT_SEED = 1234
 
 
@@ -28,29 +28,30 @@ def checksums(state):
     return {k: (float(v.double().sum()), float(v.double().abs().sum())) for k, v in state.items()}
 
 
-def crnn_fixture():
-    torch.set_num_threads(4)
+def _crnn_pair(weight_seed, class_count=None):
+    """The unmodified reference CRNN model and the oracle on the same seeded weights (checked equal).  class_count None: the
+    oracle's default.  Returns (ref, ora, charset, ref_state, out) with `out` holding the seed, keys and checksums."""
     sm = refimport.import_reference()
     from concern.charsets import EnglishCharset
-    from structure.representers.ctc_representer import CTCRepresenter
     charset = EnglishCharset()
     args = {'backbone': 'crnn_backbone', 'decoder': 'CRNNDecoder',
             'decoder_args': {'in_channels': 512, 'inner_channels': 256, 'need_reduce': False, 'charset': charset}}
-
-    torch.manual_seed(WEIGHT_SEED)
+    torch.manual_seed(weight_seed)
     ref = sm.SequenceRecognitionModel(args, torch.device('cpu'))  # structure/model.py:160-181 (DataParallel on CPU)
-    torch.manual_seed(WEIGHT_SEED)
-    ora = CRNNOracle(num_classes=len(charset))
+    torch.manual_seed(weight_seed)
+    ora = CRNNOracle() if class_count is None else CRNNOracle(num_classes=class_count(charset))
     ref_state = {k.replace('model.module.', ''): v for k, v in ref.state_dict().items()}
     assert list(ref_state.keys()) == list(ora.state_dict().keys()), "state_dict keys differ"
     for k, v in ora.state_dict().items():
         assert torch.equal(v, ref_state[k]), "seeded init differs at %s" % k
+    out = {'weight_seed': weight_seed, 'state_checksums': checksums(ref_state), 'state_keys': list(ref_state.keys())}
+    return ref, ora, charset, ref_state, out
 
-    batch = synthetic_batch(3, height=32, width=64, seed=7)
-    out = {'weight_seed': WEIGHT_SEED, 'batch': batch, 'state_checksums': checksums(ref_state),
-           'state_keys': list(ref_state.keys()), 'state_shapes': {k: tuple(v.shape) for k, v in ref_state.items()}}
 
-    # ---- training forward / backward through the reference wrapper (batch dict in, (loss, pred) out)
+def _crnn_first_step(ref, ora, batch, out):
+    """Training forward / backward through the reference wrapper (batch dict in, (loss, pred) out) and through the oracle; refuses
+    anything but bit-equality; records loss, gradient statistics and the BN running statistics after the forward in `out`.
+    Returns the reference's log-probabilities."""
     ref.train()
     ora.train()
     loss_r, pred_r = ref.forward(dict(batch), training=True)
@@ -62,11 +63,40 @@ def crnn_fixture():
     for k, p in ora.named_parameters():
         assert torch.equal(p.grad, grads_r[k]), "oracle grad != reference at %s" % k
     out['train_loss'] = loss_r.detach().clone()
-    out['train_log_probs'] = pred_r.detach().clone()
     out['grad_stats'] = {k: (float(g.double().norm()), g.flatten()[:8].clone()) for k, g in grads_r.items()}
     # BN running stats after one training forward
-    out['bn_after'] = {k.replace('model.module.', ''): v.clone() for k, v in ref.state_dict().items()
-                       if 'running' in k}
+    out['bn_after'] = {k.replace('model.module.', ''): v.clone() for k, v in ref.state_dict().items() if 'running' in k}
+    for k, v in ora.state_dict().items():
+        if 'running' in k:
+            assert torch.equal(v, out['bn_after'][k]), "oracle BN statistics != reference at %s" % k
+    return pred_r.detach()
+
+
+def _crnn_eval(ref, ora, charset, batch, out):
+    """Eval forward + greedy decode (structure/representers/ctc_representer.py:20-34), reference == oracle; returns the strings."""
+    from structure.representers.ctc_representer import CTCRepresenter
+    ref.eval()
+    ora.eval()
+    with torch.no_grad():
+        ev_r = ref.forward(dict(batch), training=False)
+        ev_o = ora(batch['image'], train=False)
+    assert torch.equal(ev_r, ev_o), "oracle eval != reference"
+    strings = CTCRepresenter(charset=charset).represent(batch, ev_r)
+    dec = greedy_decode(ev_r.numpy())
+    assert [charset.label_to_string(d) for d in dec] == [s['pred_string'] for s in strings], "decode differs"
+    out['eval_pred'] = ev_r.clone()
+    out['eval_decode'] = torch.from_numpy(dec)
+    out['eval_strings'] = [s['pred_string'] for s in strings]
+    return strings
+
+
+def crnn_fixture():
+    torch.set_num_threads(4)
+    ref, ora, charset, ref_state, out = _crnn_pair(WEIGHT_SEED, class_count=len)
+    batch = synthetic_batch(3, height=32, width=64, seed=7)
+    out['batch'] = batch
+    out['state_shapes'] = {k: tuple(v.shape) for k, v in ref_state.items()}
+    out['train_log_probs'] = _crnn_first_step(ref, ora, batch, out).clone()
 
     # ---- three Adam steps (experiments/recognition/crnn.yaml:82-89: Adam, lr 1e-3) -- loss trajectory
     opt_r = torch.optim.Adam(ref.parameters(), lr=1e-3)
@@ -88,25 +118,37 @@ def crnn_fixture():
     assert traj_r == traj_o, "oracle Adam trajectory != reference: %s vs %s" % (traj_r, traj_o)
     out['adam_losses'] = traj_r
 
-    # ---- eval forward + greedy decode (structure/representers/ctc_representer.py:20-34)
-    ref.eval()
-    ora.eval()
-    with torch.no_grad():
-        ev_r = ref.forward(dict(batch), training=False)
-        ev_o = ora(batch['image'], train=False)
-    assert torch.equal(ev_r, ev_o), "oracle eval != reference"
-    rep = CTCRepresenter(charset=charset)
-    strings = rep.represent(batch, ev_r)
-    dec = greedy_decode(ev_r.numpy())
-    assert [charset.label_to_string(d) for d in dec] == [s['pred_string'] for s in strings], "decode differs"
-    out['eval_pred'] = ev_r.clone()
-    out['eval_decode'] = torch.from_numpy(dec)
-    out['eval_strings'] = [s['pred_string'] for s in strings]
+    strings = _crnn_eval(ref, ora, charset, batch, out)
     out['label_strings'] = [s['label_string'] for s in strings]
     os.makedirs(GOLDEN, exist_ok=True)
     path = os.path.join(GOLDEN, "crnn_golden.pt")
     torch.save(out, path)
-    print("wrote", path, os.path.getsize(path), "bytes; loss", float(loss_r), "adam", traj_r)
+    print("wrote", path, os.path.getsize(path), "bytes; loss", float(out['train_loss']), "adam", traj_r)
+
+
+C0_WEIGHT_SEED, C0_BATCH = 4321, (16, 32, 100, 11)   # tests/_cases.py crnn_c0: weights seed, synthetic_batch(n, height, width, seed)
+
+
+def crnn_c0_fixture():
+    """The CRNN at the published 32x100 gray crop, N = 16 (the case tests/_cases.py calls crnn_c0): the
+    unmodified reference and the oracle on the same seeded weights and batch, first training step + eval.  The file holds the
+    gray plane only (the network is fed that plane three times), the seed and the checksums of the weights, and the outputs."""
+    torch.set_num_threads(4)
+    ref, ora, charset, _state, out = _crnn_pair(C0_WEIGHT_SEED)     # default class count, as the shared case builds it
+    n, height, width, seed = C0_BATCH
+    batch = synthetic_batch(n, height, width, seed=seed)
+    gray = batch['image'][:, :1].contiguous()
+    batch = dict(batch, image=gray.expand(-1, 3, -1, -1).contiguous())
+    out.update(batch_args=C0_BATCH, gray=gray, label=batch['label'], length=batch['length'])
+    pred_r = _crnn_first_step(ref, ora, batch, out)
+    out['train_log_probs'] = pred_r.float().clone()      # f32 values widened by the reference: stored as f32, exactly
+    assert torch.equal(out['train_log_probs'].double(), pred_r)
+    _crnn_eval(ref, ora, charset, batch, out)
+    os.makedirs(GOLDEN, exist_ok=True)
+    path = os.path.join(GOLDEN, "crnn_c0_golden.pt")
+    torch.save(out, path)
+    assert os.path.getsize(path) < 1000000, os.path.getsize(path)
+    print("wrote", path, os.path.getsize(path), "bytes; loss", float(out['train_loss']))
 
 
 def ctc2d_fixture():
@@ -330,9 +372,11 @@ if __name__ == "__main__":
     if not refimport.available():
         raise SystemExit("reference not available: golden vectors can only be regenerated in the build container")
     os.chdir("/tmp")
-    which = sys.argv[1:] or ["crnn", "ctc2d", "res50ppm", "fpn_attention", "deformable_resnet"]
+    which = sys.argv[1:] or ["crnn", "crnn_c0", "ctc2d", "res50ppm", "fpn_attention", "deformable_resnet"]
     if "crnn" in which:
         crnn_fixture()
+    if "crnn_c0" in which:
+        crnn_c0_fixture()
     if "ctc2d" in which:
         ctc2d_fixture()
     if "res50ppm" in which:

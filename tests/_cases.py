@@ -1,4 +1,5 @@
-"""The four published configurations (BASELINE.json configs[1..4] = what bench.py times) as memoised oracle runs, shared by
+"""The published configurations (BASELINE.json configs[1..4] = what bench.py times, and configs[0], the CRNN at its 32x100 gray
+crop) as memoised oracle runs, shared by
 tests/test_timed_step_gpu.py, tests/test_published_configs_gpu.py and tests/test_fullsize_parity_gpu.py so that the CPU
 oracle (float32 = the reference's arithmetic, float64 = ground truth of the gradient bars, tests/_parity.py) runs ONCE per
 configuration and process.  Each case returns a dict:
@@ -124,7 +125,9 @@ def _recognition_loss(model, b):
 
 
 # ------------------------------------------------------------------------------------------------ configs[1]: CRNN, N = 256
-def crnn_n256_hip():
+def _crnn_case_hip(n, width, gray, batch_seed, max_len, what):
+    """The HIP side of one CRNN case: weights torch.manual_seed(4321), batch synthetic_batch(n, 32, width, seed=batch_seed[,
+    max_len]); gray = the first plane replicated three times (BASELINE.md row C1 feeds a gray crop to the 3-channel network)."""
     from megreader_amd.backbones import crnn_backbone
     from megreader_amd.decoders import CRNNDecoder
     from megreader_amd.optim import FusedAdam
@@ -142,7 +145,11 @@ def crnn_n256_hip():
     torch.manual_seed(4321)
     ora = CRNNOracle()
     state0 = {k: v.clone() for k, v in ora.state_dict().items()}
-    batch = synthetic_batch(256, 32, 128, seed=11)
+    batch = synthetic_batch(n, 32, width, seed=batch_seed) if max_len is None else \
+        synthetic_batch(n, 32, width, seed=batch_seed, max_len=max_len)
+    if gray:
+        batch = dict(batch)
+        batch['image'] = batch['image'][:, :1].expand(-1, 3, -1, -1).contiguous()
 
     def build():
         m = Model()
@@ -150,13 +157,16 @@ def crnn_n256_hip():
         return m.to(DEV).train()
 
     return dict(ora=ora, state0=state0, batch=batch, build=build, loss_fn=_recognition_loss,
-                optimizer=lambda ps: FusedAdam(ps, lr=0.0), what="CRNN fp32 32x128 N=256")
+                optimizer=lambda ps: FusedAdam(ps, lr=0.0), what=what)
 
 
-def crnn_n256():
-    if "crnn" in _CACHE:
-        return _CACHE["crnn"]
-    c = crnn_n256_hip()
+def _crnn_case(n, width, gray=False, batch_seed=11, max_len=None, what=None, key=None):
+    """_crnn_case_hip + the oracle passes (f64 gradients, f32 training forward/backward, BN state after it, eval), memoised."""
+    what = what or "CRNN fp32 32x%d N=%d" % (width, n)
+    key = key or ("crnn", n, width, bool(gray), batch_seed, max_len)
+    if key in _CACHE:
+        return _CACHE[key]
+    c = _crnn_case_hip(n, width, gray, batch_seed, max_len, what)
     ora, batch = c["ora"], c["batch"]
     lab, ln = batch['label'], batch['length'].long()
 
@@ -174,12 +184,38 @@ def crnn_n256():
     with torch.no_grad():
         ev = ora(batch['image'], train=False)
     ora.train()
-    print("oracle CRNN N=256 fwd+bwd (f32 and f64) + eval: %.1f s" % (time.time() - t0))
+    print("oracle CRNN N=%d fwd+bwd (f32 and f64) + eval: %.1f s" % (n, time.time() - t0))
     c.update(state1=state1, grads32=_grads(ora), grads64=grads64,
              out32={"loss": float(loss), "logp": logp.detach(), "eval": ev})
     c["yardstick"] = lambda: _f64_bf16_storage(ora, fwd)
-    _CACHE["crnn"] = c
+    _CACHE[key] = c
     return c
+
+
+def crnn_n256_hip():
+    return _crnn_case_hip(256, 128, False, 11, None, "CRNN fp32 32x128 N=256")
+
+
+def crnn_n256():
+    return _crnn_case(256, 128, what="CRNN fp32 32x128 N=256", key="crnn")
+
+
+# ---------------------------------------------------- configs[0]: CRNN at the published 32x100 gray crop, N = 16
+def crnn_c0_hip():
+    return _crnn_case_hip(16, 100, True, 11, None, "CRNN fp32 32x100 N=16")
+
+
+def crnn_c0():
+    return _crnn_case(16, 100, gray=True, what="CRNN fp32 32x100 N=16")
+
+
+# ------------------------------------------ N = 256 at 32x120: conv3 / conv5 take the fused conv-pool launch with idle tile rows
+def crnn_w120_hip():
+    return _crnn_case_hip(256, 120, False, 11, None, "CRNN fp32 32x120 N=256")
+
+
+def crnn_w120():
+    return _crnn_case(256, 120, what="CRNN fp32 32x120 N=256")
 
 
 # ------------------------------------------------------------------------------------ configs[2]: Res50-PPM + 2D-CTC, N = 256

@@ -176,6 +176,17 @@ CONV_CASES = [
     (2, 12, 10, 16, 24, 3, 1, 2, 2),      # dilated (ResnetDilated)
     (2, 8, 8, 64, 256, 1, 1, 0, 1),       # 1x1
     (1, 15, 17, 24, 40, (2, 3), (2, 1), (0, 1), 1),  # attention encoder's (2,3) kernel, stride (2,1), pad (0,1)
+    # the CRNN pyramid of the published 32x100 crop at N = 16: feature maps 50, 25, 26 and 27 columns wide
+    (16, 16, 50, 64, 128, 3, 1, 1, 1),    # conv1
+    (16, 8, 25, 128, 256, 3, 1, 1, 1),    # conv2
+    (16, 8, 25, 256, 256, 3, 1, 1, 1),    # conv3
+    (16, 4, 26, 256, 512, 3, 1, 1, 1),    # conv4
+    (16, 4, 26, 512, 512, 3, 1, 1, 1),    # conv5
+    (16, 2, 27, 512, 512, 2, 1, 0, 1),    # conv6 (2x2, pad 0)
+    # ... and at N = 250: ragged row counts (conv1: 200 000 rows) -- the partial last tiles of the 4-wave kernels.  Neither layer
+    # takes an 8-wave tile or the head / tail split at this batch (conv1: Cout = 128; conv5: 26 000 rows are less than one round)
+    (250, 16, 50, 64, 128, 3, 1, 1, 1),   # conv1
+    (250, 4, 26, 512, 512, 3, 1, 1, 1),   # conv5
 ]
 
 
@@ -247,16 +258,24 @@ def test_batchnorm(dtype, relu):
     assert _rel_err(beta.grad, bn.bias.grad) < (1e-4 if dtype == torch.float32 else 1e-2)
 
 
+# the first four keep the ids they had when the input shape was fixed; the others are the pooled maps of the 32x100 crop (odd widths)
+MAXPOOL_CASES = [((2, 2), (2, 2), (0, 0), (3, 16, 10, 14)), ((2, 2), (2, 1), (0, 1), (3, 16, 10, 14)),
+                 ((3, 3), (2, 2), (1, 1), (3, 16, 10, 14)), ((3, 2), (1, 2), (1, 0), (3, 16, 10, 14)),
+                 ((2, 2), (2, 1), (0, 1), (4, 256, 8, 25)), ((2, 2), (2, 1), (0, 1), (4, 512, 4, 26)),
+                 ((2, 2), (2, 2), (0, 0), (4, 128, 16, 50))]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("relu_input", [False, True])
-@pytest.mark.parametrize("k,s,p", [((2, 2), (2, 2), (0, 0)), ((2, 2), (2, 1), (0, 1)), ((3, 3), (2, 2), (1, 1)),
-                                   ((3, 2), (1, 2), (1, 0))])
-def test_maxpool(dtype, k, s, p, relu_input):
+@pytest.mark.parametrize("k,s,p,shape", MAXPOOL_CASES,
+                         ids=["k%d-s%d-p%d" % (i, i, i) if i < 4 else "k%d-s%d-p%d-%s" % (i, i, i, "x".join(map(str, c[3])))
+                              for i, c in enumerate(MAXPOOL_CASES)])
+def test_maxpool(dtype, k, s, p, shape, relu_input):
     """Forward bit-exact (first-max rule on ties); backward in the fixed-geometry kernels (2x2/2, 2x2/(2,1), 3x3/2) and the
     generic one (3x2/(1,2)); relu_input=True also applies the mask of the ReLU that produced the pool input."""
     mr.set_compute_dtype(dtype)
     g = torch.Generator().manual_seed(11)
-    x = torch.randn(3, 16, 10, 14, generator=g).to(dtype)
+    x = torch.randn(*shape, generator=g).to(dtype)
     x = torch.relu(x)  # plenty of exact ties at 0: exercises the first-max rule
     xr = x.double().requires_grad_(True)
     yr = TF.max_pool2d(xr, k, s, p)
@@ -274,7 +293,10 @@ def test_maxpool(dtype, k, s, p, relu_input):
 @pytest.mark.parametrize("k,s,p,shape", [((2, 2), (2, 2), (0, 0), (5, 128, 16, 64)), ((2, 2), (2, 2), (0, 0), (3, 64, 10, 14)),
                                          ((2, 2), (2, 2), (0, 0), (2, 64, 9, 13)),      # odd sizes: uncovered last row / column
                                          ((2, 2), (2, 1), (0, 1), (4, 256, 8, 32)), ((2, 2), (2, 1), (0, 1), (3, 64, 4, 33)),
-                                         ((2, 2), (2, 1), (0, 0), (2, 64, 6, 9)), ((3, 3), (2, 2), (1, 1), (2, 64, 17, 31))])
+                                         ((2, 2), (2, 1), (0, 0), (2, 64, 6, 9)), ((3, 3), (2, 2), (1, 1), (2, 64, 17, 31)),
+                                         # the pooled maps of the 32x100 crop
+                                         ((2, 2), (2, 1), (0, 1), (4, 256, 8, 25)), ((2, 2), (2, 1), (0, 1), (4, 512, 4, 26)),
+                                         ((2, 2), (2, 2), (0, 0), (4, 128, 16, 50))])
 def test_maxpool_round5_kernels_are_bit_identical(dtype, k, s, p, shape):
     """mr_tuning.pool_fixed: the fixed-geometry forward (packed code store) and the pooled-element-organised 2x2 / stride 2
     backward give the same bits -- values, arg-max codes (through the gradient) and ReLU masking -- as the round-4 kernels."""
@@ -398,7 +420,9 @@ def test_bilstm(dtype, T, N, I, H):
         assert _rel_err(p.grad, getattr(ref, n_).grad) < (2e-4 if dtype == torch.float32 else 4e-2), n_
 
 
-@pytest.mark.parametrize("T,N,I", [(33, 256, 512), (33, 256, 256), (7, 40, 64), (2, 16, 64), (1, 5, 64)])
+@pytest.mark.parametrize("T,N,I", [(33, 256, 512), (33, 256, 256), (7, 40, 64), (2, 16, 64), (1, 5, 64),
+                                   # T = 26 / 25 of the 32x100 and 32x99 crops: one group of 16 rows, 5 rows, 250 = 15.6 groups
+                                   (26, 16, 512), (26, 16, 256), (25, 5, 512), (26, 250, 512)])
 def test_bilstm_persistent_recurrence(T, N, I):
     """The one-launch persistent recurrence (csrc/lstm_persist.hip: W_hh slices in registers, h all-gathered /
     dh reduce-scattered between workgroups through tagged granules) against (a) the per-step launches it replaces,
@@ -485,6 +509,49 @@ def test_ctc_matches_torch_and_oracle(dtype):
     o = ctc_1d(logits.float().numpy(), targets.numpy(), lengths.numpy())
     assert abs(o['loss'] - float(loss)) < 1e-6 * max(1.0, abs(o['loss']))  # f32 log-softmax round-off
     assert float((torch.from_numpy(o['grad_logits']).float() - xd.grad.float().cpu()).abs().max()) < gtol
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_ctc_ragged_input_lengths_at_the_32x100_shape(dtype):
+    """T = 26, N = 16, S = 32 (the sequence of the published 32x100 crop) with ragged INPUT lengths against F.ctc_loss and, sample
+    by sample on its own time steps, oracle.ctc; same bars as test_ctc_matches_torch_and_oracle."""
+    from oracle.ctc import ctc_1d
+    g = torch.Generator().manual_seed(29)
+    T, N, C, S = 26, 16, 38, 32
+    logits = (torch.randn(T, N, C, generator=g) * 2).to(dtype)
+    lengths = torch.randint(3, 11, (N,), generator=g)
+    lengths[3] = 0
+    targets = torch.zeros(N, S, dtype=torch.int32)
+    for i, L in enumerate(lengths.tolist()):
+        targets[i, :L] = torch.randint(2, C, (L,), generator=g, dtype=torch.int32)
+    targets[2, 1] = targets[2, 0]            # repeated label
+    in_len = torch.tensor([26, 25, 26, 7, 21, 26, 13, 26, 20, 26, 24, 26, 11, 26, 26, 1])
+    in_len = torch.maximum(in_len, 2 * lengths + 1)              # feasible whatever repeats the labels hold ...
+    in_len[15], lengths[15] = 1, 3                               # ... except the last: 3 labels in one step -> zero_infinity path
+    targets[15, :3] = torch.tensor([4, 9, 4], dtype=torch.int32)
+    assert int(in_len.max()) == T and len(set(in_len.tolist())) > 6
+    xr = logits.float().clone().requires_grad_(True)
+    lp = TF.log_softmax(xr, dim=2).double()
+    loss_r = TF.ctc_loss(lp, targets, in_len, lengths, zero_infinity=True)
+    loss_r.backward()
+    xd = logits.to(DEV).requires_grad_(True)
+    loss, logp = F.ctc_loss_logits(xd, targets.to(DEV), in_len.to(DEV), lengths.to(DEV))
+    assert loss.dtype == torch.float64
+    assert abs(float(loss) - float(loss_r)) < 1e-6 * max(1.0, abs(float(loss_r)))
+    assert float((logp.cpu() - lp.float()).abs().max()) < 2e-6
+    loss.backward()
+    gtol = 2e-6 if dtype == torch.float32 else 4e-3
+    assert float((xd.grad.float().cpu() - xr.grad).abs().max()) < gtol
+    # the oracle knows no input lengths: run it per sample on that sample's own steps (its gradient carries 1 / (1 * L))
+    per, grad = [], torch.zeros(T, N, C, dtype=torch.float64)
+    for b in range(N):
+        tb = int(in_len[b])
+        o = ctc_1d(logits[:tb, b:b + 1].float().numpy(), targets[b:b + 1].numpy(), lengths[b:b + 1].numpy())
+        per.append(o['loss'])
+        grad[:tb, b] = torch.from_numpy(o['grad_logits'])[:, 0] / N
+    loss_o = sum(per) / N
+    assert abs(loss_o - float(loss)) < 1e-6 * max(1.0, abs(loss_o))  # f32 log-softmax round-off
+    assert float((grad.float() - xd.grad.float().cpu()).abs().max()) < gtol
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

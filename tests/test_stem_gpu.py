@@ -40,7 +40,9 @@ def _reference(x, w, b, gy, round_bf16):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("N,C,H,W", [(3, 3, 32, 128), (2, 1, 8, 20), (5, 3, 2, 2), (2, 3, 16, 250), (2, 1, 4, 64),
-                                     (1, 3, 6, 32)])
+                                     (1, 3, 6, 32),
+                                     # the published 32x100 crop, 3 planes and gray: W / 2 = 50 is no multiple of 16 (generic kernel in bf16)
+                                     (16, 3, 32, 100), (16, 1, 32, 100)])
 @pytest.mark.parametrize("channels_last_weight", [False, True])
 def test_stem_matches_reference_ops(dtype, N, C, H, W, channels_last_weight):
     mr.set_compute_dtype(dtype)

@@ -191,6 +191,10 @@ def _bf16_drift(case, named32, loss32):
     # be at most 1.5 x as far from exact float64 as the float64 ORACLE ITSELF is once its activations are stored in bf16, and its
     # gradient norms must match that oracle's within 1.5 x -- a kernel that loses a term, doubles one or drifts beyond what bf16
     # storage costs anybody fails; the chaos of 53 batch-statistics BatchNorms at random initialisation (which both share) does not.
+    if bars is None:
+        # no fixed bars for this case: the yardstick rule below is the ONLY gradient bar, so it must not be vacuous
+        assert yard is not None and groups, "no yardstick group matched a parameter of %s" % case["what"]
+        assert sum(len(grp["hip"]) for grp in groups.values()) == len(rows), (sorted(groups), len(rows))
     med = lambda v: sorted(v)[len(v) // 2]
     for gname, grp in sorted(groups.items()):
         h, y = med(grp["hip"]), med(grp["yard"])
@@ -254,6 +258,20 @@ def _child(path):
 
 def test_crnn_timed_step():
     assert _isolated("crnn_n256") == 3                    # cnn.2 / cnn.4 / cnn.6: conv -> BatchNorm (no ReLU in between)
+
+
+def test_crnn_c0_timed_step():
+    # the published 32x100 gray crop at N = 16: generic stem (W / 2 = 50), odd feature-map widths 25 / 26 / 27,
+    # no 8-wave tiles.  No BF16_BARS entry on purpose: the bf16 replay is held by the yardstick rule alone (_bf16_drift)
+    assert "CRNN fp32 32x100 N=16" not in BF16_BARS   # (_bf16_drift then requires every parameter to sit in a yardstick group)
+    assert _isolated("crnn_c0") == 3
+
+
+def test_crnn_w120_timed_step():
+    # N = 256 at 32x120: conv3 (8x30: 240 of 256 tile rows) and conv5 (4x31: two images in 248 of 256 rows) take the fused conv +
+    # ReLU + max-pool launch inside the replayed bf16 step; yardstick rule only, as above
+    assert "CRNN fp32 32x120 N=256" not in BF16_BARS
+    assert _isolated("crnn_w120") == 3
 
 
 def test_res50ppm_timed_step():

@@ -72,6 +72,12 @@ def _run(N, H, W, C, K, dil, splits=0, ldx=None, lddy=None, bias=True, seed=0):
     (3, 6, 10, 64, 64, 2),       # dilated (resnet_dilated.py), image smaller than a chunk
     (5, 5, 7, 64, 72, 1),        # Cout not a multiple of the 64-row tile; IP rounded up to 8
     (2, 16, 16, 192, 40, 1),     # three Cin tiles, one partial Cout tile
+    # the 32x100 crop at N = 16: conv1 (12 800 pixels: above mr_tuning.tn_taps_min_p, the kernel the model
+    # takes), conv2 and conv5 at their odd widths 25 / 26, and conv4 at N = 250
+    (16, 16, 50, 64, 128, 1),
+    (16, 8, 25, 128, 256, 1),
+    (16, 4, 26, 512, 512, 1),
+    (250, 4, 26, 256, 512, 1),
 ])
 def test_taps_wgrad_exact(N, H, W, C, K, dil):
     assert _lib.load().mr_set_tn_taps(1) == 1
