@@ -10,6 +10,7 @@
 // larger) NCHW buffer (reference quirk Q10) -- their gradients are written back the same way.
 // All three kernels are HBM / L2-bound gather-scatter work; groups = deformable_groups = 1.
 #include "dcn_geom.h"
+#include "device.h"
 #include "../../include/megreader_hip.h"
 
 namespace mr {
@@ -452,11 +453,7 @@ int mr_dcn2_col2im(int dtype, const void* gcol, const float* offset, long long o
     const size_t lds = (size_t)PH * PW * (CC + 1) * 4;
     DISPATCH_T(dtype, {
       auto kern = dcn2_col2im_lds_kernel<T>;
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        attr_set = true;
-      }
+      if (const int rc = ensure_dynamic_lds(kern, 64 * 1024)) return rc;
       hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, stream, (const T*)gcol, offset, mask, dx, g, CC,
                          PH, PW, tiles_h, tiles_w);
     });

@@ -34,7 +34,7 @@
 //
 // Results: the buffers the per-step path saves for the backward (H_all, HC_all, W_att, CTX_all, SAVE_all), rounded at the same
 // points (hproj / gh / context / h to bf16, the context part of the input gates kept in f32), so either backward can follow.
-#include "common.h"
+#include "device.h"
 #include "igemm_core.h"
 #include "../../include/megreader_hip.h"
 
@@ -1172,20 +1172,9 @@ namespace {
 // workgroups of a group must be co-resident; workgroups that are dispatched late (a kernel of another stream still holds their CU)
 // only delay their group -- every wait is bounded (tests/test_decode_persist_gpu.py: beside a busy side stream).
 int decode_rows(int N) { return N <= 32 ? 4 : 8; }
-// CUs of the current device (cached per device): every workgroup of a launch must be resident at once, one per CU
-int decode_cus() {
-  static int cus[MR_MAX_DEVICES] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MR_MAX_DEVICES) return 0;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cus[dev] = n > 0 ? n : -1;
-  }
-  return cus[dev] > 0 ? cus[dev] : 0;
-}
+// (CUs of the current device, device_cus(): every workgroup of a launch must be resident at once, one per CU; no device = 0 CUs)
 // the XCD-colocating block map assumes the whole chip: 8 XCDs x 32 CUs.  decode_persist = 2: never use it (A/B knob)
-int decode_xmap(int nbg) { return (MR_TUNE(decode_persist) != 2 && nbg <= 8 && decode_cus() == 8 * DG) ? 1 : 0; }
+int decode_xmap(int nbg) { return (MR_TUNE(decode_persist) != 2 && nbg <= 8 && device_cus() == 8 * DG) ? 1 : 0; }
 unsigned decode_group_bytes(int R) { return R == 4 ? Xch<4>::GROUP : Xch<8>::GROUP; }
 long long decode_ws_bytes(int N) {
   const int R = decode_rows(N);
@@ -1194,17 +1183,7 @@ long long decode_ws_bytes(int N) {
 
 template <int R>
 int decode_launch(const DecP& a, hipStream_t stream) {
-  static bool attr_set[MR_MAX_DEVICES] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (dev >= 0 && dev < MR_MAX_DEVICES && !attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)decode_fwd_persist_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)Lds<R>::bytes(DT, DEPMAX)) != hipSuccess) {
-      set_error("mr_decode_persist_fwd: cannot raise the dynamic LDS limit");
-      return MR_ERR_LAUNCH;
-    }
-    attr_set[dev] = true;
-  }
+  if (const int rc = ensure_dynamic_lds(decode_fwd_persist_kernel<R>, Lds<R>::bytes(DT, DEPMAX))) return rc;
   hipLaunchKernelGGL(decode_fwd_persist_kernel<R>, dim3((a.xmap ? 8 : a.nbg) * DG), dim3(256), Lds<R>::bytes(a.T, a.Ep), stream, a);
   MR_CHECK_LAUNCH();
   return MR_OK;
@@ -1217,17 +1196,7 @@ long long decode_bwd_ws_bytes(int N) {
 
 template <int R>
 int decode_bwd_launch(const DecB& a, hipStream_t stream) {
-  static bool attr_set[MR_MAX_DEVICES] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (dev >= 0 && dev < MR_MAX_DEVICES && !attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)decode_bwd_persist_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)LdsB<R>::bytes(DT, DEPMAX)) != hipSuccess) {
-      set_error("mr_decode_persist_bwd: cannot raise the dynamic LDS limit");
-      return MR_ERR_LAUNCH;
-    }
-    attr_set[dev] = true;
-  }
+  if (const int rc = ensure_dynamic_lds(decode_bwd_persist_kernel<R>, LdsB<R>::bytes(DT, DEPMAX))) return rc;
   hipLaunchKernelGGL(decode_bwd_persist_kernel<R>, dim3((a.xmap ? 8 : a.nbg) * DG), dim3(256), LdsB<R>::bytes(a.T, a.Ep), stream, a);
   MR_CHECK_LAUNCH();
   return MR_OK;
@@ -1243,7 +1212,7 @@ int mr_decode_persist_ok(int dtype, int N, int T, int H, int Ep) {
         MR_TUNE(decode_persist) != 0))
     return 0;
   // one workgroup per CU, all of them resident at once (a partitioned or smaller device falls back to the per-step launches)
-  return cdiv(N, decode_rows(N)) * DG <= decode_cus() ? 1 : 0;
+  return cdiv(N, decode_rows(N)) * DG <= device_cus() ? 1 : 0;
 }
 
 long long mr_decode_persist_ws_bytes(int N) { return decode_ws_bytes(N); }

@@ -3,7 +3,7 @@
 // tensors are large (activations); weight-sized tensors use simple grid-stride loops.
 #include <mutex>
 #include <vector>
-#include "common.h"
+#include "device.h"
 #include "../../include/megreader_hip.h"
 #include <stdarg.h>
 
@@ -15,6 +15,59 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+// ---------------------------------------------------------------- per-device host state (device.h)
+int current_device() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MR_MAX_DEVICES) return -1;
+  return dev;
+}
+
+int device_cus() {
+  static int cus[MR_MAX_DEVICES] = {};   // 0 = not asked yet, -1 = the query failed
+  const int dev = current_device();
+  if (dev < 0) return 0;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+    cus[dev] = n > 0 ? n : -1;
+  }
+  return cus[dev] > 0 ? cus[dev] : 0;
+}
+
+const void* zero_page() {
+  static std::mutex mu;
+  static void* pages[MR_MAX_DEVICES] = {nullptr};
+  const int dev = current_device();
+  if (dev < 0) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!pages[dev]) {
+    void* p = nullptr;
+    if (hipMalloc(&p, 4096) != hipSuccess) return nullptr;
+    if (hipMemset(p, 0, 4096) != hipSuccess) return nullptr;
+    pages[dev] = p;
+  }
+  return pages[dev];
+}
+
+int ensure_dynamic_lds(const void* kernel, size_t bytes) {
+  static std::mutex mu;
+  static std::vector<const void*> raised[MR_MAX_DEVICES];
+  const int dev = current_device();
+  if (dev < 0) {
+    set_error("no current device with an index below %d", MR_MAX_DEVICES);
+    return MR_ERR_LAUNCH;
+  }
+  std::lock_guard<std::mutex> lock(mu);
+  for (const void* k : raised[dev])
+    if (k == kernel) return MR_OK;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+    set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", bytes);
+    return MR_ERR_LAUNCH;
+  }
+  raised[dev].push_back(kernel);
+  return MR_OK;
 }
 
 static inline int grid_for(long long n, int block, int max_blocks = 8192) {

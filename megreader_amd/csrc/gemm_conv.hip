@@ -6,6 +6,7 @@
 #include "igemm_p8.h"
 #include "tn_taps.h"
 #include "nt32.h"
+#include "device.h"
 #include "../../include/megreader_hip.h"
 
 #include <algorithm>
@@ -14,37 +15,39 @@
 
 namespace mr {
 
-// One 4 KiB page of zeros per device: the source of padded vectors for the direct-to-LDS loads (the only state
-// this library keeps).  Created on first use (mr_init() creates it eagerly, e.g. before hipGraph capture).
-static const void* zero_page() {
-  static std::mutex mu;
-  static void* pages[64] = {nullptr};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!pages[dev]) {
-    void* p = nullptr;
-    if (hipMalloc(&p, 4096) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, 4096) != hipSuccess) return nullptr;
-    pages[dev] = p;
-  }
-  return pages[dev];
-}
-
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 #define g_nt_variant MR_TUNE(nt_variant)  // 2 = direct-to-LDS kernel (default), 1 = register-staged kernel (A/B debugging)
 #define g_nt_deep MR_TUNE(nt_deep)     // 4-stage pipeline of the 4-wave NT kernel: 1 = automatic (low-occupancy launches), 0 never, 2 always
 
-// mr_conv2d_fwd_stats: the f64 column-statistics accumulators the NT launches of the current call attach to their epilogue
-// (EpiStore::stats), and whether every launch of the call could (the register-staged fallback kernel cannot)
-static thread_local double* g_epi_stats = nullptr;
-static thread_local const void* g_epi_addend = nullptr;   // second summand of the NT epilogue for THIS call (mr_conv2d_dgrad_add)
-static thread_local bool g_epi_stats_missed = false;
-// BatchNorm-backward sums requested for THIS call (mr_conv2d_dgrad_bnb): x / y / mean / rstd of the BatchNorm whose output
-// gradient the launch produces; the sums go to g_epi_stats.  Only the 4-wave direct-to-LDS conv kernels (EpiStoreB) serve it.
+// What ONE call asks of the epilogue of its NT launches, handed from the entry point through dispatch_nt_store to every launch_nt_*.
+// BnbRequest: x / y / mean / rstd of the BatchNorm whose output gradient the launch produces (mr_conv2d_dgrad_bnb); the sums go to
+// `stats`.  Only the 4-wave direct-to-LDS conv kernels (EpiStoreB) serve it.
 struct BnbRequest { const void* x; const void* y; const float* mean; const float* rstd; };
-static thread_local BnbRequest g_epi_bnb = {nullptr, nullptr, nullptr, nullptr};
+struct NtEpilogue {
+  const float* bias = nullptr;
+  int relu = 0;
+  const void* addend = nullptr;   // second summand, C's own layout (mr_conv2d_dgrad_add)
+  double* stats = nullptr;        // f64 column-statistics accumulators (EpiStore::stats; mr_conv2d_fwd_stats)
+  BnbRequest bnb = {nullptr, nullptr, nullptr, nullptr};
+  bool stats_missed = false;      // out: a launch of the call had no statistics epilogue (the register-staged fallback kernel)
+};
+
+template <typename T>
+static EpiStore<T> make_epi_store(void* C, long long ldc, int M, int N, const NtEpilogue& o) {
+  EpiStore<T> epi;
+  epi.C = (T*)C;
+  epi.ldc = ldc;
+  epi.bias = o.bias;
+  epi.relu = o.relu;
+  epi.M = M;
+  epi.N = N;
+  epi.vec_ok = ((ldc & 3) == 0) && aligned16(C) && aligned16(o.addend);
+  epi.addend = (const T*)o.addend;
+  epi.stats = o.stats;
+  epi.stats_ncopy = MR_BN_COPIES;
+  return epi;
+}
 
 // The direct-to-LDS NT kernels address their operands through buffer resources with 2 GiB of records.
 template <typename T>
@@ -56,11 +59,6 @@ static bool nt_fits_buffer(const NtArgs& a, const ConvGeom& g, int amode) {
   return bytesA < (1ll << 31) && bytesB < (1ll << 31);
 }
 
-static int num_cus();
-
-// The direct-to-LDS 4-wave kernel for one tile shape and epilogue type: 2-buffer loop, or the 4-buffer loop for low-occupancy
-// launches (see the comment inside).
-static int num_cus();
 // Splits of the reduction for a 4-wave NT launch of `tiles` output tiles and nk_all k-steps (NtArgs.ksplit): only launches that
 // keep at most a quarter of the CUs busy on a chain of >= 16 k-steps; as many splits as fill the chip once with >= 4 k-steps
 // each, at most 8 (mr_tuning.nt_ksplit: 0 never, 1 automatic, n: at most n).  1 = do not split.
@@ -111,14 +109,7 @@ static int launch_nt_glds(const NtArgs& a_in, const ConvGeom& g, const EpiT& epi
     const bool deep = g_nt_deep == 2 || (g_nt_deep == 1 && tiles <= num_cus() * ((160 * 1024) / lds) && nk >= 8);
     if (deep && (AMODE == 0 || (g.Cg % BK) == 0)) {
       auto kern = igemm_nt_glds_kernel<T, BM, BN, AMODE, EpiT, NST>;
-      static bool attr_set = false;  // per instantiation
-      if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-          set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", lds);
-          return MR_ERR_LAUNCH;
-        }
-        attr_set = true;
-      }
+      if (const int rc = ensure_dynamic_lds(kern, lds)) return rc;
       hipLaunchKernelGGL(kern, dim3(grid, gy), dim3(256), lds, stream, a2, g, epi);
       MR_CHECK_LAUNCH();
       return MR_OK;
@@ -134,17 +125,8 @@ static int launch_nt_glds(const NtArgs& a_in, const ConvGeom& g, const EpiT& epi
 }
 
 template <typename T, int BM, int BN, int AMODE>
-static int launch_nt_store(const NtArgs& a, const ConvGeom& g, void* C, long long ldc, const float* bias,
-                           int relu, hipStream_t stream) {
-  EpiStore<T> epi;
-  epi.C = (T*)C;
-  epi.ldc = ldc;
-  epi.bias = bias;
-  epi.relu = relu;
-  epi.M = a.M;
-  epi.N = a.N;
-  epi.vec_ok = ((ldc & 3) == 0) && ((((uintptr_t)C) & 15) == 0) && ((((uintptr_t)g_epi_addend) & 15) == 0);
-  epi.addend = (const T*)g_epi_addend;
+static int launch_nt_store(const NtArgs& a, const ConvGeom& g, void* C, long long ldc, NtEpilogue& o, hipStream_t stream) {
+  EpiStore<T> epi = make_epi_store<T>(C, ldc, a.M, a.N, o);
   const int tiles = cdiv(a.M, BM) * cdiv(a.N, BN);
   if constexpr (AMODE != 1) {
     if (g_nt_variant == 2 && nt_fits_buffer<T>(a, g, AMODE)) {
@@ -152,16 +134,14 @@ static int launch_nt_store(const NtArgs& a, const ConvGeom& g, void* C, long lon
       NtArgs a2 = a;
       a2.zero = zero_page();
       if (!a2.zero) { set_error("zero page allocation failed"); return MR_ERR_LAUNCH; }
-      epi.stats = g_epi_stats;
-      epi.stats_ncopy = MR_BN_COPIES;
       if constexpr (AMODE == 2) {
-        if (g_epi_bnb.x != nullptr) {    // statistics epilogue in BatchNorm-backward mode: its own epilogue type
+        if (o.bnb.x != nullptr) {    // statistics epilogue in BatchNorm-backward mode: its own epilogue type
           EpiStoreB<T> eb;
           static_cast<EpiStore<T>&>(eb) = epi;
-          eb.bnb_x = (const T*)g_epi_bnb.x;
-          eb.bnb_y = (const T*)g_epi_bnb.y;
-          eb.bnb_mean = g_epi_bnb.mean;
-          eb.bnb_rstd = g_epi_bnb.rstd;
+          eb.bnb_x = (const T*)o.bnb.x;
+          eb.bnb_y = (const T*)o.bnb.y;
+          eb.bnb_mean = o.bnb.mean;
+          eb.bnb_rstd = o.bnb.rstd;
           return launch_nt_glds<T, BM, BN, AMODE, EpiStoreB<T>>(a2, g, eb, grid, tiles, stream);
         }
       }
@@ -169,24 +149,12 @@ static int launch_nt_store(const NtArgs& a, const ConvGeom& g, void* C, long lon
     }
   }
   if (a.m_begin != 0) { set_error("row-range launches need the direct-to-LDS NT kernel"); return MR_ERR_ARG; }
-  if (g_epi_stats) g_epi_stats_missed = true;   // this kernel has no statistics epilogue: the caller reduces y itself
+  if (o.stats) o.stats_missed = true;   // this kernel has no statistics epilogue: the caller reduces y itself
+  epi.stats = nullptr;
   hipLaunchKernelGGL((igemm_nt_kernel<T, BM, BN, AMODE, EpiStore<T>>), dim3(tiles), dim3(256), 0, stream, a, g,
                      epi);
   MR_CHECK_LAUNCH();
   return MR_OK;
-}
-
-static int num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
-      cus = p.multiProcessorCount;
-    else
-      cus = 256;
-  }
-  return cus;
 }
 
 // ---- big-tile (8-wave) NT kernel: bf16, dense or fast-gather conv operands ---------------------------------------
@@ -251,33 +219,15 @@ static long long nt_head_rows(int M, int N, int K) {
 }
 
 template <typename T, int WM, int WN, int TM, int TN, int AMODE>
-static int launch_nt_big(const NtArgs& a, const ConvGeom& g, void* C, long long ldc, const float* bias, int relu,
-                         hipStream_t stream) {
+static int launch_nt_big(const NtArgs& a, const ConvGeom& g, void* C, long long ldc, NtEpilogue& o, hipStream_t stream) {
   constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-  EpiStore<T> epi;
-  epi.C = (T*)C;
-  epi.ldc = ldc;
-  epi.bias = bias;
-  epi.relu = relu;
-  epi.M = a.M;
-  epi.N = a.N;
-  epi.vec_ok = ((ldc & 3) == 0) && ((((uintptr_t)C) & 15) == 0) && ((((uintptr_t)g_epi_addend) & 15) == 0);
-  epi.addend = (const T*)g_epi_addend;
-  epi.stats = g_epi_stats;
-  epi.stats_ncopy = MR_BN_COPIES;
+  const EpiStore<T> epi = make_epi_store<T>(C, ldc, a.M, a.N, o);
   NtArgs a2 = a;
   a2.zero = zero_page();
   if (!a2.zero) { set_error("zero page allocation failed"); return MR_ERR_LAUNCH; }
   constexpr size_t lds = 2 * (size_t)(BM + BN) * 128;
   auto kern = igemm_nt_big_kernel<T, WM, WN, TM, TN, AMODE, EpiStore<T>>;
-  static bool attr_set = false;  // per instantiation
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", lds);
-      return MR_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = ensure_dynamic_lds(kern, lds)) return rc;
   const int tiles_m = cdiv(a.M - a.m_begin, BM), tiles_n = cdiv(a.N, BN);
   const int grid = cdiv(tiles_m, 8) * 8 * tiles_n;  // XCD-aware map: see the kernel
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WM * WN), lds, stream, a2, g, epi);
@@ -286,48 +236,29 @@ static int launch_nt_big(const NtArgs& a, const ConvGeom& g, void* C, long long 
 }
 
 // Phased-schedule 256x256 kernel (igemm_p8.h); g_use_p8: 1 = use it wherever the 8-wave 256x256 kernel would run.
-// Measured equal to the v3 kernel (850-900 TF/s on conv3 / conv5, gpurun r2j) -- the schedule is not what bounds the
+// Measured equal to the v3 kernel (850-900 TF/s on conv3 / conv5) -- the schedule is not what bounds the
 // tile: its ablation ladder (mr_tuning.nt_p8(2..4), tools/microbench_conv.py --p8) gives 1.16-1.21 PF for the bare
 // MFMA + barrier skeleton incl. prologue / epilogue, 1.03 PF with the fragment reads, 0.85-0.90 with the LDS-DMA
 // issue on top.  Default: the v3 kernel.
 #define g_use_p8 MR_TUNE(nt_p8)
 template <typename T, int AMODE>
-static int launch_nt_p8(const NtArgs& a, const ConvGeom& g, void* C, long long ldc, const float* bias, int relu,
-                        hipStream_t stream) {
+static int launch_nt_p8(const NtArgs& a, const ConvGeom& g, void* C, long long ldc, NtEpilogue& o, hipStream_t stream) {
   if constexpr (sizeof(T) != 2) {
-    return launch_nt_big<T, 2, 4, 8, 4, AMODE>(a, g, C, ldc, bias, relu, stream);
+    return launch_nt_big<T, 2, 4, 8, 4, AMODE>(a, g, C, ldc, o, stream);
   } else {
-    if (!g_use_p8) return launch_nt_big<T, 2, 4, 8, 4, AMODE>(a, g, C, ldc, bias, relu, stream);
-    EpiStore<T> epi;
-    epi.C = (T*)C;
-    epi.ldc = ldc;
-    epi.bias = bias;
-    epi.relu = relu;
-    epi.M = a.M;
-    epi.N = a.N;
-    epi.vec_ok = ((ldc & 3) == 0) && ((((uintptr_t)C) & 15) == 0) && ((((uintptr_t)g_epi_addend) & 15) == 0);
-  epi.addend = (const T*)g_epi_addend;
-    epi.stats = g_epi_stats;
-    epi.stats_ncopy = MR_BN_COPIES;
+    if (!g_use_p8) return launch_nt_big<T, 2, 4, 8, 4, AMODE>(a, g, C, ldc, o, stream);
+    const EpiStore<T> epi = make_epi_store<T>(C, ldc, a.M, a.N, o);
     NtArgs a2 = a;
     a2.zero = zero_page();
     if (!a2.zero) { set_error("zero page allocation failed"); return MR_ERR_LAUNCH; }
     constexpr size_t lds = 2 * (size_t)(256 + 256) * 128;
     const int tiles_m = cdiv(a.M - a.m_begin, 256), tiles_n = cdiv(a.N, 256);
     const int grid = cdiv(tiles_m, 8) * 8 * tiles_n;
-#define MR_P8_LAUNCH(ABL_)                                                                                        \
-  {                                                                                                               \
-    auto kern = igemm_nt_p8_kernel<AMODE, EpiStore<T>, ABL_>;                                                     \
-    static bool attr_set = false;                                                                                 \
-    if (!attr_set) {                                                                                              \
-      if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=         \
-          hipSuccess) {                                                                                           \
-        set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", lds);                                      \
-        return MR_ERR_LAUNCH;                                                                                     \
-      }                                                                                                           \
-      attr_set = true;                                                                                            \
-    }                                                                                                             \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, a2, g, epi);                                     \
+#define MR_P8_LAUNCH(ABL_)                                                    \
+  {                                                                           \
+    auto kern = igemm_nt_p8_kernel<AMODE, EpiStore<T>, ABL_>;                 \
+    if (const int rc = ensure_dynamic_lds(kern, lds)) return rc;              \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, a2, g, epi); \
   }
 #ifdef MR_ABLATION   // measurement-only ablations (mr_tuning.nt_p8(2..4)); wrong results: tools-only build
     if (g_use_p8 == 2) MR_P8_LAUNCH(1)
@@ -402,63 +333,50 @@ static bool nt_use_288x128(int M, int N, int K) {
 }
 
 template <typename T, int AMODE>
-static int dispatch_nt_store(const NtArgs& a, const ConvGeom& g, void* C, long long ldc, const float* bias,
-                             int relu, hipStream_t stream) {
+static int dispatch_nt_store(const NtArgs& a, const ConvGeom& g, void* C, long long ldc, NtEpilogue& o, hipStream_t stream) {
   if constexpr (sizeof(T) == 2 && (AMODE == 0 || AMODE == 2)) {
     constexpr int BK = 8 * VecOf<T>::N;
     // (a launch that also has to produce BatchNorm-backward sums, mr_conv2d_dgrad_bnb, stays on the 4-wave kernels: the
     // 8-wave tiles have no registers to spare for that epilogue)
     if (g_nt_variant == 2 && !forced_tile().bm && (AMODE == 0 || (g.Cg % BK) == 0) && aligned16(C) &&
-        nt_fits_buffer<T>(a, g, AMODE) && g_epi_bnb.x == nullptr) {
+        nt_fits_buffer<T>(a, g, AMODE) && o.bnb.x == nullptr) {
       const int big = nt_big_choice(a.M, a.N, a.K);
       // Ping-pong 32x32x16 kernel (nt32.hip, round 6; mr_tuning.nt_m32): 1 = wherever the automatic choice takes a 256-column
       // big tile (256x256 -> 256x256, 272x256 -> 288x256), >= 2 = shape (nt_m32 - 1) for every eligible launch (sweeps)
       if (const int m32 = MR_TUNE(nt_m32); m32 != 0 && a.m_begin == 0 && a.ksplit <= 1) {
         const int shape = m32 >= 2 ? m32 - 1 : big == 1 ? 1 : big == 3 ? 2 : 0;
-        if (shape) {
-          EpiStore<bf16_t> epi;
-          epi.C = (bf16_t*)C;
-          epi.ldc = ldc;
-          epi.bias = bias;
-          epi.relu = relu;
-          epi.M = a.M;
-          epi.N = a.N;
-          epi.vec_ok = ((ldc & 3) == 0) && ((((uintptr_t)C) & 15) == 0) && ((((uintptr_t)g_epi_addend) & 15) == 0);
-          epi.addend = (const bf16_t*)g_epi_addend;
-          epi.stats = g_epi_stats;
-          epi.stats_ncopy = MR_BN_COPIES;
-          return launch_nt32(shape, MR_TUNE(nt_m32_opt), AMODE, a, g, epi, stream);
-        }
+        if (shape)
+          return launch_nt32(shape, MR_TUNE(nt_m32_opt), AMODE, a, g, make_epi_store<bf16_t>(C, ldc, a.M, a.N, o), stream);
       }
-      if (big == 1) return launch_nt_p8<T, AMODE>(a, g, C, ldc, bias, relu, stream);
-      if (big == 2) return launch_nt_big<T, 2, 4, 9, 4, AMODE>(a, g, C, ldc, bias, relu, stream);   // 288x256, 8 waves (2x4)
-      if (big == 3) return launch_nt_big<T, 1, 8, 17, 2, AMODE>(a, g, C, ldc, bias, relu, stream);  // 272x256, 8 waves (1x8)
-      if (big == 4) return launch_nt_big<T, 2, 2, 5, 4, AMODE>(a, g, C, ldc, bias, relu, stream);   // 160x128, 4 waves (2x2)
-      if (big == 5) return launch_nt_big<T, 2, 4, 5, 2, AMODE>(a, g, C, ldc, bias, relu, stream);   // 160x128, 8 waves (2x4)
-      if (big == 6) return launch_nt_big<T, 2, 4, 8, 2, AMODE>(a, g, C, ldc, bias, relu, stream);   // 256x128, 8 waves (2x4)
-      if (big == 7) return launch_nt_big<T, 2, 4, 9, 2, AMODE>(a, g, C, ldc, bias, relu, stream);   // 288x128, 8 waves (2x4)
-      if (big == 8) return launch_nt_big<T, 2, 4, 4, 2, AMODE>(a, g, C, ldc, bias, relu, stream);   // 128x128, 8 waves (2x4)
-      if (big == 9) return launch_nt_big<T, 2, 4, 6, 2, AMODE>(a, g, C, ldc, bias, relu, stream);   // 192x128, 8 waves (2x4)
-      if (big == 10) return launch_nt_big<T, 4, 2, 2, 2, AMODE>(a, g, C, ldc, bias, relu, stream);  // 128x64, 8 waves (4x2)
-      if (big == 11) return launch_nt_big<T, 4, 2, 3, 2, AMODE>(a, g, C, ldc, bias, relu, stream);  // 192x64, 8 waves (4x2)
-      if (big == 12) return launch_nt_big<T, 4, 2, 4, 2, AMODE>(a, g, C, ldc, bias, relu, stream);  // 256x64, 8 waves (4x2)
-      if (big == 13) return launch_nt_big<T, 2, 4, 3, 2, AMODE>(a, g, C, ldc, bias, relu, stream);  // 96x128, 8 waves (2x4)
+      if (big == 1) return launch_nt_p8<T, AMODE>(a, g, C, ldc, o, stream);
+      if (big == 2) return launch_nt_big<T, 2, 4, 9, 4, AMODE>(a, g, C, ldc, o, stream);   // 288x256, 8 waves (2x4)
+      if (big == 3) return launch_nt_big<T, 1, 8, 17, 2, AMODE>(a, g, C, ldc, o, stream);  // 272x256, 8 waves (1x8)
+      if (big == 4) return launch_nt_big<T, 2, 2, 5, 4, AMODE>(a, g, C, ldc, o, stream);   // 160x128, 4 waves (2x2)
+      if (big == 5) return launch_nt_big<T, 2, 4, 5, 2, AMODE>(a, g, C, ldc, o, stream);   // 160x128, 8 waves (2x4)
+      if (big == 6) return launch_nt_big<T, 2, 4, 8, 2, AMODE>(a, g, C, ldc, o, stream);   // 256x128, 8 waves (2x4)
+      if (big == 7) return launch_nt_big<T, 2, 4, 9, 2, AMODE>(a, g, C, ldc, o, stream);   // 288x128, 8 waves (2x4)
+      if (big == 8) return launch_nt_big<T, 2, 4, 4, 2, AMODE>(a, g, C, ldc, o, stream);   // 128x128, 8 waves (2x4)
+      if (big == 9) return launch_nt_big<T, 2, 4, 6, 2, AMODE>(a, g, C, ldc, o, stream);   // 192x128, 8 waves (2x4)
+      if (big == 10) return launch_nt_big<T, 4, 2, 2, 2, AMODE>(a, g, C, ldc, o, stream);  // 128x64, 8 waves (4x2)
+      if (big == 11) return launch_nt_big<T, 4, 2, 3, 2, AMODE>(a, g, C, ldc, o, stream);  // 192x64, 8 waves (4x2)
+      if (big == 12) return launch_nt_big<T, 4, 2, 4, 2, AMODE>(a, g, C, ldc, o, stream);  // 256x64, 8 waves (4x2)
+      if (big == 13) return launch_nt_big<T, 2, 4, 3, 2, AMODE>(a, g, C, ldc, o, stream);  // 96x128, 8 waves (2x4)
       // Head / tail: rows are independent, so a problem whose 256x256 tile count is a few tiles over whole rounds of
       // the CUs (33792 x 512: 264 tiles on 256 CUs) is cut into a head that is EXACTLY whole rounds of big tiles and
       // a tail of the remaining rows for the 4-wave kernel.  No cross-workgroup reduction, two launches.
       const long long head = a.m_begin == 0 ? nt_head_rows(a.M, a.N, a.K) : 0;
       if (head == 0 && a.m_begin == 0 && nt_use_288x128(a.M, a.N, a.K))
-        return launch_nt_big<T, 2, 4, 9, 2, AMODE>(a, g, C, ldc, bias, relu, stream);
+        return launch_nt_big<T, 2, 4, 9, 2, AMODE>(a, g, C, ldc, o, stream);
       if (head > 0) {
         NtArgs ah = a;
         ah.M = (int)head;
-        int rc = launch_nt_p8<T, AMODE>(ah, g, C, ldc, bias, relu, stream);
+        int rc = launch_nt_p8<T, AMODE>(ah, g, C, ldc, o, stream);
         if (rc != MR_OK || head == a.M) return rc;
         NtArgs at = a;
         at.m_begin = (int)head;
         const TileChoice tt = nt_tile(a.M - (int)head, a.N);
 #define MR_NT_TAIL(BM_, BN_) \
-  if (tt.bm == BM_ && tt.bn == BN_) return launch_nt_store<T, BM_, BN_, AMODE>(at, g, C, ldc, bias, relu, stream);
+  if (tt.bm == BM_ && tt.bn == BN_) return launch_nt_store<T, BM_, BN_, AMODE>(at, g, C, ldc, o, stream);
         MR_NT_TAIL(128, 128) MR_NT_TAIL(128, 64) MR_NT_TAIL(96, 128) MR_NT_TAIL(96, 64) MR_NT_TAIL(64, 128)
         MR_NT_TAIL(64, 64)
 #undef MR_NT_TAIL
@@ -475,7 +393,7 @@ static int dispatch_nt_store(const NtArgs& a, const ConvGeom& g, void* C, long l
       if (w8 > 0 && a.m_begin == 0) {
         const TileChoice tw = nt_tile(a.M, a.N);
 #define MR_NT_W8(BIT_, BM_, BN_, WM_, WN_, TM_, TN_) \
-  if ((w8 & (BIT_)) && tw.bm == BM_ && tw.bn == BN_) return launch_nt_big<T, WM_, WN_, TM_, TN_, AMODE>(a, g, C, ldc, bias, relu, stream);
+  if ((w8 & (BIT_)) && tw.bm == BM_ && tw.bn == BN_) return launch_nt_big<T, WM_, WN_, TM_, TN_, AMODE>(a, g, C, ldc, o, stream);
         MR_NT_W8(1, 128, 128, 2, 4, 4, 2) MR_NT_W8(2, 128, 64, 4, 2, 2, 2) MR_NT_W8(4, 96, 128, 2, 4, 3, 2)
         MR_NT_W8(8, 64, 128, 2, 4, 2, 2) MR_NT_W8(16, 96, 64, 2, 4, 3, 1) MR_NT_W8(32, 64, 64, 2, 4, 2, 1)
 #undef MR_NT_W8
@@ -484,12 +402,21 @@ static int dispatch_nt_store(const NtArgs& a, const ConvGeom& g, void* C, long l
   }
   const TileChoice t = nt_tile(a.M, a.N);
 #define MR_NT_CASE(BM_, BN_) \
-  if (t.bm == BM_ && t.bn == BN_) return launch_nt_store<T, BM_, BN_, AMODE>(a, g, C, ldc, bias, relu, stream);
+  if (t.bm == BM_ && t.bn == BN_) return launch_nt_store<T, BM_, BN_, AMODE>(a, g, C, ldc, o, stream);
   MR_NT_CASE(128, 128) MR_NT_CASE(128, 64) MR_NT_CASE(96, 128) MR_NT_CASE(96, 64) MR_NT_CASE(64, 128)
   MR_NT_CASE(64, 64)
 #undef MR_NT_CASE
   set_error("no NT tile for %dx%d", t.bm, t.bn);
   return MR_ERR_ARG;
+}
+
+// The bf16 TN kernels that stage through buffer resources need every byte offset of both operands below the descriptors' 2 GiB
+// of records (bmode 0: dense B, else the gathered conv operand).
+static bool tn_fits_buffer(const TnArgs& a, const ConvGeom& g, int bmode) {
+  const long long bytesA = (long long)a.P * a.lda * 2;
+  const long long bytesB = bmode == 0 ? (long long)a.P * a.ldb * 2
+                                      : ((long long)a.P / ((long long)g.Hm * g.Wm) + 1) * g.Hg * g.Wg * g.ldg * 2;
+  return bytesA < (1ll << 31) && bytesB < (1ll << 31);
 }
 
 // Wide-tile TN kernel launch: SA = 2 -> 256x256 tile, SA = 1 -> 128 (NA) x 256 (NB) tile; one workgroup per CU.
@@ -515,14 +442,7 @@ static int launch_tn_big(TnArgs a, const ConvGeom& g, int total_steps, hipStream
 #endif
   constexpr int lds = 2 * (SA + 2) * 64 * 256 + 1024;  // 2 stages x [A.. | B0 | B1] x 16 KB + column-sum accumulator
   auto kern = igemm_tn_big_kernel<BMODE, SA>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", lds);
-      return MR_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = ensure_dynamic_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3(btiles * bsplits), dim3(512), lds, stream, a, g, z);
   MR_CHECK_LAUNCH();
   return MR_OK;
@@ -539,18 +459,14 @@ struct TnRecord { TnArgs a; ConvGeom g; };
 // DEVICE and process-wide behind a mutex: records are pushed on an autograd device worker thread, while the
 // end-of-backward callback that flushes them runs on whichever thread completes the graph task -- with a thread-local queue
 // that thread saw nothing pending, skipped the launch and still released the operands.
-struct TnDeferState {
-  bool on = false;
-  bool beside = false;          // mr_tn_flush_beside in progress: launches must not touch the shared split-reduction workspace
-};
+struct TnDeferState { bool on = false; };
 static thread_local TnDeferState g_tn_defer_state;
 struct TnQueue { std::vector<TnRecord> q[2]; };   // [0]: BMODE 0, [1]: BMODE 2
 static std::mutex g_tn_queue_mutex;
 static TnQueue g_tn_queue[MR_MAX_DEVICES];
-static TnQueue& tn_queue_of_current_device() {     // (call with g_tn_queue_mutex held)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  return g_tn_queue[(unsigned)dev % MR_MAX_DEVICES];
+static TnQueue* tn_queue_of_current_device() {     // (call with g_tn_queue_mutex held); null: no device to queue for
+  const int dev = current_device();
+  return dev >= 0 ? &g_tn_queue[dev] : nullptr;
 }
 
 template <int BMODE>
@@ -597,20 +513,21 @@ static int launch_tn_group(const TnRecord* recs, int n, hipStream_t stream) {
 }
 
 template <typename T, int BMODE>
-static int launch_tn_now(TnArgs a, const ConvGeom& g, hipStream_t stream);
+static int launch_tn_now(TnArgs a, const ConvGeom& g, bool beside, hipStream_t stream);
 
-static int tn_flush(hipStream_t stream, bool beside = false) {
+// beside: the stream runs beside the stream of the other weight-gradient launches (mr_tn_flush_beside)
+static int tn_flush(hipStream_t stream, bool beside) {
   TnDeferState& st = g_tn_defer_state;
   const bool was_on = st.on;
   st.on = false;      // single problems below go through launch_tn_now
-  st.beside = beside;
   int rc = MR_OK;
   TnQueue mine;       // the device's records, taken out under the lock: launches run without it
   {
     std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
-    TnQueue& dq = tn_queue_of_current_device();
-    mine.q[0].swap(dq.q[0]);
-    mine.q[1].swap(dq.q[1]);
+    if (TnQueue* dq = tn_queue_of_current_device()) {
+      mine.q[0].swap(dq->q[0]);
+      mine.q[1].swap(dq->q[1]);
+    }
   }
   for (int m = 0; m < 2 && rc == MR_OK; ++m) {
     std::vector<TnRecord>& q = mine.q[m];
@@ -618,7 +535,8 @@ static int tn_flush(hipStream_t stream, bool beside = false) {
     while (i < q.size() && rc == MR_OK) {
       const int n = (int)std::min<size_t>(TN_GROUP_MAX, q.size() - i);
       if (n == 1)
-        rc = m == 0 ? launch_tn_now<bf16_t, 0>(q[i].a, q[i].g, stream) : launch_tn_now<bf16_t, 2>(q[i].a, q[i].g, stream);
+        rc = m == 0 ? launch_tn_now<bf16_t, 0>(q[i].a, q[i].g, beside, stream)
+                    : launch_tn_now<bf16_t, 2>(q[i].a, q[i].g, beside, stream);
       else
         rc = m == 0 ? launch_tn_group<0>(&q[i], n, stream) : launch_tn_group<2>(&q[i], n, stream);
       i += n;
@@ -626,30 +544,29 @@ static int tn_flush(hipStream_t stream, bool beside = false) {
     q.clear();
   }
   st.on = was_on;
-  st.beside = false;
   return rc;
 }
 
+// beside: the launch may run concurrently with TN launches of another stream, so it must not touch the shared split-reduction
+// workspace (tickets + slabs: its users have to be stream-ordered with each other) and reduces with plain f32 atomics.  A
+// RECORDED problem takes the flag of the flush that launches it.
 template <typename T, int BMODE>
-static int launch_tn(TnArgs a, const ConvGeom& g, hipStream_t stream) {
+static int launch_tn(TnArgs a, const ConvGeom& g, bool beside, hipStream_t stream) {
   if constexpr (sizeof(T) == 2 && BMODE != 1) {
-    TnDeferState& st = g_tn_defer_state;
-    if (st.on && g_tn_defer && g_nt_variant == 2 && g_tn_buf && g_tn_big <= 0 && g_tn_fin != 2 && g_tn_splits == 0) {
-      const long long bytesA = (long long)a.P * a.lda * 2;
-      const long long bytesB = BMODE == 0 ? (long long)a.P * a.ldb * 2
-                                          : ((long long)a.P / ((long long)g.Hm * g.Wm) + 1) * g.Hg * g.Wg * g.ldg * 2;
-      if (bytesA < (1ll << 31) && bytesB < (1ll << 31)) {
-        std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
-        tn_queue_of_current_device().q[BMODE == 0 ? 0 : 1].push_back(TnRecord{a, g});
+    if (g_tn_defer_state.on && g_tn_defer && g_nt_variant == 2 && g_tn_buf && g_tn_big <= 0 && g_tn_fin != 2 &&
+        g_tn_splits == 0 && tn_fits_buffer(a, g, BMODE)) {
+      std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
+      if (TnQueue* dq = tn_queue_of_current_device()) {
+        dq->q[BMODE == 0 ? 0 : 1].push_back(TnRecord{a, g});
         return MR_OK;
       }
     }
   }
-  return launch_tn_now<T, BMODE>(a, g, stream);
+  return launch_tn_now<T, BMODE>(a, g, beside, stream);
 }
 
 template <typename T, int BMODE>
-static int launch_tn_now(TnArgs a, const ConvGeom& g, hipStream_t stream) {
+static int launch_tn_now(TnArgs a, const ConvGeom& g, bool beside, hipStream_t stream) {
   constexpr int BP = TnCfg<T>::BP;
   const int tiles = cdiv(a.NA, 128) * cdiv(a.NB, 128);
   // split count: workgroups run 2 per CU and are latency-bound, so time ~ rounds(blocks / 2*CUs) * (p-steps per
@@ -678,26 +595,18 @@ static int launch_tn_now(TnArgs a, const ConvGeom& g, hipStream_t stream) {
     // s_waitcnt vmcnt(0) that also drains the in-flight LDS-DMA prefetch; mode 2 has no spills, so the common
     // cause is elsewhere (one barrier-coupled workgroup per CU with only 32 MFMAs per wave between barriers cannot
     // hide the load latency that two independent 4-wave workgroups hide) -- left for a counter-based look.
-    if (g_nt_variant == 2 && g_tn_big > 0) {
-      const long long bytesA0 = (long long)a.P * a.lda * 2;
-      const long long bytesB0 = BMODE == 0 ? (long long)a.P * a.ldb * 2
-                                           : ((long long)a.P / ((long long)g.Hm * g.Wm) + 1) * g.Hg * g.Wg * g.ldg * 2;
-      if (bytesA0 < (1ll << 31) && bytesB0 < (1ll << 31)) {   // buffer-resource staging
-        const int rc = g_tn_big == 2 ? launch_tn_big<BMODE, 1>(a, g, total_steps, stream)
-                                     : launch_tn_big<BMODE, 2>(a, g, total_steps, stream);
-        return rc;
-      }
-    }
+    if (g_nt_variant == 2 && g_tn_big > 0 && tn_fits_buffer(a, g, BMODE))
+      return g_tn_big == 2 ? launch_tn_big<BMODE, 1>(a, g, total_steps, stream)
+                           : launch_tn_big<BMODE, 2>(a, g, total_steps, stream);
   }
   a.p_chunk = cdiv(cdiv(a.P, splits), BP) * BP;
   splits = cdiv(a.P, a.p_chunk);
   if constexpr (sizeof(T) == 2) {
     if (g_nt_variant == 2) {
       // in-launch reduction of the split partials through the all-taps kernel's workspace (TnArgs.grp)
-      // Measured (tools/gpu_r2_tn.sh): the publish + ticket round costs ~8 us of latency, the atomics it removes scale with
+      // Measured: the publish + ticket round costs ~8 us of latency, the atomics it removes scale with
       // the split count -- conv1 wgrad (5 tiles x ~100 splits) 92.6 -> 80.1 us, but conv6 wgrad (16 splits... of 64 tiles)
       // 44.2 -> 46.8 and the LSTM / Linear weight gradients (4 splits) +-2 us: automatic = only from 16 splits up.
-      const bool beside = g_tn_defer_state.beside;   // concurrent with launches of another stream: plain atomics only
       if (g_tn_fin == 2 && splits > 1 && !beside) {   // direct slabs + finalize launch (TnArgs.fin)
         void* ws = nullptr;
         long long ws_bytes = 0;
@@ -723,19 +632,16 @@ static int launch_tn_now(TnArgs a, const ConvGeom& g, hipStream_t stream) {
       }
       const void* z = zero_page();
       if (!z) { set_error("zero page allocation failed"); return MR_ERR_LAUNCH; }
-      // buffer-resource staging needs every byte offset below the descriptor's 2 GiB num_records
-      const long long bytesA = (long long)a.P * a.lda * 2;
-      const long long bytesB = BMODE == 0 ? (long long)a.P * a.ldb * 2
-                                          : ((long long)a.P / ((long long)g.Hm * g.Wm) + 1) * g.Hg * g.Wg * g.ldg * 2;
+      const bool buf_ok = tn_fits_buffer(a, g, BMODE);
 #ifdef MR_ABLATION
-      if (g_tn_abl && bytesA < (1ll << 31) && bytesB < (1ll << 31)) {   // timing-only ablations (mr_set_tn_abl)
+      if (g_tn_abl && buf_ok) {   // timing-only ablations (mr_set_tn_abl)
 #define MR_TN_ABL(V_) case V_: hipLaunchKernelGGL((igemm_tn_glds_kernel<BMODE, true, V_>), dim3(tiles * splits), \
                                                    dim3(256), 0, stream, a, g, z); break;
         switch (g_tn_abl) { MR_TN_ABL(1) MR_TN_ABL(2) MR_TN_ABL(3) MR_TN_ABL(4) MR_TN_ABL(8) MR_TN_ABL(15) default: break; }
 #undef MR_TN_ABL
       } else
 #endif
-      if (g_tn_buf && bytesA < (1ll << 31) && bytesB < (1ll << 31))
+      if (g_tn_buf && buf_ok)
         hipLaunchKernelGGL((igemm_tn_glds_kernel<BMODE, true>), dim3(tiles * splits), dim3(256), 0, stream, a, g, z);
       else
         hipLaunchKernelGGL((igemm_tn_glds_kernel<BMODE, false>), dim3(tiles * splits), dim3(256), 0, stream, a, g, z);
@@ -797,14 +703,7 @@ static int launch_nt_pool(const NtArgs& a, const ConvGeom& g, const EpiPool<bf16
   constexpr size_t lds_stage = 2 * (size_t)(BM + BN) * 128, lds_tile = (size_t)BM * BN * 2;
   constexpr size_t lds = lds_stage > lds_tile ? lds_stage : lds_tile;
   auto kern = igemm_nt_big_kernel<bf16_t, WM, WN, TM, TN, 2, EpiPool<bf16_t>>;
-  static bool attr_set = false;  // per instantiation
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", lds);
-      return MR_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = ensure_dynamic_lds(kern, lds)) return rc;
   const int tiles_m = cdiv(a.M, a.tile_rows), tiles_n = cdiv(a.N, BN);
   const int grid = cdiv(tiles_m, 8) * 8 * tiles_n;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WM * WN), lds, stream, a, g, epi);
@@ -892,8 +791,11 @@ int mr_gemm_nt(int dtype, const void* A, long long lda, const void* B, int ldb, 
   NtArgs a;
   a.A = A; a.B = B; a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.zero = nullptr;
   ConvGeom g = {};
-  if (dtype == MR_F32) return dispatch_nt_store<float, 0>(a, g, C, ldc, bias, relu, stream);
-  return dispatch_nt_store<bf16_t, 0>(a, g, C, ldc, bias, relu, stream);
+  NtEpilogue o;
+  o.bias = bias;
+  o.relu = relu;
+  if (dtype == MR_F32) return dispatch_nt_store<float, 0>(a, g, C, ldc, o, stream);
+  return dispatch_nt_store<bf16_t, 0>(a, g, C, ldc, o, stream);
 }
 
 // Deferred weight-gradient launches.  mr_tn_defer(1): from now on, on the calling host thread, the bf16 weight-gradient GEMMs that
@@ -908,21 +810,22 @@ int mr_tn_defer(int on) {
 }
 int mr_tn_pending(void) {
   std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
-  const TnQueue& dq = tn_queue_of_current_device();
-  return (int)(dq.q[0].size() + dq.q[1].size());
+  const TnQueue* dq = tn_queue_of_current_device();
+  return dq ? (int)(dq->q[0].size() + dq->q[1].size()) : 0;
 }
 // Drops the current device's recorded problems WITHOUT launching them (a backward pass that raised: its records point at operands
 // the caller is about to release) and switches recording off for the calling thread; returns how many were dropped.  Host only.
 int mr_tn_discard(void) {
   g_tn_defer_state.on = false;
   std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
-  TnQueue& dq = tn_queue_of_current_device();
-  const int n = (int)(dq.q[0].size() + dq.q[1].size());
-  dq.q[0].clear();
-  dq.q[1].clear();
+  TnQueue* dq = tn_queue_of_current_device();
+  if (!dq) return 0;
+  const int n = (int)(dq->q[0].size() + dq->q[1].size());
+  dq->q[0].clear();
+  dq->q[1].clear();
   return n;
 }
-int mr_tn_flush(hipStream_t stream) { return tn_flush(stream); }
+int mr_tn_flush(hipStream_t stream) { return tn_flush(stream, false); }
 // The same on a stream that runs BESIDE the stream of the other weight-gradient launches: single leftover problems reduce their
 // split partials with plain f32 atomics (the ticket / slab workspace of the in-launch reduction is shared per device and
 // must only be used by launches that are stream-ordered with each other).
@@ -952,8 +855,8 @@ int mr_gemm_tn2(int dtype, const void* A, long long lda, const void* B, long lon
   a.p_chunk = 0; a.row_perm_h = row_perm_h; a.colsum = colsum; a.rowtab = nullptr; a.grp = 1; a.ws = nullptr;
   a.colsum2 = colsum ? colsum2 : nullptr;
   ConvGeom g = {};
-  if (dtype == MR_F32) return launch_tn<float, 0>(a, g, stream);
-  return launch_tn<bf16_t, 0>(a, g, stream);
+  if (dtype == MR_F32) return launch_tn<float, 0>(a, g, false, stream);
+  return launch_tn<bf16_t, 0>(a, g, false, stream);
 }
 
 static int fill_geom(ConvGeom& g, int mode, int Hg, int Wg, int Cg, int ldg, int Hm, int Wm, int R, int S, int sh,
@@ -964,9 +867,10 @@ static int fill_geom(ConvGeom& g, int mode, int Hg, int Wg, int Cg, int ldg, int
 }
 
 // y[n,ho,wo,k] = act(bias[k] + sum_{r,s,c} x[n, ho*sh-ph+r*dh, wo*sw-pw+s*dw, c] * w[k,r,s,c])
-int mr_conv2d_fwd(int dtype, const void* x, const void* w_krsc, const float* bias, void* y, int relu, int Nimg,
-                  int H, int W, int Cin, int ldx, int Cout, int ldy, int R, int S, int sh, int sw, int ph, int pw,
-                  int dh, int dw, int Ho, int Wo, hipStream_t stream) {
+// (o: bias / ReLU and what else the caller wants of the epilogue)
+static int conv2d_fwd(int dtype, const void* x, const void* w_krsc, void* y, NtEpilogue& o, int Nimg, int H, int W, int Cin,
+                      int ldx, int Cout, int ldy, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int Ho, int Wo,
+                      hipStream_t stream) {
   MR_CHECK_ARG(dtype == MR_F32 || dtype == MR_BF16, "mr_conv2d_fwd: bad dtype %d", dtype);
   const int vec = dtype == MR_F32 ? 4 : 8;
   MR_CHECK_ARG(Cin % vec == 0 && ldx % vec == 0, "mr_conv2d_fwd: Cin (%d) and ldx (%d) must be multiples of %d",
@@ -980,11 +884,19 @@ int mr_conv2d_fwd(int dtype, const void* x, const void* w_krsc, const float* bia
   ConvGeom g;
   fill_geom(g, 1, H, W, Cin, ldx, Ho, Wo, R, S, sh, sw, ph, pw, dh, dw);
   if (R * S <= 32) {
-    if (dtype == MR_F32) return dispatch_nt_store<float, 2>(a, g, y, ldy, bias, relu, stream);
-    return dispatch_nt_store<bf16_t, 2>(a, g, y, ldy, bias, relu, stream);
+    if (dtype == MR_F32) return dispatch_nt_store<float, 2>(a, g, y, ldy, o, stream);
+    return dispatch_nt_store<bf16_t, 2>(a, g, y, ldy, o, stream);
   }
-  if (dtype == MR_F32) return dispatch_nt_store<float, 1>(a, g, y, ldy, bias, relu, stream);
-  return dispatch_nt_store<bf16_t, 1>(a, g, y, ldy, bias, relu, stream);
+  if (dtype == MR_F32) return dispatch_nt_store<float, 1>(a, g, y, ldy, o, stream);
+  return dispatch_nt_store<bf16_t, 1>(a, g, y, ldy, o, stream);
+}
+int mr_conv2d_fwd(int dtype, const void* x, const void* w_krsc, const float* bias, void* y, int relu, int Nimg,
+                  int H, int W, int Cin, int ldx, int Cout, int ldy, int R, int S, int sh, int sw, int ph, int pw,
+                  int dh, int dw, int Ho, int Wo, hipStream_t stream) {
+  NtEpilogue o;
+  o.bias = bias;
+  o.relu = relu;
+  return conv2d_fwd(dtype, x, w_krsc, y, o, Nimg, H, W, Cin, ldx, Cout, ldy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo, stream);
 }
 
 // host only: 1 when mr_conv2d_fwd_pool serves this geometry (else run mr_conv2d_fwd + mr_maxpool_fwd)
@@ -1032,22 +944,19 @@ int mr_conv2d_fwd_stats(int dtype, const void* x, const void* w_krsc, const floa
                         int Nimg, int H, int W, int Cin, int ldx, int Cout, int R, int S, int sh, int sw, int ph, int pw,
                         int dh, int dw, int Ho, int Wo, hipStream_t stream) {
   MR_CHECK_ARG(bn_sums != nullptr, "mr_conv2d_fwd_stats: bn_sums is null");
-  g_epi_stats = bn_sums;
-  g_epi_stats_missed = false;
-  const int rc = mr_conv2d_fwd(dtype, x, w_krsc, bias, y, 0, Nimg, H, W, Cin, ldx, Cout, Cout, R, S, sh, sw, ph, pw, dh, dw,
-                               Ho, Wo, stream);
-  const bool missed = g_epi_stats_missed;
-  g_epi_stats = nullptr;
-  g_epi_stats_missed = false;
+  NtEpilogue o;
+  o.bias = bias;
+  o.stats = bn_sums;
+  const int rc = conv2d_fwd(dtype, x, w_krsc, y, o, Nimg, H, W, Cin, ldx, Cout, Cout, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo, stream);
   if (rc != MR_OK) return rc;
-  if (missed) return mr_bn_stats(dtype, y, bn_sums, (long long)Nimg * Ho * Wo, Cout, stream);
+  if (o.stats_missed) return mr_bn_stats(dtype, y, bn_sums, (long long)Nimg * Ho * Wo, Cout, stream);
   return MR_OK;
 }
 
 // dx[n,h,w,c] = sum_{r,s,k} dy[n,(h+ph-r*dh)/sh,(w+pw-s*dw)/sw,k] * w[k,r,s,c]; w_crsk = w transposed to [c][r][s][k]
-int mr_conv2d_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, int Nimg, int H, int W, int Cin,
-                    int lddx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw,
-                    int Ho, int Wo, hipStream_t stream) {
+static int conv2d_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, NtEpilogue& o, int Nimg, int H, int W, int Cin,
+                        int lddx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int Ho, int Wo,
+                        hipStream_t stream) {
   MR_CHECK_ARG(dtype == MR_F32 || dtype == MR_BF16, "mr_conv2d_dgrad: bad dtype %d", dtype);
   const int vec = dtype == MR_F32 ? 4 : 8;
   MR_CHECK_ARG(Cout % vec == 0 && lddy % vec == 0, "mr_conv2d_dgrad: Cout/lddy must be multiples of %d", vec);
@@ -1057,11 +966,17 @@ int mr_conv2d_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, int
   ConvGeom g;
   fill_geom(g, 2, Ho, Wo, Cout, lddy, H, W, R, S, sh, sw, ph, pw, dh, dw);
   if (R * S <= 32 && sh == 1 && sw == 1) {
-    if (dtype == MR_F32) return dispatch_nt_store<float, 2>(a, g, dx, lddx, nullptr, 0, stream);
-    return dispatch_nt_store<bf16_t, 2>(a, g, dx, lddx, nullptr, 0, stream);
+    if (dtype == MR_F32) return dispatch_nt_store<float, 2>(a, g, dx, lddx, o, stream);
+    return dispatch_nt_store<bf16_t, 2>(a, g, dx, lddx, o, stream);
   }
-  if (dtype == MR_F32) return dispatch_nt_store<float, 1>(a, g, dx, lddx, nullptr, 0, stream);
-  return dispatch_nt_store<bf16_t, 1>(a, g, dx, lddx, nullptr, 0, stream);
+  if (dtype == MR_F32) return dispatch_nt_store<float, 1>(a, g, dx, lddx, o, stream);
+  return dispatch_nt_store<bf16_t, 1>(a, g, dx, lddx, o, stream);
+}
+int mr_conv2d_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, int Nimg, int H, int W, int Cin,
+                    int lddx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw,
+                    int Ho, int Wo, hipStream_t stream) {
+  NtEpilogue o;
+  return conv2d_dgrad(dtype, dy, w_crsk, dx, o, Nimg, H, W, Cin, lddx, Cout, lddy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo, stream);
 }
 
 // mr_conv2d_dgrad with a second summand in the epilogue: dx = dgrad(dy, w) + addend (addend: NHWC like dx, same lddx).  A
@@ -1072,11 +987,9 @@ int mr_conv2d_dgrad(int dtype, const void* dy, const void* w_crsk, void* dx, int
 int mr_conv2d_dgrad_add(int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend, int Nimg, int H, int W,
                         int Cin, int lddx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw,
                         int Ho, int Wo, hipStream_t stream) {
-  g_epi_addend = addend;
-  const int rc = mr_conv2d_dgrad(dtype, dy, w_crsk, dx, Nimg, H, W, Cin, lddx, Cout, lddy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo,
-                                 stream);
-  g_epi_addend = nullptr;
-  return rc;
+  NtEpilogue o;
+  o.addend = addend;
+  return conv2d_dgrad(dtype, dy, w_crsk, dx, o, Nimg, H, W, Cin, lddx, Cout, lddy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo, stream);
 }
 
 // mr_conv2d_dgrad_add that ALSO leaves the BatchNorm-backward sums of the gradient it produces: dx is the gradient of the output
@@ -1094,24 +1007,21 @@ int mr_conv2d_dgrad_bnb(int dtype, const void* dy, const void* w_crsk, void* dx,
   MR_CHECK_ARG(bn_x && bn_mean && bn_rstd && bn_sums && produced, "mr_conv2d_dgrad_bnb: null BatchNorm operand");
   MR_CHECK_ARG(lddx == Cin, "mr_conv2d_dgrad_bnb: dx must be dense (lddx == Cin), like the BatchNorm's tensors");
   MR_CHECK_ARG(aligned16(bn_x) && (bn_y == nullptr || aligned16(bn_y)), "mr_conv2d_dgrad_bnb: bn_x / bn_y must be 16-byte aligned");
-  g_epi_addend = addend;
-  g_epi_stats = bn_sums;
-  g_epi_stats_missed = false;
-  g_epi_bnb = BnbRequest{bn_x, bn_y, bn_mean, bn_rstd};
-  const int rc = mr_conv2d_dgrad(dtype, dy, w_crsk, dx, Nimg, H, W, Cin, lddx, Cout, lddy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo,
-                                 stream);
-  *produced = g_epi_stats_missed ? 0 : 1;
-  g_epi_addend = nullptr;
-  g_epi_stats = nullptr;
-  g_epi_stats_missed = false;
-  g_epi_bnb = BnbRequest{nullptr, nullptr, nullptr, nullptr};
+  NtEpilogue o;
+  o.addend = addend;
+  o.stats = bn_sums;
+  o.bnb = BnbRequest{bn_x, bn_y, bn_mean, bn_rstd};
+  const int rc = conv2d_dgrad(dtype, dy, w_crsk, dx, o, Nimg, H, W, Cin, lddx, Cout, lddy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo,
+                              stream);
+  *produced = o.stats_missed ? 0 : 1;
   return rc;
 }
 
 // dw[k,r,s,c] += sum_{n,ho,wo} dy[n,ho,wo,k] * x[n, ho*sh-ph+r*dh, wo*sw-pw+s*dw, c]   (f32, atomically accumulated)
-int mr_conv2d_wgrad(int dtype, const void* dy, const void* x, float* dw_krsc, float* dbias, int Nimg, int H, int W,
-                    int Cin, int ldx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw, int dh,
-                    int dw, int Ho, int Wo, hipStream_t stream) {
+// (beside: see launch_tn)
+static int conv2d_wgrad(int dtype, const void* dy, const void* x, float* dw_krsc, float* dbias, int Nimg, int H, int W, int Cin,
+                        int ldx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw, int dh, int dw, int Ho, int Wo,
+                        bool beside, hipStream_t stream) {
   MR_CHECK_ARG(dtype == MR_F32 || dtype == MR_BF16, "mr_conv2d_wgrad: bad dtype %d", dtype);
   const int vec = dtype == MR_F32 ? 4 : 8;
   // Cout need not be a multiple of the vector width as long as the rows of dy are (lddy): the operand loads then read the
@@ -1124,42 +1034,37 @@ int mr_conv2d_wgrad(int dtype, const void* dy, const void* x, float* dw_krsc, fl
   a.ldb = 0; a.ldc = R * S * Cin; a.p_chunk = 0; a.row_perm_h = 0; a.colsum = dbias; a.rowtab = nullptr; a.grp = 1; a.ws = nullptr;
   ConvGeom g;
   fill_geom(g, 1, H, W, Cin, ldx, Ho, Wo, R, S, sh, sw, ph, pw, dh, dw);
-  if (dtype == MR_F32) return launch_tn<float, 1>(a, g, stream);
-  return launch_tn<bf16_t, 1>(a, g, stream);
+  if (dtype == MR_F32) return launch_tn<float, 1>(a, g, beside, stream);
+  return launch_tn<bf16_t, 1>(a, g, beside, stream);
+}
+int mr_conv2d_wgrad(int dtype, const void* dy, const void* x, float* dw_krsc, float* dbias, int Nimg, int H, int W,
+                    int Cin, int ldx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw, int dh,
+                    int dw, int Ho, int Wo, hipStream_t stream) {
+  return conv2d_wgrad(dtype, dy, x, dw_krsc, dbias, Nimg, H, W, Cin, ldx, Cout, lddy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo, false,
+                      stream);
 }
 
 // Same as mr_conv2d_wgrad with a caller-owned ROW TABLE of the gather (8 bytes per output pixel, see
-// tn_rowtab_kernel): build != 0 fills it first (one small kernel), build == 0 trusts its contents -- the geometry of
+// tn_rowtab_kernel): build bit 0 fills it first (one small kernel), otherwise its contents are trusted -- the geometry of
 // a layer never changes, so callers build it once and pass it to every later step.  bf16, R*S <= 32 only
 // (otherwise, or with rowtab == null, this is mr_conv2d_wgrad).
-static int conv2d_wgrad_tab_impl(int dtype, const void* dy, const void* x, float* dw_krsc, float* dbias, int Nimg, int H,
-                                 int W, int Cin, int ldx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw,
-                                 int dh, int dw, int Ho, int Wo, void* rowtab, int build, hipStream_t stream);
-// build: bit 0 = fill the row table first; bit 1 = the launch may run CONCURRENTLY with other weight-gradient launches (a side
-// stream): the shared split-reduction workspace is then left alone (f32 atomics only), see mr_set_tn_taps_workspace.
+// build bit 1 = the launch may run CONCURRENTLY with other weight-gradient launches (a side stream): the shared split-reduction
+// workspace is then left alone (f32 atomics only), see mr_set_tn_taps_workspace.
 int mr_conv2d_wgrad_tab(int dtype, const void* dy, const void* x, float* dw_krsc, float* dbias, int Nimg, int H,
                         int W, int Cin, int ldx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw,
                         int dh, int dw, int Ho, int Wo, void* rowtab, int build, hipStream_t stream) {
-  taps_set_concurrent((build & 2) != 0);
-  const int rc = conv2d_wgrad_tab_impl(dtype, dy, x, dw_krsc, dbias, Nimg, H, W, Cin, ldx, Cout, lddy, R, S, sh, sw, ph, pw, dh,
-                                       dw, Ho, Wo, rowtab, build & 1, stream);
-  taps_set_concurrent(false);
-  return rc;
-}
-
-static int conv2d_wgrad_tab_impl(int dtype, const void* dy, const void* x, float* dw_krsc, float* dbias, int Nimg, int H,
-                                 int W, int Cin, int ldx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw,
-                                 int dh, int dw, int Ho, int Wo, void* rowtab, int build, hipStream_t stream) {
+  const bool beside = (build & 2) != 0;
+  build &= 1;
   if (rowtab == nullptr || dtype != MR_BF16 || R * S > 32 || g_nt_variant != 2)
-    return mr_conv2d_wgrad(dtype, dy, x, dw_krsc, dbias, Nimg, H, W, Cin, ldx, Cout, lddy, R, S, sh, sw, ph, pw, dh,
-                           dw, Ho, Wo, stream);
+    return conv2d_wgrad(dtype, dy, x, dw_krsc, dbias, Nimg, H, W, Cin, ldx, Cout, lddy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo,
+                        beside, stream);
   MR_CHECK_ARG(Cin % 8 == 0 && ldx % 8 == 0 && lddy % 8 == 0 && Cout > 0 && Cout <= lddy,
                "mr_conv2d_wgrad_tab: Cin/ldx/lddy must be multiples of 8 and Cout <= lddy");
   MR_CHECK_ARG(aligned16(dy) && aligned16(x) && ((uintptr_t)rowtab & 7) == 0, "mr_conv2d_wgrad_tab: alignment");
   if (g_tn_taps && taps_eligible(Nimg, H, W, Cin, ldx, Cout, lddy, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo,
                                  (long long)Nimg * Ho * Wo * 8)) {
     TapsProblem tp;
-    tp.dy = dy; tp.x = x; tp.dw = dw_krsc; tp.dbias = dbias; tp.tab = (int*)rowtab; tp.build = build;
+    tp.dy = dy; tp.x = x; tp.dw = dw_krsc; tp.dbias = dbias; tp.tab = (int*)rowtab; tp.build = build; tp.beside = beside;
     tp.N = Nimg; tp.H = H; tp.W = W; tp.Cin = Cin; tp.ldx = ldx; tp.Cout = Cout; tp.lddy = lddy; tp.dil = dh;
     return launch_tn_taps(tp, g_tn_splits, stream);
   }
@@ -1172,7 +1077,7 @@ static int conv2d_wgrad_tab_impl(int dtype, const void* dy, const void* x, float
     hipLaunchKernelGGL(tn_rowtab_kernel, dim3(cdiv(a.P, 256)), dim3(256), 0, stream, g, a.P, (int2*)rowtab);
     MR_CHECK_LAUNCH();
   }
-  return launch_tn<bf16_t, 2>(a, g, stream);
+  return launch_tn<bf16_t, 2>(a, g, beside, stream);
 }
 
 }  // extern "C"

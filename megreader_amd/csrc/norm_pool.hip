@@ -1,7 +1,7 @@
 // BatchNorm2d (training statistics) and MaxPool2d on NHWC tensors.  HBM-bound kernels.
 // Reference call sites: backbones/crnn.py:17-31,49-52 (MaxPool2d((2,2)), MaxPool2d((2,2),(2,1),(0,1)),
 // BatchNorm2d without activation), backbones/resnet.py:26-30 (BatchNorm2d), resnet.py:199 (MaxPool2d 3x3 s2 p1).
-#include "common.h"
+#include "device.h"
 #include "../../include/megreader_hip.h"
 
 
@@ -895,9 +895,9 @@ static inline int bn_fused_grid_x(long long P, int rows, int slabs) {
 static int bn_onepass_cap() {
   static int cap = -1;
   if (cap >= 0) return cap;
-  int dev = 0, cus = 0, occ_b = 0, occ_f = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+  const int cus = device_cus();
+  int occ_b = 0, occ_f = 0;
+  if (cus == 0 ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_b, bn_bwd_onepass_kernel<bf16_t, 8>, 256, 0) != hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_f, bn_bwd_onepass_kernel<float, 8>, 256, 0) != hipSuccess) {
     (void)hipGetLastError();

@@ -1,6 +1,7 @@
 // Per-shape launcher of the ping-pong 32x32x16 NT kernel: included by nt32_s<N>.hip with MR_NT32_SHAPE defined (one translation
 // unit per tile shape: the instantiations are the slowest compiles of the library).
 #include "nt32.h"
+#include "device.h"
 #include "igemm_nt32.h"
 
 #if MR_NT32_SHAPE == 1      // 256x256: 2x4 waves of 128x64
@@ -37,14 +38,7 @@ static int launch_one(const NtArgs& a, const ConvGeom& g, const EpiStore<bf16_t>
   constexpr size_t lds_stage = 2 * (size_t)(BM + BN) * 128, lds_out = (size_t)BM * BN * 2;   // stage buffers; output tile (epilogue)
   constexpr size_t lds = lds_stage > lds_out ? lds_stage : lds_out;
   auto kern = igemm_nt32_kernel<S_WM, S_WN, S_TM, S_TN, AMODE, EpiStore<bf16_t>, PH, OPT, ABL>;
-  static bool attr_set = false;  // per instantiation
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      set_error("hipFuncSetAttribute(max dynamic LDS = %zu) failed", lds);
-      return MR_ERR_LAUNCH;
-    }
-    attr_set = true;
-  }
+  if (const int rc = ensure_dynamic_lds(kern, lds)) return rc;
   const int tiles_m = cdiv(a.M - a.m_begin, BM), tiles_n = cdiv(a.N, BN);
   const int grid = cdiv(tiles_m, 8) * 8 * tiles_n;  // XCD-aware map: see the kernel
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, a, g, epi);

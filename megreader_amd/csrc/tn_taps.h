@@ -13,6 +13,7 @@ struct TapsProblem {
   float* dbias;     // optional [Cout]: += column sums of dy
   int* tab;         // caller-owned table, >= taps_table_ints(...) ints
   int build;        // != 0: fill the table first
+  bool beside;      // the launch may run beside TN launches of another stream: it must not touch the shared workspace
   int N, H, W, Cin, ldx, Cout, lddy, dil;
 };
 
@@ -23,7 +24,6 @@ int taps_eligible(int N, int H, int W, int Cin, int ldx, int Cout, int lddy, int
 // once by the caller; launches that use it must be stream-ordered with respect to each other.
 void taps_set_workspace(void* p, long long bytes);
 void taps_get_workspace(void** p, long long* bytes);   // the current device's registered workspace (or null, 0)
-void taps_set_concurrent(bool on);   // this host thread's next launches must not touch the shared workspace
 #ifdef MR_ABLATION
 int taps_set_abl(int mask);   // timing-only ablations (wrong results), see tn_taps.hip
 #endif

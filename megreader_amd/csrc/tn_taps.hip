@@ -25,6 +25,7 @@
 // 36 MFMAs) per wave.  Wave w owns Cin columns 16w..16w+15 of the block for all 4 Cout row tiles and all 9 taps
 // (36 accumulator tiles = 144 registers).
 #include "tn_taps.h"
+#include "device.h"
 #include "tuning.h"
 #include "igemm_core.h"
 
@@ -396,19 +397,6 @@ static __global__ __launch_bounds__(256) void taps_finalize_kernel(const f32x4* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-static int taps_num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
-      cus = p.multiProcessorCount;
-    else
-      cus = 256;
-  }
-  return cus;
-}
-
 struct TapsLayout {
   int Wp, IP, len;   // len = table length (multiple of 64)
 };
@@ -437,27 +425,18 @@ int taps_eligible(int N, int H, int W, int Cin, int ldx, int Cout, int lddy, int
 }
 
 // one workspace per device (one process may drive several GPUs): indexed by the current device at set / launch time
-static void* g_taps_ws_dev[64] = {nullptr};
-static long long g_taps_ws_bytes_dev[64] = {0};
+static void* g_taps_ws_dev[MR_MAX_DEVICES] = {nullptr};
+static long long g_taps_ws_bytes_dev[MR_MAX_DEVICES] = {0};
 #define g_taps_grp MR_TUNE(tn_taps_group)   // 0 = automatic, 1 = atomics only, > 1 = forced group size
-static int taps_cur_dev() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  return dev;
-}
-// set while a launch may run concurrently with other TN launches on another stream (mr_conv2d_wgrad_tab flags bit 1): the shared
-// split-reduction workspace (tickets + slabs) must then not be used -- its launches have to be stream-ordered with each other
-static thread_local bool g_tn_concurrent = false;
-void taps_set_concurrent(bool on) { g_tn_concurrent = on; }
 void taps_set_workspace(void* p, long long bytes) {
-  const int dev = taps_cur_dev();
+  const int dev = current_device();
   if (dev < 0) return;
   g_taps_ws_dev[dev] = p;
   g_taps_ws_bytes_dev[dev] = p ? bytes : 0;
 }
 void taps_get_workspace(void** p, long long* bytes) {
-  const int dev = taps_cur_dev();
-  *p = (dev >= 0 && !g_tn_concurrent) ? g_taps_ws_dev[dev] : nullptr;
+  const int dev = current_device();
+  *p = dev >= 0 ? g_taps_ws_dev[dev] : nullptr;
   *bytes = dev >= 0 ? g_taps_ws_bytes_dev[dev] : 0;
 }
 
@@ -501,7 +480,7 @@ int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream
   a.dil = p.dil;
   a.nchunks = l.len / 64;
   const int tiles = cdiv(p.Cout, 64) * (p.Cin / 64);
-  const int cus = taps_num_cus();
+  const int cus = num_cus();
   const int w8 = g_taps_w8;
   const int per_cu = w8 ? 1 : 2;   // resident workgroups per CU
   const int halves = w8 ? 2 : 1;   // independent reduction ranges per workgroup
@@ -521,9 +500,9 @@ int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream
   splits = cdiv(a.nchunks, a.cps * halves);
   // group reduction: needs the registered workspace (tickets + one slab per workgroup) and unique tickets
   a.grp = 1;
-  const int dev = taps_cur_dev();
-  void* const g_taps_ws = (dev >= 0 && !g_tn_concurrent) ? g_taps_ws_dev[dev] : nullptr;
-  const long long g_taps_ws_bytes = dev >= 0 ? g_taps_ws_bytes_dev[dev] : 0;
+  void* g_taps_ws = nullptr;
+  long long g_taps_ws_bytes = 0;
+  if (!p.beside) taps_get_workspace(&g_taps_ws, &g_taps_ws_bytes);
   a.ws = g_taps_ws;
   {
     int want = g_taps_grp ? g_taps_grp : (splits >= 4 ? 4 : (splits >= 2 ? 2 : 1));
@@ -543,20 +522,13 @@ int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream
   }
   const int lds = w8 ? 147456 : (4 + 4) * 64 * 128 + 4096;
   const int threads = w8 ? 512 : 256;
-  static bool attr_set[2] = {false, false};
   const void* kp = w8 ? (const void*)igemm_tn_taps_kernel<2, 1, 0, true> : (const void*)igemm_tn_taps_kernel<2, 1, 0, false>;
-  if (!attr_set[w8]) {
-    if (hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      set_error("hipFuncSetAttribute(max dynamic LDS = %d) failed", lds);
-      return MR_ERR_LAUNCH;
-    }
-    attr_set[w8] = true;
-  }
+  if (const int rc = ensure_dynamic_lds(kp, lds)) return rc;
 #ifdef MR_ABLATION
   if (g_taps_abl && !w8) {
     a.fin = 0;
 #define MR_TAPS_ABL(V_) case V_: { auto k2 = igemm_tn_taps_kernel<2, 1, V_>; \
-      (void)hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
+      if (const int rc = ensure_dynamic_lds(k2, lds)) return rc; \
       hipLaunchKernelGGL(k2, dim3(tiles * splits), dim3(256), lds, stream, a); } break;
     switch (g_taps_abl) { MR_TAPS_ABL(1) MR_TAPS_ABL(2) MR_TAPS_ABL(4) MR_TAPS_ABL(8) MR_TAPS_ABL(16) MR_TAPS_ABL(6)
       MR_TAPS_ABL(7) MR_TAPS_ABL(15) MR_TAPS_ABL(31) MR_TAPS_ABL(32) MR_TAPS_ABL(64) MR_TAPS_ABL(128) MR_TAPS_ABL(256) MR_TAPS_ABL(512) MR_TAPS_ABL(1024) MR_TAPS_ABL(1536) MR_TAPS_ABL(2048) MR_TAPS_ABL(2056) MR_TAPS_ABL(9)
