@@ -257,8 +257,7 @@ _TN_WS_CALLS = frozenset(("mr_gemm_tn", "mr_gemm_tn2", "mr_conv2d_wgrad", "mr_co
 def ensure_tn_workspace(device=None):
     """Register (once per device) the workspace of the weight-gradient kernels' in-launch split reduction
     (mr_set_tn_taps_workspace): 16 KB of tickets + one 147456-byte slab per workgroup of a full launch (2 per CU).
-    Launches that use it must be stream-ordered with each other: MEGREADER_FAN / MEGREADER_OVERLAP (weight-gradient
-    GEMMs forked onto side streams) switch the reduction back to plain atomics."""
+    Launches that use it must be stream-ordered with each other."""
     if device is None:
         idx = torch.cuda.current_device()
     else:
@@ -274,8 +273,6 @@ def ensure_tn_workspace(device=None):
             rc = lib.mr_set_tn_taps_workspace(ws.data_ptr(), nbytes)
         if rc != 0:
             raise RuntimeError("mr_set_tn_taps_workspace failed: %s" % lib.mr_last_error().decode())
-        if os.environ.get("MEGREADER_FAN", "0") == "1" or os.environ.get("MEGREADER_OVERLAP", "0") == "1":
-            set_tuning(tn_group=1, tn_taps_group=1, nt_ksplit=0)      # GEMMs of one layer on several streams: nobody may use the shared slabs / tickets
     return ws
 
 
@@ -305,7 +302,7 @@ def call(name, *args):
             timer.deferred.append((name, args))          # recorded, not launched: its time is the flush's
         else:
             timer.records.append((name, args, e0, e1))
-    elif timer is not None and timer.track_deferred and name in ("mr_tn_flush", "mr_tn_flush_beside") and timer.deferred:
+    elif timer is not None and timer.track_deferred and name == "mr_tn_flush" and timer.deferred:
         group, timer.deferred = timer.deferred, []
         rc, e0, e1 = _bracketed(getattr(lib, name), args)
         timer.records.append(("mr_tn_flush", group, e0, e1))

@@ -8,7 +8,6 @@ reference's names and shapes; every forward converts them to the operand images 
 There is no CPU path in this file: CPU tensors raise NotImplementedError (same as the reference's
 ``ops/ctc_2d/ctc_loss_2d.py:12-13`` does for its CUDA-only op).
 """
-import contextlib
 import ctypes
 import os
 
@@ -114,72 +113,6 @@ def zero_segments(segments):
         call("mr_zero_multi", n, (ctypes.c_void_p * n)(*[p for p, _ in chunk]), (ctypes.c_longlong * n)(*[b for _, b in chunk]))
 
 
-class _Side(object):
-    """Side HIP stream for weight-gradient GEMMs that nothing later in the backward pass depends on.  The LSTM
-    recurrences are launch-latency-bound chains that leave most CUs idle; the weight-gradient GEMMs of one layer run
-    beside the recurrence chain of the next.  Fork = the side stream waits for the producing stream; join = an
-    autograd-engine callback at the end of the backward pass makes the backward stream wait for the side stream, so
-    everything after `backward()` (optimizer, gradient clipping, the next zero_grad) is ordered as usual.  Inside a
-    hipGraph capture this records a fork/join in the graph."""
-    stream = None
-    pending = []    # tensors the side stream still reads / writes: kept alive until the join
-    queued = False
-    enabled = os.environ.get("MEGREADER_OVERLAP", "0") == "1"  # measured slower on the CRNN step (see DESIGN.md): off
-
-    @staticmethod
-    def fork():
-        main = torch.cuda.current_stream()
-        if _Side.stream is None or _Side.stream.device != main.device:
-            _Side.stream = torch.cuda.Stream(device=main.device)
-        _Side.stream.wait_stream(main)
-        if not _Side.queued:
-            torch.autograd.Variable._execution_engine.queue_callback(_Side.join)
-            _Side.queued = True
-        return _Side.stream
-
-    @staticmethod
-    def join():
-        if _Side.stream is not None:
-            torch.cuda.current_stream().wait_stream(_Side.stream)
-        del _Side.pending[:]
-        _Side.queued = False
-
-
-class _Fan(object):
-    """Fork/join of INDEPENDENT launches inside one autograd Function: the weight-gradient GEMMs of an LSTM / Linear
-    layer (dense TN GEMMs with 16..64 output tiles: each alone leaves most CUs with one latency-bound workgroup or none,
-    tools/microbench_tn_dense.py) run on side HIP streams beside each other and beside the layer's input-gradient GEMM,
-    and are joined before the Function returns -- nothing outlives the call, unlike _Side.  Inside a hipGraph capture the
-    event waits become parallel branches of the graph.
-    MEASURED SLOWER on the CRNN step (3.31 ms with, 3.17 ms without; gpurun_out r2p): the four GEMMs compete for the
-    same CUs and lose their XCD-local tile maps; the per-launch fix that did pay is the split model in
-    gemm_conv.hip:launch_tn.  Off unless MEGREADER_FAN=1."""
-    streams = {}
-    enabled = os.environ.get("MEGREADER_FAN", "0") == "1"
-
-    @staticmethod
-    def run(fns):
-        """fns[0] runs on the current stream, fns[1:] on side streams; returns after the current stream waits for all."""
-        fns = [f for f in fns if f is not None]
-        if not fns:
-            return
-        if not _Fan.enabled or len(fns) == 1:
-            for f in fns:
-                f()
-            return
-        main = torch.cuda.current_stream()
-        pool = _Fan.streams.setdefault(main.device, [])
-        while len(pool) < len(fns) - 1:
-            pool.append(torch.cuda.Stream(device=main.device))
-        for st, f in zip(pool, fns[1:]):
-            st.wait_stream(main)
-            with torch.cuda.stream(st):
-                f()
-        fns[0]()
-        for st in pool[:len(fns) - 1]:
-            main.wait_stream(st)
-
-
 def accumulate_multi(pairs):
     """dst += src for a list of (dst, src) dense f32 tensor pairs, 8 pairs per launch (mr_accumulate_multi)."""
     for i in range(0, len(pairs), 8):
@@ -198,20 +131,11 @@ class _TnDefer(object):
     an autograd-engine callback at the end of the backward pass, earlier whenever MAX problems are waiting.  The operands of the
     recorded problems are kept alive here until the flush; parameters are reported to data-parallel wrappers
     (notify_grad_ready) only after the launch that completes their gradient.
-    MEGREADER_TN_DEFER=0 (or mr_tuning.tn_defer = 0): every launch immediate (A/B)."""
+    MEGREADER_TN_DEFER=0 (or mr_tuning.tn_defer = 0): every launch immediate (A/B).
+    Every launch stays on the backward stream: forking weight-gradient launches onto side streams was measured slower in
+    every step (CHANGELOG.md, "Retired: the side-stream weight-gradient switches")."""
     enabled = os.environ.get("MEGREADER_TN_DEFER", "1") != "0"
     MAX = 12
-    # MEGREADER_TN_SIDE: where a flush in the MIDDLE of a backward pass is launched.  0: on the backward stream.  1: the group a
-    # BiLSTM layer closes (its four weight gradients + the Linear layers recorded behind it) goes to the side stream (_Side),
-    # beside the next layer's recurrence -- a latency chain on half of the CUs.  2: also the convolution problems, SIDE_MAX at a
-    # time, beside the input-gradient chain (pays when that chain's launches leave CUs idle: small per-GPU batches).
-    # Never for parameters a data-parallel wrapper watches (it wants the gradients as they complete, on the backward stream).
-    # MEASURED SLOWER in every replayed step (profiles/r05_ab_tn_side_stream.txt: CRNN 2.542 -> 2.565 / 2.560 ms, 32 crops 1.154 ->
-    # 1.173 / 1.210, Res50-PPM 11.21 -> 11.69, FPN-attention 8.25 -> 9.37, DB 9.05 -> 9.83 for modes 1 / 2): a grouped launch
-    # holds 198 VGPRs per lane, so the recurrence's workgroups cannot share a SIMD with it and wait for its CUs anyway, and
-    # beside the convolution chain the two streams evict each other's L2 lines.  Default 0; kept as an A/B switch.
-    side = int(os.environ.get("MEGREADER_TN_SIDE", "0"))
-    SIDE_MAX = int(os.environ.get("MEGREADER_TN_SIDE_MAX", "3"))
     keep = []
     notify = []
     queued = False
@@ -282,26 +206,13 @@ class _TnDefer(object):
         _TnDefer.keep.extend(t for t in tensors if t is not None)
         _TnDefer.notify.extend(params)
         if n >= _TnDefer.MAX:
-            _TnDefer.flush(final=False, side=_TnDefer.side >= 2)
-        elif _TnDefer.side >= 2 and n >= _TnDefer.SIDE_MAX:
-            _TnDefer.flush(final=False, side=True, only_side=True)
+            _TnDefer.flush(final=False)
         return True
 
     @staticmethod
-    def flush(final=True, side=False, only_side=False):
-        """side: the caller is in the middle of a backward pass and nothing before its end reads these gradients -- launch on
-        the side stream if MEGREADER_TN_SIDE allows (only_side: or not at all yet)."""
+    def flush(final=True):
+        """Launch what is recorded and report its parameters ready; final: the end-of-backward callback of the graph task."""
         if load().mr_tn_pending():
-            watched = any(getattr(p, "_mr_grad_ready_hooks", None) for p in _TnDefer.notify)
-            if side and not final and _TnDefer.side >= 1 and not watched:
-                with torch.cuda.stream(_Side.fork()):
-                    call("mr_tn_flush_beside")
-                _Side.pending.extend(_TnDefer.keep)      # operands stay alive until the join at the end of the backward pass
-                del _TnDefer.keep[:]
-                del _TnDefer.notify[:]                   # nobody watches these parameters
-                return
-            if only_side:
-                return
             call("mr_tn_flush")
         ready, _TnDefer.notify = _TnDefer.notify, []
         del _TnDefer.keep[:]
@@ -312,6 +223,16 @@ class _TnDefer(object):
             notify_grad_ready(p)
 
 
+def _wgrad(launch, may_defer, keep, params, immediate=None):
+    """The weight-gradient launch of one layer.  may_defer (every gradient it writes goes to a sink) and _TnDefer.begin()
+    succeeds: `launch` under recording, `keep` alive and `params` reported ready by the flush; True when the problems were
+    really recorded.  Otherwise `immediate` (default: `launch`) now and False: the caller reports its parameters itself."""
+    if may_defer and _TnDefer.begin():
+        return _TnDefer.record(launch, keep, params)
+    (immediate or launch)()
+    return False
+
+
 def discard_deferred_wgrads():
     """Drop every recorded, not yet launched weight-gradient problem (a backward pass that raised; a failed capture)."""
     _TnDefer.abort()
@@ -319,10 +240,8 @@ def discard_deferred_wgrads():
 
 def flush_deferred_wgrads():
     """Launch every recorded weight-gradient problem now (data-parallel wrappers call this before they finalise a backward
-    pass; harmless when nothing is recorded) and make the current stream wait for the ones already launched on the side stream."""
+    pass; harmless when nothing is recorded)."""
     _TnDefer.flush(final=False)
-    if _Side.queued:
-        _Side.join()
 
 
 def to_internal(x, dtype):
@@ -571,17 +490,13 @@ class Conv2dFn(Function):
                 # (Kw % 8: the all-taps kernel needs whole channel vectors and its table has another format than the GEMM
                 # kernel's -- two layers of one geometry that differ in that must not share a table)
                 tab, build = _wgrad_rowtab(g.device, (N, H, W, Cp, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo), Kw % 8 == 0)
-            # sunk gradients have no reader inside the backward pass: the launch may wait and share a grouped launch (_TnDefer)
-            defer = w_sink is not None and (not want_db or b_sink is not None) and _TnDefer.begin()
-
             def wgrad_launch():
                 call("mr_conv2d_wgrad_tab", dt, ptr(g), ptr(xi), ptr(gw), ptr(db) if want_db else 0, N, H, W, Cp, Cp, Kw,
                      Kp, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo, ptr(tab), build)
-            if defer:
-                if _TnDefer.record(wgrad_launch, (g, xi, tab), [weight_p] + ([bias_p] if want_db else [])):
-                    return dx, None, None, None, None, None, None, None, None, None, None
-            else:
-                wgrad_launch()
+            # sunk gradients have no reader inside the backward pass: the launch may wait and share a grouped launch (_TnDefer)
+            if _wgrad(wgrad_launch, w_sink is not None and (not want_db or b_sink is not None), (g, xi, tab),
+                      [weight_p] + ([bias_p] if want_db else [])):
+                return dx, None, None, None, None, None, None, None, None, None, None
             if w_sink is not None:
                 dwt = None
                 notify_grad_ready(weight_p)
@@ -1186,27 +1101,14 @@ class LinearFn(Function):
             gb = b_sink if b_sink is not None else torch.zeros((Np,), dtype=torch.float32, device=gy.device)
         if ctx.needs_input_grad[1]:
             gw = w_sink if w_sink is not None else torch.zeros((Np, K), dtype=torch.float32, device=gy.device)
-            # sunk gradients have no consumer inside the backward pass: side stream (see _Side)
-            overlap = (w_sink is not None and (gb is None or b_sink is not None) and _Side.enabled and
-                       not getattr(weight_p, "_mr_grad_ready_hooks", None))
-            if overlap:
+            def lin_launch():
                 if dx_fn is not None:
                     dx_fn()
-                with torch.cuda.stream(_Side.fork()):
-                    call("mr_gemm_tn", dt, ptr(gp), Np, ptr(x2), K, ptr(gw), K, M, NA, K, 0, ptr(gb))
-                _Side.pending.extend((gp, x2))
-            elif (w_sink is not None and (gb is None or b_sink is not None) and not _Fan.enabled and
-                  dtype == torch.bfloat16 and _TnDefer.begin()):
-                # sunk gradients: recorded for a grouped launch (_TnDefer); the flush reports the parameters ready
-                def lin_launch():
-                    if dx_fn is not None:
-                        dx_fn()
-                    call("mr_gemm_tn", dt, ptr(gp), Np, ptr(x2), K, ptr(gw), K, M, NA, K, 0, ptr(gb))
-                if _TnDefer.record(lin_launch, (gp, x2), [weight_p] + ([bias_p] if want_db else [])):
-                    return dx, None, None
-            else:   # input-gradient and weight-gradient GEMMs are independent: side by side (_Fan)
-                _Fan.run([dx_fn, lambda: call("mr_gemm_tn", dt, ptr(gp), Np, ptr(x2), K, ptr(gw), K, M, NA, K, 0,
-                                              ptr(gb))])
+                call("mr_gemm_tn", dt, ptr(gp), Np, ptr(x2), K, ptr(gw), K, M, NA, K, 0, ptr(gb))
+            # sunk gradients: recorded for a grouped launch (_TnDefer); the flush reports the parameters ready
+            if _wgrad(lin_launch, w_sink is not None and (gb is None or b_sink is not None) and dtype == torch.bfloat16,
+                      (gp, x2), [weight_p] + ([bias_p] if want_db else [])):
+                return dx, None, None
             dx_fn = None
             if w_sink is not None:
                 notify_grad_ready(weight_p)
@@ -1316,15 +1218,12 @@ class ConvTranspose2x2Fn(Function):
                     dw = tmp[:, :K4].reshape(Cin, Cout, 2, 2)
             else:
                 gw = w_sink if w_sink is not None else torch.zeros((Cin, K4), dtype=torch.float32, device=dev)
-                defer = w_sink is not None and dtype == torch.bfloat16 and _TnDefer.begin()
 
                 # dW[ci, (co, i, j)] += sum_p x[p, ci] dy2[p, (co, i, j)]: the parameter's own memory order
                 def deconv_launch():
                     call("mr_gemm_tn", dt, ptr(x2), Cin, ptr(dy2), ld2, ptr(gw), K4, P, Cin, K4, 0, 0)
-                if not defer:
-                    deconv_launch()
-                if defer and _TnDefer.record(deconv_launch, (x2, dy2), [weight_p]):
-                    pass
+                if _wgrad(deconv_launch, w_sink is not None and dtype == torch.bfloat16, (x2, dy2), [weight_p]):
+                    pass        # the flush reports the parameter ready
                 elif w_sink is not None:
                     notify_grad_ready(weight_p)
                 else:
@@ -1473,49 +1372,39 @@ class BiLSTMFn(Function):
         dgates = gates
         sinks = [grad_sink(p, tuple(p.shape)) for p in ctx.params]
         use_sinks = all(s is not None for s in sinks)
-        # with sinks nothing downstream consumes the weight gradients: run their GEMMs on the side stream, beside the
-        # next layer's recurrence chain (not under data-parallel hooks, which want the gradients as they complete)
-        overlap = (use_sinks and _Side.enabled and
-                   not any(getattr(p, "_mr_grad_ready_hooks", None) for p in ctx.params))
-        side = _Side.fork() if overlap else None
         dx = dx_fn = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((T, N, I), dtype=dtype, device=dev)
             dx_fn = lambda: call("mr_gemm_nt", dt, ptr(dgates), 8 * H, ptr(wcat_t), 8 * H, ptr(dx), I, 0, 0, T * N, I,
                                  8 * H)
-        if (use_sinks and not overlap and not _Fan.enabled and dtype == torch.bfloat16 and T > 1 and _TnDefer.begin()):
-            # Grouped launch (_TnDefer): the four weight-gradient GEMMs of the layer -- W_ih and W_hh of both directions, each
-            # straight into its sink, the bias sums (column sums of dgates, shared by b_ih and b_hh) into both bias sinks --
-            # plus whatever the Linear layers behind this one recorded run as ONE launch.
-            def lstm_launch():
-                if dx_fn is not None:
-                    dx_fn()
-                P = (T - 1) * N
-                for d in range(2):    # bias gradient = column sums of dgates, added to b_ih AND b_hh by the same launch
-                    call("mr_gemm_tn2", dt, ptr(dgates) + d * 4 * H * es, 8 * H, ptr(x), I, ptr(sinks[4 * d]), I, T * N, 4 * H, I,
-                         H, ptr(sinks[4 * d + 2]), ptr(sinks[4 * d + 3]))
-                # forward direction: dgates[t] (t >= 1) with h[t-1]; reverse direction: dgates[t] (t <= T-2) with h[t+1]
-                call("mr_gemm_tn", dt, ptr(dgates) + N * 8 * H * es, 8 * H, ptr(out), 2 * H, ptr(sinks[1]), H, P, 4 * H, H, H, 0)
-                call("mr_gemm_tn", dt, ptr(dgates) + 4 * H * es, 8 * H, ptr(out) + (N * 2 * H + H) * es, 2 * H, ptr(sinks[5]), H,
-                     P, 4 * H, H, H, 0)
-            if _TnDefer.record(lstm_launch, (dgates, x, out), list(ctx.params)):
-                # one launch for the layer (and the Linear layers recorded behind it); a data-parallel wrapper wants the
-                # gradients as they complete, and the next layer's recurrence is a latency chain that leaves the CUs idle anyway
-                # (MEGREADER_TN_SIDE >= 1: beside that chain, on the side stream)
-                _TnDefer.flush(final=False, side=True)
-            else:
-                for p in ctx.params:
-                    notify_grad_ready(p)
-            return (dx,) + (None,) * 8
-        if overlap and dx_fn is not None:
-            dx_fn()
-        with torch.cuda.stream(side) if overlap else contextlib.nullcontext():
-            # one zeroed scratch: [2,4H,I] input-weight gradients (both directions from ONE GEMM) + [2,4H] bias sums
+        P = (T - 1) * N
+        grads = (None,) * 8
+
+        # Grouped launch (_TnDefer): the four weight-gradient GEMMs of the layer -- W_ih and W_hh of both directions, each
+        # straight into its sink, the bias sums (column sums of dgates, shared by b_ih and b_hh) into both bias sinks --
+        # plus whatever the Linear layers behind this one recorded run as ONE launch.
+        def lstm_grouped():
+            if dx_fn is not None:
+                dx_fn()
+            for d in range(2):    # bias gradient = column sums of dgates, added to b_ih AND b_hh by the same launch
+                call("mr_gemm_tn2", dt, ptr(dgates) + d * 4 * H * es, 8 * H, ptr(x), I, ptr(sinks[4 * d]), I, T * N, 4 * H, I,
+                     H, ptr(sinks[4 * d + 2]), ptr(sinks[4 * d + 3]))
+            # forward direction: dgates[t] (t >= 1) with h[t-1]; reverse direction: dgates[t] (t <= T-2) with h[t+1]
+            call("mr_gemm_tn", dt, ptr(dgates) + N * 8 * H * es, 8 * H, ptr(out), 2 * H, ptr(sinks[1]), H, P, 4 * H, H, H, 0)
+            call("mr_gemm_tn", dt, ptr(dgates) + 4 * H * es, 8 * H, ptr(out) + (N * 2 * H + H) * es, 2 * H, ptr(sinks[5]), H,
+                 P, 4 * H, H, H, 0)
+
+        # Without deferral: both input-weight gradients from ONE GEMM into a zeroed scratch, folded into the sinks afterwards
+        def lstm_immediate():
+            nonlocal grads
+            if dx_fn is not None:
+                dx_fn()
+            # one zeroed scratch: [2,4H,I] input-weight gradients + [2,4H] bias sums
             nfl = 2 * 4 * H * (I + 1)
             # pre-zeroed arena slice (saves a fill launch) ONLY when the scratch is consumed inside this call (sinks): without
             # sinks views of it are returned as parameter gradients, and a later ZeroArena.reset() would hand the same bytes
             # to somebody else while p.grad still points at them
-            arena = None if (overlap or not use_sinks) else ZeroArena.take(dev, (nfl + 1) // 2)
+            arena = ZeroArena.take(dev, (nfl + 1) // 2) if use_sinks else None
             scratch = (arena.view(torch.float32)[:nfl] if arena is not None else
                        torch.zeros((nfl,), dtype=torch.float32, device=dev))
             gw_ih = scratch[:2 * 4 * H * I].view(2, 4 * H, I)
@@ -1525,34 +1414,29 @@ class BiLSTMFn(Function):
             else:
                 gw_hh = torch.zeros((2, 4 * H, H), dtype=torch.float32, device=dev)
                 g_hh = (gw_hh[0], gw_hh[1])
-            P = (T - 1) * N
-            fns = [
-                # bias gradient = column sums of dgates, fused into the same pass
-                lambda: call("mr_gemm_tn", dt, ptr(dgates), 8 * H, ptr(x), I, ptr(gw_ih), I, T * N, 8 * H, I, H,
-                             ptr(gb)),
-                # forward direction: dgates[t] (t>=1) with h[t-1]
-                (lambda: call("mr_gemm_tn", dt, ptr(dgates) + N * 8 * H * es, 8 * H, ptr(out), 2 * H, ptr(g_hh[0]),
-                              H, P, 4 * H, H, H, 0)) if T > 1 else None,
-                # reverse direction: dgates[t] (t<=T-2) with h[t+1]
-                (lambda: call("mr_gemm_tn", dt, ptr(dgates) + 4 * H * es, 8 * H, ptr(out) + (N * 2 * H + H) * es,
-                              2 * H, ptr(g_hh[1]), H, P, 4 * H, H, H, 0)) if T > 1 else None]
-            if overlap:
-                for f in fns:
-                    if f is not None:
-                        f()
-            else:   # the four GEMMs (dx + three weight gradients) are independent: side by side (_Fan)
-                _Fan.run([dx_fn] + fns)
+            # bias gradient = column sums of dgates, fused into the same pass
+            call("mr_gemm_tn", dt, ptr(dgates), 8 * H, ptr(x), I, ptr(gw_ih), I, T * N, 8 * H, I, H, ptr(gb))
+            if T > 1:
+                # forward direction: dgates[t] (t>=1) with h[t-1]; reverse direction: dgates[t] (t<=T-2) with h[t+1]
+                call("mr_gemm_tn", dt, ptr(dgates) + N * 8 * H * es, 8 * H, ptr(out), 2 * H, ptr(g_hh[0]), H, P, 4 * H, H, H, 0)
+                call("mr_gemm_tn", dt, ptr(dgates) + 4 * H * es, 8 * H, ptr(out) + (N * 2 * H + H) * es, 2 * H, ptr(g_hh[1]),
+                     H, P, 4 * H, H, H, 0)
             if use_sinks:
                 # w_ih, b_ih, b_hh of both directions: one launch folds the scratch into the six sinks
                 accumulate_multi([(sinks[0], gw_ih[0]), (sinks[4], gw_ih[1]), (sinks[2], gb[0]), (sinks[3], gb[0]),
                                   (sinks[6], gb[1]), (sinks[7], gb[1])])
-        if overlap:
-            _Side.pending.extend((dgates, x, out, scratch))
-        if use_sinks:
+            else:
+                grads = (gw_ih[0], g_hh[0], gb[0], gb[0].clone(), gw_ih[1], g_hh[1], gb[1], gb[1].clone())
+
+        if _wgrad(lstm_grouped, use_sinks and dtype == torch.bfloat16 and T > 1, (dgates, x, out), list(ctx.params),
+                  immediate=lstm_immediate):
+            # one launch for the layer (and the Linear layers recorded behind it); a data-parallel wrapper wants the
+            # gradients as they complete, and the next layer's recurrence is a latency chain that leaves the CUs idle anyway
+            _TnDefer.flush(final=False)
+        elif use_sinks:
             for p in ctx.params:
                 notify_grad_ready(p)
-            return (dx,) + (None,) * 8
-        return (dx, gw_ih[0], g_hh[0], gb[0], gb[0].clone(), gw_ih[1], g_hh[1], gb[1], gb[1].clone())
+        return (dx,) + grads
 
 
 def bilstm(x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r):

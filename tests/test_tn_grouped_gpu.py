@@ -205,6 +205,46 @@ def test_grouped_conv_wgrad_equals_float64(count):
         F._ROWTABS.clear()
 
 
+def test_flush_beside_and_concurrent_wgrad_on_a_second_stream():
+    """The two entry points for callers that drive two streams (include/megreader_hip.h): mr_tn_flush_beside launches the
+    recorded problems on a stream beside the one that recorded them, and build bit 1 of mr_conv2d_wgrad_tab keeps an immediate
+    launch off the shared split-reduction workspace.  Exact integers again: both must equal float64 arithmetic."""
+    lib = _lib.load()
+    old_p = _lib.set_tuning(tn_taps_min_p=1 << 30)      # keep every shape off the all-taps kernel
+    F._ROWTABS.clear()
+    try:
+        g = torch.Generator().manual_seed(211)
+        dense = [_dense_problem(g, P, NA, NB, lda=lda, perm_h=ph, colsum=cs) for (P, NA, NB, lda, ph, cs) in DENSE_SHAPES[:5]]
+        convs = [_conv_problem(g, *shape) for shape in CONV_SHAPES[:4]]
+        alone = _conv_problem(g, *CONV_SHAPES[4])
+        assert lib.mr_tn_pending() == 0
+        lib.mr_tn_defer(1)
+        for pr in dense:
+            _launch_dense(pr)
+        for pr in convs:
+            _launch_conv(pr, 1)                         # the row-table kernel runs at once, the GEMM is recorded
+        lib.mr_tn_defer(0)
+        assert lib.mr_tn_pending() == len(dense) + len(convs)
+        main = torch.cuda.current_stream()
+        side = torch.cuda.Stream()
+        side.wait_stream(main)                          # after the producers of the operands and the row tables
+        with torch.cuda.stream(side):
+            call("mr_tn_flush_beside")
+            _launch_conv(alone, 1 | 2)                  # immediate: table built, atomics only
+        assert lib.mr_tn_pending() == 0
+        main.wait_stream(side)
+        torch.cuda.synchronize()
+        for pr in dense:
+            _check_dense(pr)
+        for pr in convs + [alone]:
+            got = pr["gw"].cpu().double()
+            assert torch.equal(got, pr["ref"]), "dW: max |err| %g" % float((got - pr["ref"]).abs().max())
+            assert torch.equal(pr["gb"].cpu().double(), pr["b_ref"])
+    finally:
+        _lib.set_tuning(**old_p)
+        F._ROWTABS.clear()
+
+
 def _crnn_head(T, N, seed):
     from megreader_amd.decoders.crnn import BidirectionalLSTM
     torch.manual_seed(seed)
