@@ -432,8 +432,11 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   // hyper[6]: scale applied to the raw gradient (data parallel: 1 / world size folded into the update instead of a
   // separate pass over the flat gradient buffer after the all-reduce); 0 = unset = 1
   const float gs = hyper[6] != 0.f ? hyper[6] : 1.f;
-  const float bc1 = 1.f - powf(b1, step);
-  const float bc2 = 1.f - powf(b2, step);
+  // 1 - beta^t as -expm1(t * log(beta)): the plain difference 1 - powf(beta, t) cancels (beta2 = 0.999, t = 2: 9 of 24 bits gone,
+  // more with powf's own 2 ulp), which left the first steps up to 34x further from a float64 Adam than torch's float32 Adam is
+  // (tests/test_optim_gpu.py).  beta = 0: log = -inf, expm1 = -1, correction 1, as before.
+  const float bc1 = -expm1f(step * logf(b1));
+  const float bc2 = -expm1f(step * logf(b2));
   const float step_size = lr / bc1;
   const float inv_sqrt_bc2 = 1.f / sqrtf(bc2);
   const long long nv = n / 4;
@@ -735,6 +738,8 @@ int mr_adam_step(float* p, const float* g, float* m, float* v, long long n, floa
 }
 
 int mr_sgd_step(float* p, const float* g, float* buf, long long n, float* hyper, hipStream_t stream) {
+  MR_CHECK_ARG(((uintptr_t)p & 15) == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)buf & 15) == 0,
+               "mr_sgd_step: buffers must be 16-byte aligned");
   hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, stream, p, g, buf, n, (const float*)hyper);
   MR_CHECK_LAUNCH();
   return MR_OK;
