@@ -417,7 +417,11 @@ int mr_ctc_fwd(int dtype, const void* logits, int ldl, const void* targets, int 
                double* loss, double* log_probs_f64, hipStream_t stream);
 /* log_probs_f64 (nullable, f64 [T][N][C]): the same log-probabilities widened to float64 -- what the reference returns as
  * `pred` (decoders/crnn.py:96 `log_softmax(pred, dim=2).to(torch.float64)`), written by the same kernel.
- * mr_ctc_bwd writes the padding columns C .. ldg-1 of grad_logits as zeros.
+ * mr_ctc_bwd writes every element of grad_logits [T][N][ldg] exactly once, the padding columns C .. ldg-1 as zeros.
+ * C is not limited.  Up to the alphabet whose four float rows fit in 64 KB of LDS next to the 2S+1 states (S = 32: C <= 3 932) the
+ * per-sample kernels do the log-softmax themselves and the gradient kernel stages its rows in LDS; beyond it (mr_ctc_wide) a
+ * row-parallel log-softmax over all T*N rows runs in front of the recursions and the gradient kernel streams the classes from HBM,
+ * with nothing per class in LDS.  S is limited by the LDS of the recursion: (2S+1) * 36 + 16 <= 64 KB.
  * alpha, beta: f64 [N][T][2S+1] -- scratch that travels from mr_ctc_fwd to mr_ctc_bwd: the log-domain forward / backward
  * variables (mr_tuning.ctc_linear = 0, or an emission table beyond 64 KB of LDS) or, by default, their scaled linear-domain
  * counterparts (alpha rescaled per step by exact powers of two; beta without the emission of its own step).  beta may be null in mr_ctc_fwd when no gradient is wanted (the beta recursion runs
@@ -427,6 +431,8 @@ int mr_ctc_bwd(int dtype, const float* log_probs, const double* alpha, const dou
                const void* targets, int targets_i64, const void* input_lengths, const void* target_lengths,
                int lengths_i64, const double* grad_out, int T, int N, int C, int S, int blank, int zero_infinity,
                void* grad_logits, int ldg, hipStream_t stream);
+/* host only: 1 when mr_ctc_fwd / mr_ctc_bwd serve an alphabet of C classes and targets padded to S with the wide kernels */
+int mr_ctc_wide(int C, int S);
 
 /* ---- 2D-CTC (replaces the CUDA extension ops/ctc_2d: csrc/ctc2d.h:7-43, cuda/ctc2d_cuda_kernel.cu) -------------
  * log_probs [T,H,N,C] contiguous (`dtype`), targets [N,S] i64, lengths [N] i64.  Reference pybind signatures:
