@@ -666,6 +666,22 @@ int mr_decode_persist_bwd(const void* cat_wt, const void* ic_wt, long long ldict
                           const void* DHO_all, const float* ga, long long ldga, void* DGI_all, void* DHC_all, void* DCTX_all,
                           float* deproj, float* dv, void* denc, void* ws, long long ws_bytes, int S, int N, int T, int Ep,
                           hipStream_t stream);
+/* ... and the GREEDY form of the forward for inference (the eval loop of attention_decoder.py:84-118): the same kernel, compiled
+ * without the stores of the backward's buffers.  Step 0 is fed `start_word` for every row, step s + 1 the arg-max of step s's
+ * output layer out_w [C][H] / out_b (f32, nullable), 1 <= C <= 256, first index on ties; no idx, no flags.  h0 [N][H] is the
+ * initial state.  Writes pred[n * ldp + s] (int32, ldp >= S) for EVERY step s < S -- the last step's arg-max is one more
+ * best-class sweep behind the loop -- and, only when H_all is not null, H_all [S+1][N][H] ([0] = h0).  Rows of a batch group
+ * whose hand-off timed out get -1 in pred from that step on (status word as above).  ws / ws_bytes as mr_decode_persist_fwd
+ * (mr_decode_persist_ws_bytes(N)).  A bad shape is refused before any launch. */
+int mr_decode_greedy_ok(int dtype, int N, int T, int H, int Ep, int C);   /* host only: mr_decode_persist_ok and 1 <= C <= 256 */
+int mr_decode_greedy_fwd(const void* cat_w, const float* cat_b, const void* ic_w, long long ldic, const void* G, long long ldG,
+                         const void* out_w, const float* out_b, int C, const void* eproj, const void* enc, const float* v,
+                         const void* h0, int start_word, int* pred, long long ldp, void* H_all, void* ws, long long ws_bytes,
+                         int S, int N, int T, int Ep, hipStream_t stream);
+/* The reference's early stop, applied afterwards: pred int32 [N][ldp], S columns used.  With t* = the first column in which all N
+ * rows equal `blank`, every element of the columns > t* becomes `blank`; no such column: nothing changes.  (No step before t*
+ * depends on the break, so decoding all S steps and trimming gives the loop's tensor.)  One workgroup; any N. */
+int mr_decode_greedy_trim(int* pred, long long ldp, int N, int S, int blank, hipStream_t stream);
 
 /* ---- Round-4 decode-step fusions (csrc/gemm_skinny.hip): the element-wise GRU kernels in the epilogue of the M <= 32 GEMM next
  *      to them, the output layer + log-softmax + NLL + arg-max feedback as one kernel.  Same reference lines as above

@@ -227,7 +227,8 @@ struct DecP {
   const bf16_t* eproj;     // [N][T][H]
   const bf16_t* enc;       // [N][T][Ep]
   const float* v;          // [H]
-  bf16_t* H_all;           // [S+1][N][H]   ([0] is the initial state: read)
+  const bf16_t* h0;        // [N][H] initial state (the training form: H_all[0])
+  bf16_t* H_all;           // [S+1][N][H]   (greedy form: nullable, and [0] is written)
   bf16_t* HC_all;          // [S][N][4H]
   float* W_att;            // [S][N][T]
   bf16_t* CTX_all;         // [S][N][Ep]
@@ -237,6 +238,9 @@ struct DecP {
   int S, N, T, Ep, nbg;
   int xmap;                // block -> role map that puts a group's 32 slices on one XCD (decode_roles)
   unsigned hello_off;      // byte offset (from xch) of the XCC-id exchange
+  int* pred;               // greedy form: [N][ldp] int32, the arg-max of every step (-1: the row's group timed out)
+  long long ldp;
+  int start_word;          // greedy form: the word fed to step 0
 };
 
 // LDS carve-up (bytes), shared by the kernel and the launcher
@@ -259,7 +263,11 @@ struct Lds {
 
 }  // namespace
 
-template <int R>
+// GREEDY (inference, mr_decode_greedy_fwd): every step after the first is fed the arg-max of the step before, no idx / flags are
+// read, none of the backward's buffers is stored (H_all only when the caller passes one) and the arg-max of EVERY step goes to
+// pred: the last step's h' is published and gathered like any other, wave 3 scores it and one more best-class sweep -- with the
+// tag and slot of a step S -- ends the kernel (the "tail").
+template <int R, bool GREEDY = false>
 __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
   typedef Mma<bf16_t>::Frag Frag;
   typedef Xch<R> X;
@@ -305,7 +313,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
     const bf16_t* q = a.ic_w + (long long)((wave < 3 ? wave : 0) * DH + g * DU + l15) * a.ldic + lg * 8;
     // wave 3 has no W_ic tile: with arg-max feedback its fragments hold the slice's 8 rows of the output layer instead
     const int cls = g * 8 + l15;
-    const bool out_row = a.flags != nullptr && wave == 3 && l15 < 8 && cls < a.C;
+    const bool out_row = (GREEDY || a.flags != nullptr) && wave == 3 && l15 < 8 && cls < a.C;
     const bf16_t* qo = a.out_w + (long long)(out_row ? cls : 0) * DH + lg * 8;
 #pragma unroll
     for (int c = 0; c < 18; ++c) {
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
       wic[c] = *(const Frag*)&t;
     }
   }
-  const bool coin = a.flags != nullptr;
+  const bool coin = GREEDY || a.flags != nullptr;
   f32x4 obias = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};      // classes that do not exist never win
   if (coin && wave == 3 && lg < 2) {
 #pragma unroll
@@ -354,7 +362,10 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
   for (int i = tid; i < 16 * HLD / 8; i += 256) {
     const int r = i / (HLD / 8), c = (i - r * (HLD / 8)) * 8, rr = bg * R + r;
     uint4 h0 = make_uint4(0, 0, 0, 0);
-    if (r < R && rr < N && c < DH) h0 = *(const uint4*)(a.H_all + (long long)rr * DH + c);
+    if (r < R && rr < N && c < DH) {
+      h0 = *(const uint4*)(a.h0 + (long long)rr * DH + c);
+      if (GREEDY && a.H_all && g == 0) *(uint4*)(a.H_all + (long long)rr * DH + c) = h0;
+    }
     *(uint4*)(hbuf + r * HLD + c) = h0;
   }
   for (int i = tid; i < 16 * CLD / 8; i += 256) ((uint4*)sCtx)[i] = make_uint4(0, 0, 0, 0);
@@ -389,7 +400,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
   const bool row_g_ok = gru_thread && row_g < N;
   bool dead = false;
   // the word rows of the GRU's input gates, fetched one step ahead (idx -> row is a dependent pair of loads)
-  long long widx = row_g_ok ? a.idx[row_g] : 0;
+  long long widx = GREEDY ? (long long)a.start_word : (row_g_ok ? a.idx[row_g] : 0);
   unsigned short gw[3] = {0, 0, 0};       // raw bf16: converted where they are used, so the loads are waited for there
   if (row_g_ok) {
     const unsigned short* gp = (const unsigned short*)(a.G + widx * a.ldG + jg);
@@ -409,17 +420,20 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
   }
 
   int flag_prev = 1;             // flags[s - 1] while step s runs
-  for (int s = 0; s < S; ++s) {
+  for (int s = 0; s < (GREEDY ? S + 1 : S); ++s) {
     const unsigned tag = (unsigned)(s + 1);
     const unsigned slot = (unsigned)(s & 1);
+    const bool tail = GREEDY && s == S;      // greedy form: only the best-class sweep of the last step's output layer is left
     // arg-max feedback: is the word of THIS step the arg-max of the previous step's output layer?  (uniform)
     // (the coin of step s is fetched during step s: read here it was a global round trip at the top of every step)
-    const bool fed_argmax = coin && s > 0 && flag_prev == 0;
-    if (coin) flag_prev = a.flags[s];
-    if (coin) {
-      if (row_g_ok) widx = a.idx[(long long)s * N + row_g];                        // the given word (ignored on arg-max steps)
-    } else if (row_g_ok && s + 1 < S) {
-      widx = a.idx[(long long)(s + 1) * N + row_g];                                // used after the context hand-off
+    const bool fed_argmax = GREEDY ? s > 0 : (coin && s > 0 && flag_prev == 0);
+    if constexpr (!GREEDY) {
+      if (coin) flag_prev = a.flags[s];
+      if (coin) {
+        if (row_g_ok) widx = a.idx[(long long)s * N + row_g];                      // the given word (ignored on arg-max steps)
+      } else if (row_g_ok && s + 1 < S) {
+        widx = a.idx[(long long)(s + 1) * N + row_g];                              // used after the context hand-off
+      }
     }
     // ---- 1. stacked hidden projection of the slice's units: [16 rows] x [this wave's 16 columns of W_cat]
     {
@@ -455,12 +469,13 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
       const unsigned p01 = pack_bf16(acc[0] + cbias[0], acc[1] + cbias[1]);
       const unsigned p23 = pack_bf16(acc[2] + cbias[2], acc[3] + cbias[3]);
       *(f32x4*)(sHC + (wave * 16 + l15) * DU + lg * 4) = f32x4{bf16_lo(p01), bf16_hi(p01), bf16_lo(p23), bf16_hi(p23)};
-      if (row_f_ok) *(uint2*)(a.HC_all + ((long long)s * N + row_f) * 4 * DH + colbase) = make_uint2(p01, p23);
+      if constexpr (!GREEDY)
+        if (row_f_ok) *(uint2*)(a.HC_all + ((long long)s * N + row_f) * 4 * DH + colbase) = make_uint2(p01, p23);
     }
     lds_barrier();
     DEC_TICK(0)
     // ---- partial energies of (sample w + 4i, position lane) over the slice's 16 units -> the slices of that sample
-    {
+    if (!tail) {
       const unsigned xs = xg + X::XS_OFF + slot * X::XS_SLOT + (unsigned)(g * R * DT * 8);
 #pragma unroll
       for (int i = 0; i < R / 4; ++i) {
@@ -486,7 +501,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
       u32x4 pv[5];
       unsigned offS5[5] = {offS[0], offS[1], offS[2], offS[3], 0u};
       // arg-max steps: the 32 slices' best classes of every sample ride in the same sweep (thread <-> (sample, slice))
-      const unsigned wantS = 0xfu | ((fed_argmax && tid < R * DG) ? 0x10u : 0u);
+      const unsigned wantS = (tail ? 0u : 0xfu) | ((fed_argmax && tid < R * DG) ? 0x10u : 0u);
       offS5[4] = (wantS & 0x10u) ? (X::XL_OFF + slot * X::XL_SLOT + (unsigned)tid * 16u) - (X::XS_OFF + slot * X::XS_SLOT) : offS[0];
       pv[4] = u32x4{0u, 0u, 0u, 0u};
       if (!dead && !gather_pairs<5>(rx, offS5, xg + X::XS_OFF + slot * X::XS_SLOT, wantS, tag, pv)) {
@@ -516,13 +531,25 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
         const int c2 = __builtin_amdgcn_readlane(bc, 47), c3 = __builtin_amdgcn_readlane(bc, 63);
         const float va = hb ? v2 : v0, vb = hb ? v3 : v1;
         const int ca = hb ? c2 : c0, cb = hb ? c3 : c1;
-        const int word = (vb > va || (vb == va && cb < ca)) ? cb : ca;
+        const bool second = vb > va || (vb == va && cb < ca);
+        int word = second ? cb : ca;
+        if constexpr (GREEDY) {
+          // a timed-out hand-off (here, or a sibling's that poisoned h' with NaN: every logit is NaN then) ends the row's words
+          const float best = second ? vb : va;
+          if (dead || !(best == best)) word = -1;
+        } else if (dead) {
+          word = 0;
+        }
         if ((lane & 31) == 0) {
           const int r = tid >> 5;
-          sWord[r] = dead ? 0 : word;
-          if (g == 0 && bg * R + r < N) a.idx[(long long)s * N + bg * R + r] = dead ? 0 : word;
+          sWord[r] = word < 0 ? 0 : word;
+          if (g == 0 && bg * R + r < N) {
+            if constexpr (GREEDY) a.pred[(long long)(bg * R + r) * a.ldp + (s - 1)] = word;     // the word of step s - 1
+            else a.idx[(long long)s * N + bg * R + r] = word;
+          }
         }
       }
+      if (tail) break;
       float s0 = 0.f, s1 = 0.f;
       if (!dead) {
 #pragma unroll
@@ -548,7 +575,8 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
         const float ex = lane < T ? __builtin_amdgcn_exp2f((e - mx) * 1.4426950408889634f) : 0.f;
         const float sm = wave_sum_dpp(ex);
         const float w = ex * __builtin_amdgcn_rcpf(sm);
-        if (wave == 0 && cpart == 0 && lane < T && row_o_ok) a.W_att[((long long)s * N + row_o) * T + lane] = w;
+        if constexpr (!GREEDY)
+          if (wave == 0 && cpart == 0 && lane < T && row_o_ok) a.W_att[((long long)s * N + row_o) * T + lane] = w;
         // this thread's positions of the context sum: t = ctg, ctg + TG, ...  (every lane runs every iteration: a shuffle
         // reads 0 from a lane that is not executing)
         f32x4 cacc = {0.f, 0.f, 0.f, 0.f};
@@ -568,7 +596,8 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
         if (ctx_thread && ctg == 0) {
           const unsigned p01 = pack_bf16(cacc[0], cacc[1]), p23 = pack_bf16(cacc[2], cacc[3]);
           gran2_publish(rx, xg + X::XC_OFF + slot * X::XC_SLOT + (unsigned)((nloc * nu + u0 + cu) * 16), p01, p23, tag, local);
-          if (row_o_ok) *(uint2*)(a.CTX_all + ((long long)s * N + row_o) * Ep + (u0 + cu) * 4) = make_uint2(p01, p23);
+          if constexpr (!GREEDY)
+            if (row_o_ok) *(uint2*)(a.CTX_all + ((long long)s * N + row_o) * Ep + (u0 + cu) * 4) = make_uint2(p01, p23);
         }
       }
     }
@@ -612,9 +641,11 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
       const float hp = (float)hbuf[gm * HLD + jg];
       float hnew = (1.f - z) * nn_ + z * hp;
       if (sDead[0] | sDead[1] | sDead[2]) hnew = __builtin_nanf("");
-      if (row_g_ok) {
-        float* sv = a.SAVE_all + ((long long)s * N + row_g) * 3 * DH + jg;
-        sv[0] = r; sv[DH] = z; sv[2 * DH] = nn_;
+      if constexpr (!GREEDY) {
+        if (row_g_ok) {
+          float* sv = a.SAVE_all + ((long long)s * N + row_g) * 3 * DH + jg;
+          sv[0] = r; sv[DH] = z; sv[2 * DH] = nn_;
+        }
       }
       if (!row_g_ok) hnew = 0.f;
       if (!coin && row_g_ok && s + 1 < S) {        // the next step's word rows: a whole step to arrive
@@ -624,13 +655,14 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
       const float h1 = __shfl_down(hnew, 1, 64), h2 = __shfl_down(hnew, 2, 64), h3 = __shfl_down(hnew, 3, 64);
       if (!(gu & 3)) {
         const unsigned p01 = pack_bf16(hnew, h1), p23 = pack_bf16(h2, h3);
-        if (s + 1 < S)
+        if (GREEDY || s + 1 < S)            // (greedy form: the last h' too -- the tail scores it)
           gran2_publish(rx, xg + X::XH_OFF + slot * X::XH_SLOT + (unsigned)((gm * (DH / 4) + (jg >> 2)) * 16), p01, p23, tag, local);
-        if (row_g_ok) *(uint2*)(a.H_all + ((long long)(s + 1) * N + row_g) * DH + jg) = make_uint2(p01, p23);
+        if (row_g_ok && (!GREEDY || a.H_all != nullptr))
+          *(uint2*)(a.H_all + ((long long)(s + 1) * N + row_g) * DH + jg) = make_uint2(p01, p23);
       }
     }
     DEC_TICK(7)
-    if (s + 1 == S) break;
+    if (!GREEDY && s + 1 == S) break;
     // ---- 3. all-gather of h' -> LDS
     {
       u32x4 hv[X::CNT_H];
@@ -1165,6 +1197,36 @@ __global__ __launch_bounds__(256, 1) void decode_bwd_persist_kernel(DecB a) {
   }
 }
 
+// The reference's early stop applied after the fact (attention_decoder.py:84-118: pred starts as blank, the loop breaks once every
+// sample emitted blank at the same step): t* = the first column of pred [N][ldp] (S used) in which all N rows are `blank`;
+// everything in the columns > t* becomes `blank`.  ONE workgroup: wave w scans the columns w, w + 4, ... in rising order (lanes
+// over the rows) and stops at its first all-blank one.
+__global__ __launch_bounds__(256) void decode_trim_kernel(int* pred, long long ldp, int N, int S, int blank) {
+  __shared__ int tstar;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (tid == 0) tstar = S;
+  __syncthreads();
+  for (int c = wave; c < S; c += 4) {
+    bool other = false;
+    for (int n0 = 0; n0 < N && !other; n0 += 64) {
+      const int n = n0 + lane;
+      other = __any(n < N && pred[(long long)n * ldp + c] != blank);
+    }
+    if (!other) {
+      if (lane == 0) atomicMin(&tstar, c);
+      break;
+    }
+  }
+  __syncthreads();
+  const int first = tstar + 1;            // first column to overwrite
+  if (first >= S) return;
+  const int w = S - first;
+  for (long long i = tid; i < (long long)N * w; i += 256) {
+    const long long n = i / w;
+    pred[n * ldp + first + (int)(i - n * w)] = blank;
+  }
+}
+
 namespace {
 // rows per batch group: 4 while the grid (32 workgroups per group, ONE per CU: 460+ registers a lane) stays within the 256 CUs,
 // else 8.  The bytes a workgroup gathers per hand-off scale with the rows: before the XCD placement 4-row groups ran a step in
@@ -1181,10 +1243,11 @@ long long decode_ws_bytes(int N) {
   return (long long)cdiv(N, R) * decode_group_bytes(R) + HELLO_BYTES + 256;
 }
 
-template <int R>
+template <int R, bool GREEDY = false>
 int decode_launch(const DecP& a, hipStream_t stream) {
-  if (const int rc = ensure_dynamic_lds(decode_fwd_persist_kernel<R>, Lds<R>::bytes(DT, DEPMAX))) return rc;
-  hipLaunchKernelGGL(decode_fwd_persist_kernel<R>, dim3((a.xmap ? 8 : a.nbg) * DG), dim3(256), Lds<R>::bytes(a.T, a.Ep), stream, a);
+  if (const int rc = ensure_dynamic_lds(decode_fwd_persist_kernel<R, GREEDY>, Lds<R>::bytes(DT, DEPMAX))) return rc;
+  hipLaunchKernelGGL((decode_fwd_persist_kernel<R, GREEDY>), dim3((a.xmap ? 8 : a.nbg) * DG), dim3(256), Lds<R>::bytes(a.T, a.Ep),
+                     stream, a);
   MR_CHECK_LAUNCH();
   return MR_OK;
 }
@@ -1241,10 +1304,54 @@ int mr_decode_persist_fwd(const void* cat_w, const float* cat_b, const void* ic_
   }
   DecP a{(const bf16_t*)cat_w, cat_b, (const bf16_t*)ic_w, ldic, (const bf16_t*)G, ldG, idx, flags, (const bf16_t*)out_w, out_b, C,
          (const bf16_t*)eproj,
-         (const bf16_t*)enc, v, (bf16_t*)H_all, (bf16_t*)HC_all, W_att, (bf16_t*)CTX_all, SAVE_all, (u64*)ws,
+         (const bf16_t*)enc, v, (const bf16_t*)H_all, (bf16_t*)H_all, (bf16_t*)HC_all, W_att, (bf16_t*)CTX_all, SAVE_all, (u64*)ws,
          (unsigned*)((char*)ws + (long long)nbg * decode_group_bytes(R) + HELLO_BYTES), S, N, T, Ep, nbg, decode_xmap(nbg),
-         (unsigned)(nbg * decode_group_bytes(R))};
+         (unsigned)(nbg * decode_group_bytes(R)), nullptr, 0, 0};
   return R == 4 ? decode_launch<4>(a, stream) : decode_launch<8>(a, stream);
+}
+
+// host only: can the greedy form take this shape?  (what mr_decode_persist_ok asks, and an output layer of at most 8 classes a slice)
+int mr_decode_greedy_ok(int dtype, int N, int T, int H, int Ep, int C) {
+  return (C >= 1 && C <= 8 * DG && mr_decode_persist_ok(dtype, N, T, H, Ep)) ? 1 : 0;
+}
+
+// The greedy form of the loop (inference): step 0 is fed start_word, every later step the arg-max of the step before; pred[n * ldp + s]
+// = the arg-max of step s for all S steps; H_all [S+1][N][H] only when not null.  ws / ws_bytes as mr_decode_persist_fwd.
+int mr_decode_greedy_fwd(const void* cat_w, const float* cat_b, const void* ic_w, long long ldic, const void* G, long long ldG,
+                         const void* out_w, const float* out_b, int C, const void* eproj, const void* enc, const float* v,
+                         const void* h0, int start_word, int* pred, long long ldp, void* H_all, void* ws, long long ws_bytes,
+                         int S, int N, int T, int Ep, hipStream_t stream) {
+  const bool prezeroed = ws_bytes < 0;
+  if (prezeroed) ws_bytes = -ws_bytes;
+  MR_CHECK_ARG(S >= 1 && N >= 1 && N <= 64 && T >= 1 && T <= DT && Ep >= 8 && Ep <= DEPMAX && Ep % 8 == 0 && ldic >= Ep &&
+                   ldG >= 3 * DH && ldp >= S,
+               "mr_decode_greedy_fwd: bad shape S=%d N=%d T=%d Ep=%d", S, N, T, Ep);
+  MR_CHECK_ARG(out_w != nullptr && C >= 1 && C <= 8 * DG && start_word >= 0 && start_word < C,
+               "mr_decode_greedy_fwd: needs the output layer, 1 <= C <= 256 and a start word below C (C=%d, start_word=%d)", C,
+               start_word);
+  MR_CHECK_ARG(cat_w && ic_w && G && eproj && enc && v && h0 && pred && ws, "mr_decode_greedy_fwd: null argument (N=%d)", N);
+  MR_CHECK_ARG(ws_bytes >= decode_ws_bytes(N), "mr_decode_greedy_fwd: workspace too small (%lld < %lld)", ws_bytes,
+               decode_ws_bytes(N));
+  const int R = decode_rows(N), nbg = cdiv(N, R);
+  // every workgroup of the launch must be resident at once (mr_decode_greedy_ok says so beforehand; here it is an error)
+  MR_CHECK_ARG(nbg * DG <= device_cus(), "mr_decode_greedy_fwd: %d workgroups do not fit the device's CUs", nbg * DG);
+  if (!prezeroed && hipMemsetAsync(ws, 0, (size_t)decode_ws_bytes(N), stream) != hipSuccess) {
+    set_error("mr_decode_greedy_fwd: memset of the exchange buffer failed");
+    return MR_ERR_LAUNCH;
+  }
+  DecP a{(const bf16_t*)cat_w, cat_b, (const bf16_t*)ic_w, ldic, (const bf16_t*)G, ldG, nullptr, nullptr, (const bf16_t*)out_w, out_b,
+         C, (const bf16_t*)eproj, (const bf16_t*)enc, v, (const bf16_t*)h0, (bf16_t*)H_all, nullptr, nullptr, nullptr, nullptr,
+         (u64*)ws, (unsigned*)((char*)ws + (long long)nbg * decode_group_bytes(R) + HELLO_BYTES), S, N, T, Ep, nbg,
+         decode_xmap(nbg), (unsigned)(nbg * decode_group_bytes(R)), pred, ldp, start_word};
+  return R == 4 ? decode_launch<4, true>(a, stream) : decode_launch<8, true>(a, stream);
+}
+
+// pred [N][ldp] int32, S columns used: everything behind the first column in which all N rows are `blank` becomes `blank`
+int mr_decode_greedy_trim(int* pred, long long ldp, int N, int S, int blank, hipStream_t stream) {
+  MR_CHECK_ARG(pred != nullptr && N >= 1 && S >= 1 && ldp >= S, "mr_decode_greedy_trim: bad shape N=%d S=%d ldp=%lld", N, S, ldp);
+  hipLaunchKernelGGL(decode_trim_kernel, dim3(1), dim3(256), 0, stream, pred, ldp, N, S, blank);
+  MR_CHECK_LAUNCH();
+  return MR_OK;
 }
 
 // host only: the persistent BACKWARD of the loop (groups of 4 rows only: N <= 32)

@@ -13,10 +13,12 @@ Function (`_DecodeLoopFn`, round 3): per step forward
 embedding -> word_linear -> W_ih[:, :H] only depends on the class index, so it is a [classes, 3H] table computed once per
 forward; W_attn[:, :H] and W_hh share their input and are one stacked GEMM; every weight gradient is ONE transpose-read
 GEMM over all 32 steps after the loop (per-step inputs / output gradients live in [S, N, .] buffers that the step kernels
-write in place); the encoder-side attention gradient is one kernel after the loop.  Eval (greedy decode with early stop)
-keeps the per-step path:
+write in place); the encoder-side attention gradient is one kernel after the loop.  Eval (greedy decode with early stop) in
+bf16 is ONE persistent launch for all `max_size` steps (`_greedy_decode`: mr_decode_greedy_fwd, the greedy form of the training
+kernel, then mr_decode_greedy_trim for the reference's early stop) with no host synchronisation, so an eval forward can be
+captured into a graph; fp32, more than 256 classes, H != 512 or MEGREADER_DECODE_PERSIST=0 keep the per-step path:
   [GEMM word] -> [GEMM hproj] -> attn_step -> [GEMMs gi_w, gi_c, gh] -> gru_gates -> [GEMM out] -> nll_step
-with the GEMMs on the MFMA NT/TN kernels.  The reference's per-step Linear(1057 -> 512) over cat([hidden x T, enc])
+(a host sync per step for the early stop) with the GEMMs on the MFMA NT/TN kernels.  The reference's per-step Linear(1057 -> 512) over cat([hidden x T, enc])
 is split algebraically into hidden and encoder halves, so the encoder half (eproj) is one GEMM per sequence.
 Weights shared by the 32 steps are converted once per forward; their gradients (and those of eproj / enc / v)
 accumulate in f32 buffers across the steps and are handed to autograd by the step that runs backward last (step 0).
@@ -50,6 +52,9 @@ BATCHED_OUT = os.environ.get("MEGREADER_DECODE_BATCHED_OUT", "1") != "0"
 _PERSIST_ENV = os.environ.get("MEGREADER_DECODE_PERSIST", "1")       # "0" | "1" | "fwd" | "bwd"
 PERSIST = _PERSIST_ENV in ("1", "fwd")
 PERSIST_BWD = _PERSIST_ENV in ("1", "bwd")
+# the eval side: greedy decoding as one persistent launch (mr_decode_greedy_fwd) unless MEGREADER_DECODE_PERSIST=0
+PERSIST_EVAL = _PERSIST_ENV != "0"
+GREEDY_ROWS = 64            # rows of one launch of the decode kernel (mr_decode_persist_ok: N <= 64)
 
 
 def _persist_workspace(N, dev, backward=False):
@@ -68,6 +73,53 @@ def _persist_workspace(N, dev, backward=False):
     if F_.LSTM_STATUS is not None:
         F_.LSTM_STATUS.append(ws[nbytes - 256:nbytes - 252])
     return ws, size
+
+
+def _greedy_persist_ok(dtype, N, T, Hd, Ep, C):
+    """Does the eval decode of this shape run as one persistent launch per 64 rows?  (bf16, what mr_decode_greedy_ok asks, and
+    the MEGREADER_DECODE_PERSIST switch.)"""
+    return (PERSIST_EVAL and dtype == torch.bfloat16
+            and bool(load().mr_decode_greedy_ok(dtype_code(dtype), min(N, GREEDY_ROWS), T, Hd, Ep, C)))
+
+
+def _trim_pred(pred, blank):
+    """The reference's early stop after the fact (attention_decoder.py:84-118): everything behind the first step at which EVERY row
+    of the batch emitted `blank` is `blank`.  In place, one launch."""
+    call("mr_decode_greedy_trim", ptr(pred), pred.stride(0), pred.shape[0], pred.shape[1], int(blank))
+    return pred
+
+
+def _greedy_decode(enc, eproj, v, cat, ic, G, out, blank, max_size, trim=True):
+    """Greedy decoding of enc [N, T, Ep] / eproj [N, T, H] (bf16) as persistent launches: int32 [N, max_size].  cat / ic / out are
+    the `_SeqLinear` stacks of the training loop ([W_attn[:, :H]; W_hh], W_ih's context columns, the output layer), G the word table
+    [C, >= 3H].  Batches beyond 64 rows go as consecutive launches of at most 64 rows on the current stream, then ONE trim over
+    the whole batch.  Every launch zeroes its own exchange workspace (a memset node under capture; never the ZeroArena, which only
+    the fused optimizers' zero_grad() re-zeroes) and its status word joins nn.functional.LSTM_STATUS.  Nothing here waits for
+    the device."""
+    from ..nn import functional as F_
+    N, T, Ep = enc.shape
+    Hd = eproj.shape[2]
+    C = out.nout
+    dtype, dev = enc.dtype, enc.device
+    if not bool(load().mr_decode_greedy_ok(dtype_code(dtype), min(N, GREEDY_ROWS), T, Hd, Ep, C)):
+        raise RuntimeError("the persistent greedy decode does not take N=%d T=%d H=%d Ep=%d C=%d in %s"
+                           % (N, T, Hd, Ep, C, dtype))
+    assert cat.np_ == 4 * Hd and ic.np_ == 3 * Hd and ic.kp == Ep and out.kp == Hd
+    assert G.dtype == dtype and G.is_contiguous() and G.shape[0] >= C and G.shape[1] >= 3 * Hd
+    assert enc.is_contiguous() and eproj.is_contiguous() and eproj.dtype == dtype and eproj.shape[:2] == (N, T)
+    vf = v.detach().float().contiguous()
+    pred = torch.empty((N, max_size), dtype=torch.int32, device=dev)
+    h0 = torch.zeros((min(N, GREEDY_ROWS), Hd), dtype=dtype, device=dev)
+    for r0 in range(0, N, GREEDY_ROWS):
+        n = min(GREEDY_ROWS, N - r0)
+        nbytes = load().mr_decode_persist_ws_bytes(n)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        if F_.LSTM_STATUS is not None:
+            F_.LSTM_STATUS.append(ws[nbytes - 256:nbytes - 252])
+        call("mr_decode_greedy_fwd", ptr(cat.w_n), ptr(cat.bias_d), ptr(ic.w_n), Ep, ptr(G), G.shape[1], ptr(out.w_n),
+             ptr(out.bias_d), C, ptr(eproj[r0]), ptr(enc[r0]), ptr(vf), ptr(h0), int(blank), ptr(pred[r0]), max_size, 0, ptr(ws),
+             nbytes, max_size, n, T, Ep)
+    return _trim_pred(pred, blank) if trim else pred
 
 
 def _ceil_to(x, m):
@@ -624,7 +676,17 @@ class AttentionDecoder(nn.Module):
                                                                self.gt_as_output is not None and bool(self.gt_as_output)))
             return loss, att.view(N, -1, self.height, self.max_size)
 
-        # ---- eval: greedy decode, one step at a time (arg-max feedback, early stop when every sample emitted a blank)
+        # ---- eval: greedy decode (arg-max feedback, early stop when every sample emitted a blank).  bf16: all steps in ONE
+        # persistent launch per 64 rows and the early stop as a trim behind it -- no host synchronisation (_greedy_decode)
+        if _greedy_persist_ok(dtype, N, T, Hd, Ep, C):
+            with torch.no_grad():
+                rows = _EmbedRowsFn.apply(torch.arange(C, device=dev), cell.embedding.weight, Cp, dtype)
+                G = lin_iw(lin_word(rows))                      # the word table of the training branch
+                cat = _SeqLinear([Wa[:, :Hd], cell.rnn.weight_hh], [None, cell.rnn.bias_hh], Hd, dtype)
+                ic = _SeqLinear(cell.rnn.weight_ih[:, Hd:Hd + E], None, Ep, dtype)
+                out = _SeqLinear(cell.out.weight, cell.out.bias, Hd, dtype)
+                return _greedy_decode(enc, eproj, cell.attn.v, cat, ic, G, out, self.charset.blank, self.max_size)
+        # otherwise one step at a time
         lin_h = _SeqLinear(Wa[:, :Hd], None, Hd, dtype)
         lin_ic = _SeqLinear(cell.rnn.weight_ih[:, Hd:Hd + E], None, Ep, dtype)
         lin_hh = _SeqLinear(cell.rnn.weight_hh, cell.rnn.bias_hh, Hd, dtype)
