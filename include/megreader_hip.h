@@ -583,6 +583,27 @@ int mr_db_components(const float* prob, float thresh, int* labels, void* points,
                      hipStream_t stream);
 int mr_db_box_scores(const float* prob, const float* boxes, float* out, int B, int N, int H, int W, hipStream_t stream);
 
+/* ---- DB detector metrics (concern/icdar2015_eval/detection/iou.py:13-179 `evaluate_image` for quadrilaterals, the
+ * evaluator of structure/measurers/quad_measurer.py).  All arithmetic float64.  gt f64 [N][G][4][2] / det f64 [N][D][4][2]
+ * padded per image, gt_count / det_count i32 [N] = used slots.
+ * mr_quad_iou: gt_valid i32 [N][G], det_valid i32 [N][D] (1 = area non-zero and neither pair of opposite edges intersects
+ * or touches), gt_area / det_area f64 (absolute shoelace area), inter f64 [N][G][D] (area of the intersection, exact for
+ * convex and concave quads of either orientation), iou f64 [N][G][D] = inter / (gt_area + det_area - inter).  Every
+ * element is written; padding slots and pairs with an invalid member get 0.
+ * mr_quad_match: one image per wavefront; indices are positions in the compacted lists of VALID quads, original order.
+ * gt_ignore i32 [N][G]: a valid gt with ignore != 0 is don't-care; a valid det d is don't-care iff a don't-care gt g has
+ * inter[g][d] / det_area[d] > area_precision_constraint; going through g ascending and d ascending, (g, d) match iff both
+ * are unmatched, both care and iou[g][d] > iou_constraint (the reference's greedy order).  counts i32 [N][4] = (gtCare,
+ * detCare, detMatched, valid gts); scores f64 [N][3] = (precision, recall, hmean) by the reference's case analysis;
+ * match_det i32 [N][G] = det matched to gt g or -1 (-1 in unused slots); gt_dontcare i32 [N][G] / det_dontcare i32 [N][D]
+ * flags (0 in unused slots).  G and D up to 1024 each, MR_ERR_UNSUPPORTED beyond. */
+int mr_quad_iou(const double* gt, const int* gt_count, const double* det, const int* det_count, int N, int G, int D,
+                int* gt_valid, int* det_valid, double* gt_area, double* det_area, double* inter, double* iou,
+                hipStream_t stream);
+int mr_quad_match(const int* gt_valid, const int* det_valid, const int* gt_ignore, const double* det_area, const double* inter,
+                  const double* iou, int N, int G, int D, double iou_constraint, double area_precision_constraint, int* counts,
+                  double* scores, int* match_det, int* gt_dontcare, int* det_dontcare, hipStream_t stream);
+
 /* ---- Attention-GRU decoder step kernels (decoders/attention_decoder.py:146-231; the GEMMs use mr_gemm_nt/tn) ----- */
 int mr_attn_step_fwd(int dtype, const void* hproj, const void* eproj, const float* v, const void* enc, float* weights,
                      void* context, int N, int T, int Hd, int Ep, hipStream_t stream);

@@ -28,7 +28,7 @@ OVERRIDES = {
     # structure.measurers, ...]` + `class: CTCRepresenter` (concern/config.py:28-29,57-60), resolved with getattr
     "structure.representers": ("megreader_amd.structure", ["CTCRepresenter", "CTCRepresenter2D",
                                                            "SegDetectorRepresenter"]),
-    "structure.measurers": ("megreader_amd.structure", ["SequenceRecognitionMeasurer"]),
+    "structure.measurers": ("megreader_amd.structure", ["SequenceRecognitionMeasurer", "QuadMeasurer"]),
 }
 
 

@@ -1,6 +1,7 @@
 """GPU mirrors of the reference's evaluation-side structure classes (representers / measurers)."""
 from .representers import CTCRepresenter, CTCRepresenter2D  # noqa: F401,E402
 from .measurers import SequenceRecognitionMeasurer  # noqa: F401,E402
+from .quad_measurer import QuadMeasurer  # noqa: F401,E402
 from .seg_detector_representer import SegDetectorRepresenter  # noqa: F401,E402
 
 
