@@ -737,8 +737,12 @@ int mr_softmax_nc1t(int dtype, const void* logits, int ldl, float* out, int T, i
  *   with element strides; per column h* = argmax_h max_c(classify*mask), c* = argmax_c at h*; same collapse.
  * mr_seq_measure: structure/measurers/sequence_recognition_measurer.py:66-72,101-112 on id sequences (blank / unknown
  *   dropped as concern/charsets.py:60-62 does; fold: nullable id -> canonical id table for `.upper()`):
- *   acc[n] = sequences equal; ed[n] = Levenshtein distance (-1 if a sequence exceeds 63 symbols);
- *   score[n] (f64) = 0 if len(label) == 0 else 1 - min(len, ed) / len. */
+ *   acc[n] = sequences equal; ed[n] = Levenshtein distance; label_len[n] = symbols of the label;
+ *   score[n] (f64) = 0 if len(label) == 0 else 1 - min(len, ed) / len.  Every output is exact for any number of
+ *   symbols per row: rows with both sequences <= 63 symbols take one anti-diagonal pass in registers, longer rows a
+ *   row-by-row pass in LDS (same launch).  The LDS holds both sequences whole, so S and S2 above MR_SEQ_MEASURE_MAX
+ *   are refused with MR_ERR_ARG and nothing is written. */
+#define MR_SEQ_MEASURE_MAX 4096
 int mr_ctc_greedy_decode(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T,
                          int blank, int unknown, int* out, int* out_len, hipStream_t stream);
 int mr_ctc2d_greedy_decode(const float* classify, long long cn, long long cc, long long ch, long long cw,

@@ -105,13 +105,18 @@ __global__ __launch_bounds__(64) void ctc2d_greedy_decode_kernel(const float* cl
   if (lane == 0 && out_len) out_len[n] = count;
 }
 
-// Accuracy and normalised edit distance of id sequences.  One wave per sample; sequences (after dropping blank /
-// unknown ids) must be <= 63 symbols.  fold: optional id -> canonical id table (case folding: `.upper()`).
+// Accuracy and normalised edit distance of id sequences.  One wave per sample.  Both sequences are compacted (blank /
+// unknown ids dropped) into LDS in full: a_s[S], b_s[S2], row[S2] ints of dynamic LDS, which is what caps S and S2 at
+// MR_SEQ_MEASURE_MAX.  Rows whose two compacted lengths are <= 63 run the one-wave anti-diagonal Levenshtein; any longer
+// row takes the (wave-uniform) row-by-row branch below.  fold: optional id -> canonical id table (case folding: `.upper()`).
 __global__ __launch_bounds__(64) void seq_measure_kernel(const int* labels, int S, const int* preds, int S2, int N,
                                                          int blank, int unknown, const int* fold, int* acc, int* ed,
                                                          int* lab_len, double* score) {
   const int n = blockIdx.x, lane = threadIdx.x;
-  __shared__ int a_s[64], b_s[64];
+  extern __shared__ __attribute__((aligned(16))) int seq_lds[];
+  int* a_s = seq_lds;
+  int* b_s = a_s + S;
+  int* row = b_s + S2;
   // compact both sequences (concern/charsets.py:60-62 label_to_string drops blank and unknown)
   int la = 0, lb = 0;
   for (int pass = 0; pass < 2; ++pass) {
@@ -126,14 +131,58 @@ __global__ __launch_bounds__(64) void seq_measure_kernel(const int* labels, int 
       if (keep && fold) v = fold[v];
       const unsigned long long km = __ballot(keep);
       const int pos = cnt + __popcll(km & ((1ull << lane) - 1ull));
-      if (keep && pos < 64) dst[pos] = v;
+      if (keep) dst[pos] = v;   // pos < len: at most one symbol per source position
       cnt += __popcll(km);
     }
     if (pass == 0) la = cnt; else lb = cnt;
   }
   __syncthreads();
-  const bool too_long = la > 63 || lb > 63;
-  const int La = min(la, 63), Lb = min(lb, 63);
+  if (la > 63 || lb > 63) {   // wave-uniform
+    // accuracy: same length and every position equal
+    bool eq = la == lb;
+    if (eq)
+      for (int p = lane; p < la; p += 64) eq = eq && a_s[p] == b_s[p];
+    const bool same = __all(eq);
+    // Levenshtein row by row: row[j-1] holds D[i-1][j] entering row i and D[i][j] leaving it.  Column j = j0 + lane + 1
+    // stays on one lane for all rows, so a lane only ever reads back what it wrote itself.  With
+    // tmp[j] = min(D[i-1][j] + 1, D[i-1][j-1] + cost), the left dependence D[i][j] = min(tmp[j], D[i][j-1] + 1) unrolls
+    // to D[i][j] - j = min(D[i][0], min_{1<=k<=j} (tmp[k] - k)): an inclusive prefix-min over the lanes, carried from
+    // chunk to chunk in `run`.
+    const int BIG = 1 << 29;
+    for (int j = lane + 1; j <= lb; j += 64) row[j - 1] = j;   // D[0][j]
+    for (int i = 1; i <= la; ++i) {
+      const int ai = a_s[i - 1];
+      int diag = i - 1;   // D[i-1][j0]: the column left of this chunk, before row i overwrote it
+      int run = i;        // min over the columns left of this chunk of D[i][k] - k; column 0: D[i][0] = i
+      for (int j0 = 0; j0 < lb; j0 += 64) {
+        const int j = j0 + lane + 1;
+        const bool in = j <= lb;
+        const int up = in ? row[j - 1] : BIG;
+        int ul = __shfl_up(up, 1, 64);
+        if (lane == 0) ul = diag;
+        int t = in ? min(up + 1, ul + (ai != b_s[j - 1])) - j : BIG;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const int o = __shfl_up(t, off, 64);
+          if (lane >= off) t = min(t, o);
+        }
+        t = min(t, run);
+        if (in) row[j - 1] = t + j;
+        diag = __shfl(up, 63, 64);   // only read by a next chunk, which exists only if this one was full
+        run = __shfl(t, 63, 64);
+      }
+    }
+    __syncthreads();
+    if (lane == 0) {
+      const int result = lb == 0 ? la : row[lb - 1];
+      acc[n] = same ? 1 : 0;
+      ed[n] = result;
+      lab_len[n] = la;
+      score[n] = la == 0 ? 0.0 : (double)(1 - (double)min(la, result) * 1.0 / (double)la);
+    }
+    return;
+  }
+  const int La = la, Lb = lb;
   bool eq = la == lb;
   if (lane < La && lane < Lb) eq = eq && a_s[lane] == b_s[lane];
   const bool same = __all(eq);
@@ -163,7 +212,7 @@ __global__ __launch_bounds__(64) void seq_measure_kernel(const int* labels, int 
   result = __shfl(result, Lb, 64);
   if (lane == 0) {
     acc[n] = same ? 1 : 0;
-    ed[n] = too_long ? -1 : result;
+    ed[n] = result;
     lab_len[n] = la;
     // sequence_recognition_measurer.py:106-111 in the same IEEE double operations as the python expression
     score[n] = la == 0 ? 0.0 : (double)(1 - (double)min(la, result) * 1.0 / (double)la);
@@ -298,8 +347,11 @@ int mr_ctc2d_greedy_decode(const float* classify, long long cn, long long cc, lo
 int mr_seq_measure(const int* labels, int S, const int* preds, int S2, int N, int blank, int unknown, const int* fold,
                    int* acc, int* ed, int* label_len, double* score, hipStream_t stream) {
   MR_CHECK_ARG(N >= 0 && S > 0 && S2 > 0, "mr_seq_measure: bad shape N=%d S=%d S2=%d", N, S, S2);
+  MR_CHECK_ARG(S <= MR_SEQ_MEASURE_MAX && S2 <= MR_SEQ_MEASURE_MAX,
+               "mr_seq_measure: S=%d S2=%d exceed MR_SEQ_MEASURE_MAX=%d ids per row", S, S2, MR_SEQ_MEASURE_MAX);
   if (N == 0) return MR_OK;
-  hipLaunchKernelGGL(seq_measure_kernel, dim3(N), dim3(64), 0, stream, labels, S, preds, S2, N, blank, unknown, fold,
+  const size_t lds = ((size_t)S + 2 * (size_t)S2) * sizeof(int);   // a_s[S], b_s[S2], row[S2]: <= 48 KiB at the cap
+  hipLaunchKernelGGL(seq_measure_kernel, dim3(N), dim3(64), lds, stream, labels, S, preds, S2, N, blank, unknown, fold,
                      acc, ed, label_len, score);
   MR_CHECK_LAUNCH();
   return MR_OK;

@@ -31,20 +31,48 @@ class ImgDesc(ctypes.Structure):
                 ("dst_w", ctypes.c_int), ("scale_x", ctypes.c_double), ("scale_y", ctypes.c_double)]
 
 
+_FOLDS_TO = None
+
+
+def _folds_to():
+    """{string u: [codepoints cp with chr(cp).upper() == u != chr(cp)]} over all of Unicode (surrogates excluded: they
+    cannot be encoded as UTF-32 text).  One scan of the codepoints, about half a second, so once per process."""
+    global _FOLDS_TO
+    if _FOLDS_TO is None:
+        inv = {}
+        for cp in range(0x110000):
+            if 0xD800 <= cp <= 0xDFFF:
+                continue
+            ch = chr(cp)
+            up = ch.upper()
+            if up != ch:
+                inv.setdefault(up, []).append(cp)
+        _FOLDS_TO = inv
+    return _FOLDS_TO
+
+
 def charset_table(charset):
-    """Sorted (codepoint, id) arrays of a charset, case folding baked in (concern/charsets.py:37-41: `index()`
-    upper-cases the query unless case_sensitive).  Multi-codepoint / None entries (blank, unknown) are skipped."""
-    pairs = {}
+    """Sorted (codepoint, id) arrays of a charset: exactly the codepoints cp with charset.index(chr(cp)) != unknown, and
+    that id (concern/charsets.py:37-41).  Case sensitive: the single-character classes themselves.  Otherwise `index()`
+    upper-cases the query, so cp maps to the class chr(cp).upper() when that is a class -- a class that is not its own
+    upper case ('a' of EnglishPrintableCharset) is never a target and gets no entry under its own id.  None entries
+    (blank, unknown) are skipped, and so are multi-character ones unless they are the upper case of a codepoint ('SS' in
+    the alphabet ChineseCharset builds from a dictionary that holds 'ß')."""
+    classes = {}
     for i in range(len(charset)):
         ch = charset[i]
-        if not isinstance(ch, str) or len(ch) != 1:
-            continue
-        pairs.setdefault(ord(ch), i)
-    if not getattr(charset, "case_sensitive", False):
-        for cp, i in list(pairs.items()):
-            lo = chr(cp).lower()
-            if len(lo) == 1 and lo.upper() == chr(cp):
-                pairs.setdefault(ord(lo), i)
+        if isinstance(ch, str):
+            classes[ch] = i                     # as the charset's own lookup table: the last of equal entries
+    if getattr(charset, "case_sensitive", False):
+        pairs = {ord(ch): i for ch, i in classes.items() if len(ch) == 1}
+    else:
+        folds_to = _folds_to()
+        pairs = {}
+        for ch, i in classes.items():
+            if len(ch) == 1 and ch.upper() == ch:
+                pairs[ord(ch)] = i
+            for cp in folds_to.get(ch, ()):
+                pairs[cp] = i
     cps = sorted(pairs)
     return np.array(cps, dtype=np.int32), np.array([pairs[c] for c in cps], dtype=np.int32)
 

@@ -50,7 +50,9 @@ def ctc2d_greedy_decode(classify, mask, blank=0, unknown=1):
 
 def sequence_measure(labels, preds, blank=0, unknown=1, fold=None):
     """labels i32 [N, S], preds i32 [N, S2] (device).  Returns dict of device tensors:
-    accuracy (bool [N]), edit_distance (f64 [N], the reference's normalised score), distance (i32 [N]), label_length."""
+    accuracy (bool [N]), edit_distance (f64 [N], the reference's normalised score), distance (i32 [N], the Levenshtein
+    distance of the two id sequences without blank / unknown), label_length (i32 [N]).  All four are exact for any
+    number of symbols per row; S and S2 above MR_SEQ_MEASURE_MAX (4096, include/megreader_hip.h) raise."""
     require_cuda(labels, preds)
     labels = labels.to(torch.int32).contiguous()
     preds = preds.to(torch.int32).contiguous()
