@@ -12,14 +12,6 @@
 
 namespace mr {
 
-// tanh of the attention energies: 1 - 2 / (1 + 2^(x * 2/ln 2)) on the hardware exp2 / rcp units (absolute error ~2e-7; exact
-// limits +-1 at +-inf).  The library tanhf is ~40 VALU instructions and a decode step evaluates T*Hd = 32768 of them per sample
-// on ONE workgroup: round 6 measured attn_fwd2_kernel as bound by exactly that (prefetching every global load of the step
-// changed nothing; profiles/r06_attention_tanh.txt), so both directions share this form.
-__device__ __forceinline__ float att_tanh(float x) {
-  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * 2.885390081777927f));
-}
-
 // ---------------------------------------------------------------- attention step
 template <typename T>
 __global__ __launch_bounds__(256) void attn_step_fwd_kernel(const T* __restrict__ hproj, const T* __restrict__ eproj,

@@ -95,6 +95,15 @@ __device__ __forceinline__ f32x4 load4(const bf16_t* p) {
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return tanhf(x); }
 
+// tanh of the attention energies: 1 - 2 / (1 + 2^(x * 2/ln 2)) on the hardware exp2 / rcp units (absolute error ~2e-7; exact
+// limits +-1 at +-inf).  The library tanhf is ~40 VALU instructions and a decode step evaluates T*Hd = 32768 of them per sample
+// on ONE workgroup: round 6 measured attn_fwd2_kernel as bound by exactly that (prefetching every global load of the step
+// changed nothing; profiles/r06_attention_tanh.txt), so both directions share this form, and so do the
+// persistent decode kernels (decode_persist.hip).
+__device__ __forceinline__ float att_tanh(float x) {
+  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * 2.885390081777927f));
+}
+
 // Workgroup barrier that orders LDS traffic only: vector-memory loads / stores in flight STAY in flight (fences restricted to the
 // "local" address space compile to s_waitcnt lgkmcnt(0) + s_barrier).  __syncthreads() also waits for vmcnt(0) -- every outstanding
 // global access of the wave: on the per-step chain of the persistent kernels that put the HBM latency of prefetches and the write

@@ -27,15 +27,13 @@
 //   With arg-max feedback (flags[s] == 0: attention_decoder.py:107-110) wave 3 also scores the slice's 8 classes of the output
 //   layer on the h' it holds; the best (logit, class) of every (sample, slice) rides in the energies sweep of the next step.
 // The backward kernel (second half of the file) runs the steps in reverse with three reduce-scatters of f32 partial sums.
-// Protocol: lstm_persist.hip's -- a granule is one naturally aligned 8-byte {value, tag} written by one store and polled by sc1
-// (agent scope, L1-bypassing) loads; tag = step + 1, never 0; the exchange buffer is zeroed ahead of the launch; two slots
-// alternate (every hand-off is all-to-all inside the group, so no producer can run two steps ahead of a consumer).
-// Every spin is bounded: on timeout the workgroup records a code in the status word, stops waiting and POISONS h' with NaN.
+// Protocol, granule helpers, co-location check and workspace layout: persist_xch.h.  Two slots are enough here because every
+// hand-off is all-to-all inside the group, so no producer can run two steps ahead of a consumer; what a timeout poisons is h'.
 //
 // Results: the buffers the per-step path saves for the backward (H_all, HC_all, W_att, CTX_all, SAVE_all), rounded at the same
 // points (hproj / gh / context / h to bf16, the context part of the input gates kept in f32), so either backward can follow.
 #include "device.h"
-#include "igemm_core.h"
+#include "persist_xch.h"
 #include "../../include/megreader_hip.h"
 
 namespace mr {
@@ -49,12 +47,6 @@ constexpr int DT = 64;           // positions (max)
 constexpr int DEPMAX = 576;      // encoder channels (max, multiple of 32)
 constexpr int HLD = DH + 8;      // LDS row stride of h (elements): conflict-free 16-byte fragment reads
 constexpr int CLD = DEPMAX + 8;  // LDS row stride of the contexts
-constexpr unsigned SPIN_LIMIT = 1u << 21;
-constexpr unsigned TIMING_MAGIC = 0x54494D45u;
-
-typedef unsigned long long u64;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-constexpr int AUX_SC1 = 16;
 
 // exchange layout of one batch group of R rows (bytes)
 template <int R>
@@ -69,36 +61,11 @@ struct Xch {
   static constexpr int CNT_H = R * (DH / 4) / 256;               // ... of the hidden gather
 };
 
-__device__ __forceinline__ void gran2_store(rsrc_t r, unsigned byte_off, unsigned v0, unsigned v1, unsigned tag) {
-  __builtin_amdgcn_raw_buffer_store_b128(u32x4{v0, tag, v1, tag}, r, (int)byte_off, 0, AUX_SC1);
-}
-// `local` (uniform): all 32 slices of the batch group were found on ONE XCD (group_on_one_xcd below).  A plain store then KEEPS the
-// line in that XCD's L2 and the siblings' sc1 (L1-bypassing) polls hit it there; an sc1 store drops the line from L2 and every
-// poll pays the fabric round trip (MI355X_MICROARCH.md, "stores of each flavour"; lstm_persist.hip does the same with 4 slices).
-__device__ __forceinline__ void gran2_publish(rsrc_t r, unsigned byte_off, unsigned v0, unsigned v1, unsigned tag, bool local) {
-  if (local)
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{v0, tag, v1, tag}, r, (int)byte_off, 0, 0);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{v0, tag, v1, tag}, r, (int)byte_off, 0, AUX_SC1);
-}
-__device__ __forceinline__ u32x4 gran2_load(rsrc_t r, unsigned byte_off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, AUX_SC1);
-}
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const bf16_t x = (bf16_t)a, y = (bf16_t)b;
-  return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
-}
-__device__ __forceinline__ float bf16_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 __device__ __forceinline__ int wave_of_thread() { return (int)(threadIdx.x >> 6); }
 // sigmoid on the hardware exp2 / rcp units (the GRU cell sits on the chain: the library forms cost ~0.15 us per step; absolute
 // error ~2e-7, h is rounded to bf16 right after -- lstm_persist.hip does the same)
 __device__ __forceinline__ float dec_sigmoid(float x) {
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * -1.4426950408889634f));
-}
-// the energies' tanh: the form of attention.hip (att_tanh)
-__device__ __forceinline__ float dec_tanh(float x) {
-  return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * 2.885390081777927f));
 }
 
 // Cross-lane sums on the DPP path (one VALU op a level; __shfl_xor is a ds_bpermute round trip a level and the softmax of a step
@@ -136,34 +103,6 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
   return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 
-// Gather CNT 16-byte granule pairs (bit k of `want`: this thread needs pair k at byte offset base + off[k]; the other offsets must
-// still point into the workspace); a pair is accepted when both of its tags equal `tag`.  Every sweep issues ALL its loads before
-// it looks at any of them: with a load inside the per-pair branch the compiler put `s_waitcnt vmcnt(0)` behind each one (seen in
-// the ISA) and a 5-pair sweep paid five L2 round trips in a row.  The wave leaves together.  Returns false on timeout.
-template <int CNT>
-__device__ __forceinline__ bool gather_pairs(rsrc_t rx, const unsigned (&off)[CNT], unsigned base, unsigned want, unsigned tag,
-                                             u32x4 (&v)[CNT]) {
-  unsigned need = want;
-  for (unsigned spins = 0;; ++spins) {
-    u32x4 t[CNT];
-#pragma unroll
-    for (int k = 0; k < CNT; ++k) t[k] = gran2_load(rx, base + off[k]);
-    __builtin_amdgcn_sched_barrier(0);       // (the scheduler otherwise sinks the last load behind the first wait)
-#pragma unroll
-    for (int k = 0; k < CNT; ++k) {
-      if (((need >> k) & 1u) && t[k][1] == tag && t[k][3] == tag) {
-        v[k] = t[k];
-        need &= ~(1u << k);
-      }
-    }
-    if (__all(need == 0)) return true;
-    if (spins > SPIN_LIMIT) return false;
-    __builtin_amdgcn_s_sleep(1);
-  }
-}
-
-
-constexpr unsigned HELLO_TAG = 0x48454C4Fu;
 constexpr unsigned HELLO_BYTES = 8 * DG * 16;     // [8 groups][32 slices] granule pairs, between the exchange slots and the status
 
 // Workgroup -> (slice g, batch group bg).  xmap: the grid is 8 x 32 workgroups and hardware workgroup b is dispatched to XCD
@@ -179,36 +118,6 @@ __device__ __forceinline__ bool decode_roles(int xmap, int nbg, int& g, int& bg)
   g = b % DG;
   bg = b / DG;
   return true;
-}
-
-// Are the 32 slices of this batch group on one XCD?  The placement above is a dispatch-order ASSUMPTION, so it is verified: every
-// workgroup publishes its HW_REG_XCC_ID (sc1 store: visible anywhere) and reads its 31 siblings'.  Only if all agree does this
-// workgroup publish with plain stores.  A sibling that does not answer within the spin bound counts as "elsewhere" (sc1 stores
-// are always correct).  `sh` is one LDS word; status word 1 counts the workgroups that answered yes.
-__device__ __forceinline__ bool group_on_one_xcd(rsrc_t rx, unsigned hello_base, int g, int xmap, int* sh, unsigned* status) {
-  if (!xmap) return false;
-  unsigned me;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(me));
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid == 0) gran2_store(rx, hello_base + (unsigned)(g * 16), me, me, HELLO_TAG);
-  if (tid < 64) {
-    bool same = true;
-    if (lane < DG && lane != g) {
-      same = false;
-      for (unsigned spins = 0; spins < SPIN_LIMIT; ++spins) {
-        const u32x4 v = gran2_load(rx, hello_base + (unsigned)(lane * 16));
-        if (v[1] == HELLO_TAG) { same = v[0] == me; break; }
-        __builtin_amdgcn_s_sleep(2);
-      }
-    }
-    const bool all_same = __all(same);
-    if (lane == 0) {
-      *sh = all_same ? 1 : 0;
-      if (all_same) atomicAdd(status + 1, 1u);
-    }
-  }
-  __syncthreads();
-  return *sh != 0;
 }
 
 struct DecP {
@@ -373,7 +282,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
 
   const rsrc_t rx = make_rsrc(a.xch);
   const unsigned xg = (unsigned)bg * X::GROUP;
-  const bool local = group_on_one_xcd(rx, a.hello_off + (unsigned)(bg * DG * 16), g, a.xmap, &sDead[3], a.status);
+  const bool local = group_on_one_xcd<DG, SPIN_LIMIT>(rx, a.hello_off + (unsigned)(bg * DG * 16), g, a.xmap, &sDead[3], a.status);
   // per-thread constants of the gathers
   unsigned offC[X::CNT_C], ldsC[X::CNT_C], wantC = 0;      // contexts: R * nu pairs
 #pragma unroll
@@ -408,8 +317,8 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
   }
   __syncthreads();
   // phase clock (tools/microbench_decode.py): thread 0 of slices 0 and 1 of group 0 adds the 100 MHz wall clock spent in each
-  // phase of a step into status words [8 + 16 g + phase]; only when the caller set status word 2 (the product never does)
-  const bool timing = tid == 0 && bg == 0 && g < 2 && a.status[2] == TIMING_MAGIC;
+  // phase of a step into status words [PERSIST_ST_TICKS + 16 g + phase]; only when the caller set status word 2 (the product never does)
+  const bool timing = tid == 0 && bg == 0 && g < 2 && a.status[PERSIST_ST_TIMING] == TIMING_MAGIC;
   unsigned long long tprev = timing ? wall_clock64() : 0ull;
   unsigned tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define DEC_TICK(i)                                   \
@@ -486,8 +395,8 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
         float sc0 = 0.f, sc1 = 0.f;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          sc0 += vv[2 * q] * dec_tanh(hp[2 * q] + bf16_lo(ew[q]));
-          sc1 += vv[2 * q + 1] * dec_tanh(hp[2 * q + 1] + bf16_hi(ew[q]));
+          sc0 += vv[2 * q] * att_tanh(hp[2 * q] + bf16_lo(ew[q]));
+          sc1 += vv[2 * q + 1] * att_tanh(hp[2 * q + 1] + bf16_hi(ew[q]));
         }
         float sc = sc0 + sc1;
         if (lane >= T) sc = 0.f;
@@ -506,7 +415,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
       pv[4] = u32x4{0u, 0u, 0u, 0u};
       if (!dead && !gather_pairs<5>(rx, offS5, xg + X::XS_OFF + slot * X::XS_SLOT, wantS, tag, pv)) {
         dead = true;
-        if (lane == 0) { atomicMax(a.status, 1u); sDead[0] = 1; }
+        if (lane == 0) { atomicMax(a.status + PERSIST_ST_TIMEOUT, 1u); sDead[0] = 1; }
       }
       DEC_TICK(2)
       if (fed_argmax && tid < R * DG) {         // (whole waves: R * 32 threads)
@@ -607,7 +516,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
       u32x4 cv[X::CNT_C];
       if (!dead && !gather_pairs<X::CNT_C>(rx, offC, xg + X::XC_OFF + slot * X::XC_SLOT, wantC, tag, cv)) {
         dead = true;
-        if (lane == 0) { atomicMax(a.status, 2u); sDead[1] = 1; }
+        if (lane == 0) { atomicMax(a.status + PERSIST_ST_TIMEOUT, 2u); sDead[1] = 1; }
       }
       if (!dead) {
 #pragma unroll
@@ -637,7 +546,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
                   in_ = bf16_lo(gw[2]) + sGI[2 * 16 * DU + o];
       const float hr = sHC[16 * DU + o], hz = sHC[2 * 16 * DU + o], hn = sHC[3 * 16 * DU + o];
       const float r = dec_sigmoid(ir + hr), z = dec_sigmoid(iz + hz);
-      const float nn_ = dec_tanh(in_ + r * hn);
+      const float nn_ = att_tanh(in_ + r * hn);
       const float hp = (float)hbuf[gm * HLD + jg];
       float hnew = (1.f - z) * nn_ + z * hp;
       if (sDead[0] | sDead[1] | sDead[2]) hnew = __builtin_nanf("");
@@ -670,7 +579,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
           dead || gather_pairs<X::CNT_H>(rx, offH, xg + X::XH_OFF + slot * X::XH_SLOT, (1u << X::CNT_H) - 1u, tag, hv);
       if (!okh) {
         dead = true;
-        if (lane == 0) { atomicMax(a.status, 3u); sDead[2] = 1; }
+        if (lane == 0) { atomicMax(a.status + PERSIST_ST_TIMEOUT, 3u); sDead[2] = 1; }
       }
       lds_barrier();        // every GRU thread has read its h
       if (!dead) {
@@ -686,7 +595,7 @@ __global__ __launch_bounds__(256, 1) void decode_fwd_persist_kernel(DecP a) {
   }
   if (timing) {
 #pragma unroll
-    for (int i = 0; i < 10; ++i) a.status[8 + 16 * g + i] = tacc[i];
+    for (int i = 0; i < 10; ++i) a.status[PERSIST_ST_TICKS + 16 * g + i] = tacc[i];
   }
 #undef DEC_TICK
 }
@@ -858,7 +767,7 @@ __global__ __launch_bounds__(256, 1) void decode_bwd_persist_kernel(DecB a) {
 
   const rsrc_t rx = make_rsrc(a.xch);
   const unsigned xg = (unsigned)bg * X::GROUP;
-  const bool local = group_on_one_xcd(rx, a.hello_off + (unsigned)(bg * DG * 16), g, a.xmap, &sDead[3], a.status);
+  const bool local = group_on_one_xcd<DG, SPIN_LIMIT>(rx, a.hello_off + (unsigned)(bg * DG * 16), g, a.xmap, &sDead[3], a.status);
   // GRU ownership: thread <-> (sample gm, unit gu of the slice)
   const int gm = tid >> 4, gu = tid & 15, row_g = bg * R + gm, jg = g * DU + gu;
   const bool gru_thread = gm < R;
@@ -886,7 +795,7 @@ __global__ __launch_bounds__(256, 1) void decode_bwd_persist_kernel(DecB a) {
   bool dead = false;
   __syncthreads();
   // phase clock, as in the forward kernel
-  const bool timing = tid == 0 && bg == 0 && g < 2 && a.status[2] == TIMING_MAGIC;
+  const bool timing = tid == 0 && bg == 0 && g < 2 && a.status[PERSIST_ST_TIMING] == TIMING_MAGIC;
   unsigned long long tprev = timing ? wall_clock64() : 0ull;
   unsigned tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define DEC_TICK(i)                                   \
@@ -942,7 +851,7 @@ __global__ __launch_bounds__(256, 1) void decode_bwd_persist_kernel(DecB a) {
       u32x4 av[R];
       if (!dead && !gather_pairs<R>(rx, offA, xg + X::XA_OFF + (slot ^ 1u) * X::XA_SLOT, (1u << R) - 1u, tag - 1u, av)) {
         dead = true;
-        if (lane == 0) { atomicMax(a.status, 4u); sDead[0] = 1; }
+        if (lane == 0) { atomicMax(a.status + PERSIST_ST_TIMEOUT, 4u); sDead[0] = 1; }
       }
       float s0 = 0.f, s1 = 0.f;
       if (!dead) {
@@ -1022,7 +931,7 @@ __global__ __launch_bounds__(256, 1) void decode_bwd_persist_kernel(DecB a) {
       u32x4 dvv[X::CNT_D];
       if (!dead && !gather_pairs<X::CNT_D>(rx, offD, xg + X::XD_OFF + slot * X::XD_SLOT, wantD, tag, dvv)) {
         dead = true;
-        if (lane == 0) { atomicMax(a.status, 5u); sDead[1] = 1; }
+        if (lane == 0) { atomicMax(a.status + PERSIST_ST_TIMEOUT, 5u); sDead[1] = 1; }
       }
       DEC_TICK(3)
       float s0 = 0.f, s1 = 0.f;
@@ -1092,7 +1001,7 @@ __global__ __launch_bounds__(256, 1) void decode_bwd_persist_kernel(DecB a) {
           offW[i * (SPS / 2) + k] = (unsigned)((((wave + 4 * i) * SPS + half * (SPS / 2) + k) * DT + 2 * tp) * 8);
       if (!dead && !gather_pairs<NB>(rx, offW, xg + X::XW_OFF + slot * X::XW_SLOT, (1u << NB) - 1u, tag, wv)) {
         dead = true;
-        if (lane == 0) { atomicMax(a.status, 6u); sDead[2] = 1; }
+        if (lane == 0) { atomicMax(a.status + PERSIST_ST_TIMEOUT, 6u); sDead[2] = 1; }
       }
       DEC_TICK(6)
 #pragma unroll
@@ -1126,7 +1035,7 @@ __global__ __launch_bounds__(256, 1) void decode_bwd_persist_kernel(DecB a) {
         const f32x4 de4 = *(const f32x4*)(sDe + n * 64 + tc * 16 + j4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float th = dec_tanh(hp + evr[j4 + e]);
+          const float th = att_tanh(hp + evr[j4 + e]);
           const float gg = de4[e] * vq * (1.f - th * th);
           dacc[j4 + e] += gg;
           dvq += de4[e] * th;
@@ -1172,7 +1081,7 @@ __global__ __launch_bounds__(256, 1) void decode_bwd_persist_kernel(DecB a) {
   }
   if (timing) {
 #pragma unroll
-    for (int i = 0; i < 10; ++i) a.status[8 + 16 * g + i] = tacc[i];
+    for (int i = 0; i < 10; ++i) a.status[PERSIST_ST_TICKS + 16 * g + i] = tacc[i];
   }
 #undef DEC_TICK
   // ---- the accumulated gradients of eproj (own 16 columns) and v
@@ -1238,9 +1147,9 @@ int decode_rows(int N) { return N <= 32 ? 4 : 8; }
 // the XCD-colocating block map assumes the whole chip: 8 XCDs x 32 CUs.  decode_persist = 2: never use it (A/B knob)
 int decode_xmap(int nbg) { return (MR_TUNE(decode_persist) != 2 && nbg <= 8 && device_cus() == 8 * DG) ? 1 : 0; }
 unsigned decode_group_bytes(int R) { return R == 4 ? Xch<4>::GROUP : Xch<8>::GROUP; }
-long long decode_ws_bytes(int N) {
+long long decode_slot_bytes(int N) {
   const int R = decode_rows(N);
-  return (long long)cdiv(N, R) * decode_group_bytes(R) + HELLO_BYTES + 256;
+  return (long long)cdiv(N, R) * decode_group_bytes(R);
 }
 
 template <int R, bool GREEDY = false>
@@ -1252,9 +1161,9 @@ int decode_launch(const DecP& a, hipStream_t stream) {
   return MR_OK;
 }
 unsigned decode_bwd_group_bytes(int) { return XchB<4>::GROUP; }
-long long decode_bwd_ws_bytes(int N) {
+long long decode_bwd_slot_bytes(int N) {
   const int R = decode_rows(N);
-  return (long long)cdiv(N, R) * decode_bwd_group_bytes(R) + HELLO_BYTES + 256;
+  return (long long)cdiv(N, R) * decode_bwd_group_bytes(R);
 }
 
 template <int R>
@@ -1278,7 +1187,7 @@ int mr_decode_persist_ok(int dtype, int N, int T, int H, int Ep) {
   return cdiv(N, decode_rows(N)) * DG <= device_cus() ? 1 : 0;
 }
 
-long long mr_decode_persist_ws_bytes(int N) { return decode_ws_bytes(N); }
+long long mr_decode_persist_ws_bytes(int N) { return persist_ws_total(decode_slot_bytes(N), HELLO_BYTES); }
 
 // All S steps of the attention-GRU decode loop in one launch (see the file header).  idx [S][N] = the word fed to each step;
 // H_all[0] = the initial state.  flags null: every step is fed idx[s].  flags [S] (device): where flags[s] == 0, step s + 1 is fed
@@ -1288,25 +1197,19 @@ int mr_decode_persist_fwd(const void* cat_w, const float* cat_b, const void* ic_
                           long long* idx, const int* flags, const void* out_w, const float* out_b, int C, const void* eproj,
                           const void* enc, const float* v, void* H_all, void* HC_all, float* W_att, void* CTX_all,
                           float* SAVE_all, void* ws, long long ws_bytes, int S, int N, int T, int Ep, hipStream_t stream) {
-  const bool prezeroed = ws_bytes < 0;
-  if (prezeroed) ws_bytes = -ws_bytes;
   MR_CHECK_ARG(S >= 1 && N >= 1 && N <= 64 && T >= 1 && T <= DT && Ep >= 8 && Ep <= DEPMAX && Ep % 8 == 0 && ldic >= Ep &&
                    ldG >= 3 * DH,
                "mr_decode_persist_fwd: bad shape S=%d N=%d T=%d Ep=%d", S, N, T, Ep);
   MR_CHECK_ARG(flags == nullptr || (out_w != nullptr && C >= 1 && C <= 8 * DG),
                "mr_decode_persist_fwd: arg-max feedback needs the output layer and C <= 256 (C=%d)", C);
-  MR_CHECK_ARG(ws_bytes >= decode_ws_bytes(N), "mr_decode_persist_fwd: workspace too small (%lld < %lld)", ws_bytes,
-               decode_ws_bytes(N));
+  PersistWs w;
+  if (const int rc = persist_ws_prepare("mr_decode_persist_fwd", ws, ws_bytes, decode_slot_bytes(N), HELLO_BYTES, stream, &w))
+    return rc;
   const int R = decode_rows(N), nbg = cdiv(N, R);
-  if (!prezeroed && hipMemsetAsync(ws, 0, (size_t)decode_ws_bytes(N), stream) != hipSuccess) {
-    set_error("mr_decode_persist_fwd: memset of the exchange buffer failed");
-    return MR_ERR_LAUNCH;
-  }
   DecP a{(const bf16_t*)cat_w, cat_b, (const bf16_t*)ic_w, ldic, (const bf16_t*)G, ldG, idx, flags, (const bf16_t*)out_w, out_b, C,
          (const bf16_t*)eproj,
-         (const bf16_t*)enc, v, (const bf16_t*)H_all, (bf16_t*)H_all, (bf16_t*)HC_all, W_att, (bf16_t*)CTX_all, SAVE_all, (u64*)ws,
-         (unsigned*)((char*)ws + (long long)nbg * decode_group_bytes(R) + HELLO_BYTES), S, N, T, Ep, nbg, decode_xmap(nbg),
-         (unsigned)(nbg * decode_group_bytes(R)), nullptr, 0, 0};
+         (const bf16_t*)enc, v, (const bf16_t*)H_all, (bf16_t*)H_all, (bf16_t*)HC_all, W_att, (bf16_t*)CTX_all, SAVE_all, w.xch,
+         w.status, S, N, T, Ep, nbg, decode_xmap(nbg), w.hello_off, nullptr, 0, 0};
   return R == 4 ? decode_launch<4>(a, stream) : decode_launch<8>(a, stream);
 }
 
@@ -1321,8 +1224,6 @@ int mr_decode_greedy_fwd(const void* cat_w, const float* cat_b, const void* ic_w
                          const void* out_w, const float* out_b, int C, const void* eproj, const void* enc, const float* v,
                          const void* h0, int start_word, int* pred, long long ldp, void* H_all, void* ws, long long ws_bytes,
                          int S, int N, int T, int Ep, hipStream_t stream) {
-  const bool prezeroed = ws_bytes < 0;
-  if (prezeroed) ws_bytes = -ws_bytes;
   MR_CHECK_ARG(S >= 1 && N >= 1 && N <= 64 && T >= 1 && T <= DT && Ep >= 8 && Ep <= DEPMAX && Ep % 8 == 0 && ldic >= Ep &&
                    ldG >= 3 * DH && ldp >= S,
                "mr_decode_greedy_fwd: bad shape S=%d N=%d T=%d Ep=%d", S, N, T, Ep);
@@ -1330,19 +1231,15 @@ int mr_decode_greedy_fwd(const void* cat_w, const float* cat_b, const void* ic_w
                "mr_decode_greedy_fwd: needs the output layer, 1 <= C <= 256 and a start word below C (C=%d, start_word=%d)", C,
                start_word);
   MR_CHECK_ARG(cat_w && ic_w && G && eproj && enc && v && h0 && pred && ws, "mr_decode_greedy_fwd: null argument (N=%d)", N);
-  MR_CHECK_ARG(ws_bytes >= decode_ws_bytes(N), "mr_decode_greedy_fwd: workspace too small (%lld < %lld)", ws_bytes,
-               decode_ws_bytes(N));
   const int R = decode_rows(N), nbg = cdiv(N, R);
   // every workgroup of the launch must be resident at once (mr_decode_greedy_ok says so beforehand; here it is an error)
   MR_CHECK_ARG(nbg * DG <= device_cus(), "mr_decode_greedy_fwd: %d workgroups do not fit the device's CUs", nbg * DG);
-  if (!prezeroed && hipMemsetAsync(ws, 0, (size_t)decode_ws_bytes(N), stream) != hipSuccess) {
-    set_error("mr_decode_greedy_fwd: memset of the exchange buffer failed");
-    return MR_ERR_LAUNCH;
-  }
+  PersistWs w;
+  if (const int rc = persist_ws_prepare("mr_decode_greedy_fwd", ws, ws_bytes, decode_slot_bytes(N), HELLO_BYTES, stream, &w))
+    return rc;
   DecP a{(const bf16_t*)cat_w, cat_b, (const bf16_t*)ic_w, ldic, (const bf16_t*)G, ldG, nullptr, nullptr, (const bf16_t*)out_w, out_b,
          C, (const bf16_t*)eproj, (const bf16_t*)enc, v, (const bf16_t*)h0, (bf16_t*)H_all, nullptr, nullptr, nullptr, nullptr,
-         (u64*)ws, (unsigned*)((char*)ws + (long long)nbg * decode_group_bytes(R) + HELLO_BYTES), S, N, T, Ep, nbg,
-         decode_xmap(nbg), (unsigned)(nbg * decode_group_bytes(R)), pred, ldp, start_word};
+         w.xch, w.status, S, N, T, Ep, nbg, decode_xmap(nbg), w.hello_off, pred, ldp, start_word};
   return R == 4 ? decode_launch<4, true>(a, stream) : decode_launch<8, true>(a, stream);
 }
 
@@ -1359,7 +1256,7 @@ int mr_decode_persist_bwd_ok(int dtype, int N, int T, int H, int Ep) {
   return (N <= 32 && mr_decode_persist_ok(dtype, N, T, H, Ep)) ? 1 : 0;
 }
 
-long long mr_decode_persist_bwd_ws_bytes(int N) { return N <= 32 ? decode_bwd_ws_bytes(N) : 0; }
+long long mr_decode_persist_bwd_ws_bytes(int N) { return N <= 32 ? persist_ws_total(decode_bwd_slot_bytes(N), HELLO_BYTES) : 0; }
 
 // All S steps of the decode loop's backward (in reverse) in one launch -- what the per-step mr_gemm_gru_bwd / mr_gru_bwd2 +
 // mr_gemm_nt + mr_attn_bwd2 launches compute.  cat_wt [H][4H] and ic_wt [Ep][ldict >= 3H] are the TRANSPOSED weight images
@@ -1372,22 +1269,16 @@ int mr_decode_persist_bwd(const void* cat_wt, const void* ic_wt, long long ldict
                           const void* DHO_all, const float* ga, long long ldga, void* DGI_all, void* DHC_all, void* DCTX_all,
                           float* deproj, float* dv, void* denc, void* ws, long long ws_bytes, int S, int N, int T, int Ep,
                           hipStream_t stream) {
-  const bool prezeroed = ws_bytes < 0;
-  if (prezeroed) ws_bytes = -ws_bytes;
   MR_CHECK_ARG(S >= 1 && N >= 1 && N <= 32 && T >= 1 && T <= DT && Ep >= 8 && Ep <= DEPMAX && Ep % 8 == 0 && ldict >= 3 * DH,
                "mr_decode_persist_bwd: bad shape S=%d N=%d T=%d Ep=%d", S, N, T, Ep);
-  MR_CHECK_ARG(ws_bytes >= decode_bwd_ws_bytes(N), "mr_decode_persist_bwd: workspace too small (%lld < %lld)", ws_bytes,
-               decode_bwd_ws_bytes(N));
-  const int R = decode_rows(N), nbg = cdiv(N, R);
-  if (!prezeroed && hipMemsetAsync(ws, 0, (size_t)decode_bwd_ws_bytes(N), stream) != hipSuccess) {
-    set_error("mr_decode_persist_bwd: memset of the exchange buffer failed");
-    return MR_ERR_LAUNCH;
-  }
+  PersistWs w;
+  if (const int rc = persist_ws_prepare("mr_decode_persist_bwd", ws, ws_bytes, decode_bwd_slot_bytes(N), HELLO_BYTES, stream, &w))
+    return rc;
+  const int nbg = cdiv(N, decode_rows(N));
   DecB a{(const bf16_t*)cat_wt, (const bf16_t*)ic_wt, ldict, (const bf16_t*)eproj, (const bf16_t*)enc, v,
          (const bf16_t*)H_all, (const bf16_t*)HC_all, W_att, SAVE_all, (const bf16_t*)DHO_all, ga, ldga, (bf16_t*)DGI_all,
-         (bf16_t*)DHC_all, (bf16_t*)DCTX_all, deproj, dv, (bf16_t*)denc, (u64*)ws,
-         (unsigned*)((char*)ws + (long long)nbg * decode_bwd_group_bytes(R) + HELLO_BYTES), S, N, T, Ep, nbg, decode_xmap(nbg),
-         (unsigned)(nbg * decode_bwd_group_bytes(R))};
+         (bf16_t*)DHC_all, (bf16_t*)DCTX_all, deproj, dv, (bf16_t*)denc, w.xch, w.status, S, N, T, Ep, nbg, decode_xmap(nbg),
+         w.hello_off};
   return decode_bwd_launch<4>(a, stream);
 }
 

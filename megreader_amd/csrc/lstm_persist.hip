@@ -21,16 +21,8 @@
 //   Cell state c_t (forward) and the carried dc (backward) live in registers; cbuf / gates / out are written as the
 //   step kernels write them, so the weight-gradient GEMMs that follow are unchanged.
 //
-// Inter-workgroup protocol (MI355X_MICROARCH.md "Workgroup dispatch, XCD placement & inter-workgroup visibility",
-// cdna_hip_programming.md Guideline 16 form R2): granule = one naturally aligned 8-byte {value, tag} written by ONE
-// relaxed agent-scope atomic store (global_store_dwordx2 sc1) and read by relaxed agent-scope atomic loads
-// (global_load_dwordx2 sc1): placement-independent, no dependence on dispatch order beyond co-residency of the 4
-// members of a group.  tag = step + 1 (never 0); the exchange buffer is zeroed by a memset node ahead of every launch;
-// two slots alternate (a producer can run at most one step ahead of its slowest consumer).  Every spin is bounded:
-// on timeout the workgroup records a code in the status word, stops waiting (no hang) and POISONS its outputs with NaN, so
-// the failure reaches the loss / the gradients instead of silently corrupting a training run.
-#include "common.h"
-#include "igemm_core.h"
+// Inter-workgroup protocol, granule helpers, XCD co-location check and workspace layout: persist_xch.h.
+#include "persist_xch.h"
 #include "../../include/megreader_hip.h"
 
 namespace mr {
@@ -40,40 +32,12 @@ constexpr int PG = 4;          // slices (workgroups) per batch group
 constexpr int PR = 16;         // batch rows per group (one MFMA M tile)
 constexpr int PHS = PH / PG;   // hidden units per slice (64)
 constexpr int PLD = PH + 8;    // LDS row stride (elements): 16 rows x 16-byte fragment reads without bank conflicts
-constexpr unsigned SPIN_LIMIT = 1u << 21;
-
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) u64 gu64;
-typedef __attribute__((address_space(1))) unsigned gu32;
 
 constexpr int FWD_GRAN = PR * PH / 2;                 // granules per slot, forward  (bf16 pair per granule): 2048
 constexpr int BWD_GRAN_SLAB = PR * PHS;               // granules per (dest, src) slab, backward (one f32 each): 1024
 constexpr int BWD_GRAN = PG * (PG - 1) * BWD_GRAN_SLAB;  // per slot: 12288
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-constexpr int AUX_SC1 = 16;   // cache-policy bit of the raw buffer builtins: sc1 = agent scope (write-through / L1 bypass)
-
-// Two adjacent granules travel as ONE 16-byte sc1 access: {value0, tag, value1, tag}.  Each 8-byte half is a granule on
-// its own (carries its tag), so the pair needs no atomicity beyond the naturally aligned 8 bytes.
-__device__ __forceinline__ void gran2_store(rsrc_t r, unsigned byte_off, unsigned v0, unsigned v1, unsigned tag) {
-  __builtin_amdgcn_raw_buffer_store_b128(u32x4{v0, tag, v1, tag}, r, (int)byte_off, 0, AUX_SC1);
-}
-__device__ __forceinline__ u32x4 gran2_load(rsrc_t r, unsigned byte_off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, AUX_SC1);
-}
-// `local` (uniform): all four slices of the batch group were found on ONE XCD (xcd_colocated below).  A plain store
-// then KEEPS the line in that XCD's L2 and the siblings' sc1 (L1-bypassing) polls hit it there; an sc1 store drops
-// the line from L2 and every poll pays the fabric round trip (MI355X_MICROARCH.md, "stores of each flavour").
-__device__ __forceinline__ void gran2_publish(rsrc_t r, unsigned byte_off, unsigned v0, unsigned v1, unsigned tag,
-                                              bool local) {
-  if (local)
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{v0, tag, v1, tag}, r, (int)byte_off, 0, 0);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4{v0, tag, v1, tag}, r, (int)byte_off, 0, AUX_SC1);
-}
-
-constexpr unsigned HELLO_TAG = 0x48454C4Fu;
-constexpr unsigned HELLO_SPINS = 1u << 16;
+constexpr unsigned HELLO_SPINS = 1u << 16;   // spin bound of the co-location check (group_on_one_xcd<PG, HELLO_SPINS>)
 
 // Workgroup -> (slice g, batch group bg, direction).  xcd_map: hardware workgroup b is dispatched to XCD b % 8
 // (round-robin), so the four slices of a group take block indices that are congruent mod 8.
@@ -91,48 +55,11 @@ __device__ __forceinline__ void persist_roles(int xcd_map, int nbg, int& g, int&
   }
 }
 
-// Are the four slices of this batch group on one XCD?  The placement above is a dispatch-order ASSUMPTION, so it is
-// verified: every workgroup publishes its HW_REG_XCC_ID (sc1 store: visible anywhere) and reads its three siblings'.
-// Only if all four agree does this workgroup publish with plain stores.  A sibling that does not answer within the
-// spin bound counts as "elsewhere" (sc1 stores are always correct).  `sh` is one LDS word.
-__device__ __forceinline__ bool xcd_colocated(rsrc_t rx, unsigned hello_base, int g, int xcd_map, int* sh,
-                                              unsigned* status) {
-  if (!xcd_map) return false;
-  unsigned me;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(me));
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid == 0) gran2_store(rx, hello_base + (unsigned)(g * 16), me, me, HELLO_TAG);
-  if (tid < 64) {
-    bool same = true;
-    if (lane < PG - 1) {
-      const int gf = lane + (lane >= g);
-      same = false;
-      for (unsigned spins = 0; spins < HELLO_SPINS; ++spins) {
-        const u32x4 v = gran2_load(rx, hello_base + (unsigned)(gf * 16));
-        if (v[1] == HELLO_TAG) { same = v[0] == me; break; }
-        __builtin_amdgcn_s_sleep(2);
-      }
-    }
-    const bool all_same = __all(same);
-    if (lane == 0) {
-      *sh = all_same ? 1 : 0;
-      if (all_same) atomicAdd(status + 1, 1u);
-    }
-  }
-  __syncthreads();
-  return *sh != 0;
-}
-
 // Gate non-linearities on the dependency chain of the recurrence: v_exp_f32 + v_rcp_f32 forms (a few ulp; this path
 // only exists in bf16 compute mode, where h is rounded to 8 mantissa bits right after).  Saturate correctly:
 // exp -> inf gives rcp -> 0.
 __device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float ftanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const bf16_t x = (bf16_t)a, y = (bf16_t)b;
-  return (unsigned)__builtin_bit_cast(unsigned short, x) | ((unsigned)__builtin_bit_cast(unsigned short, y) << 16);
-}
 
 struct LstmPFwd {
   const bf16_t* xproj;  // [T*N, 8H]  (dir-major, gate-interleaved)
@@ -176,8 +103,8 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persist_kernel(LstmPFwd a) {
   }
   const rsrc_t rx = make_rsrc(a.xch);
   const unsigned xbase = (unsigned)(((long long)dir * a.nbg + bg) * 2 * FWD_GRAN * 8);   // bytes
-  const bool local = xcd_colocated(rx, a.hello_off + (unsigned)((dir * a.nbg + bg) * PG * 16), g, a.xcd_map, &local_sh,
-                                   a.status);
+  const bool local = group_on_one_xcd<PG, HELLO_SPINS>(rx, a.hello_off + (unsigned)((dir * a.nbg + bg) * PG * 16), g,
+                                                       a.xcd_map, &local_sh, a.status);
   const int u0 = wave * 16 + lg * 4;          // first of this lane's 4 units inside the slice
   const int j0 = g * PHS + u0;                // ... as a hidden-unit index
   float cst[4] = {0.f, 0.f, 0.f, 0.f};
@@ -190,8 +117,8 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persist_kernel(LstmPFwd a) {
   uint4 pend_g0 = make_uint4(0, 0, 0, 0), pend_g1 = pend_g0;
   long long pend_r = -1;
   // phase clock (tools/microbench_lstm.py --phases): thread 0 of workgroup 0 adds the 100 MHz wall clock spent in each phase of a
-  // step into status words [8 + phase]; only when the caller set status word 2 (the product never does)
-  const bool timing = tid == 0 && blockIdx.x == 0 && a.status[2] == 0x54494D45u;
+  // step into status words [PERSIST_ST_TICKS + phase]; only when the caller set status word 2 (the product never does)
+  const bool timing = tid == 0 && blockIdx.x == 0 && a.status[PERSIST_ST_TIMING] == TIMING_MAGIC;
   unsigned long long tprev = timing ? wall_clock64() : 0ull;
   unsigned tacc[4] = {0, 0, 0, 0};
 #define LSTM_TICK(i)                                  \
@@ -242,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persist_kernel(LstmPFwd a) {
           }
           if (__all(ok)) break;
           if (spins > SPIN_LIMIT) {
-            if (lane == 0) atomicMax(a.status, 1u);
+            if (lane == 0) atomicMax(a.status + PERSIST_ST_TIMEOUT, 1u);
             dead = true;
             break;
           }
@@ -333,7 +260,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_persist_kernel(LstmPFwd a) {
   }
   if (timing) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) a.status[8 + i] = tacc[i];
+    for (int i = 0; i < 4; ++i) a.status[PERSIST_ST_TICKS + i] = tacc[i];
   }
 #undef LSTM_TICK
 }
@@ -376,8 +303,8 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persist_kernel(LstmPBwd a) {
   }
   const rsrc_t rx = make_rsrc(a.xch);
   const unsigned xbase = (unsigned)(((long long)dir * a.nbg + bg) * 2 * BWD_GRAN * 8);   // bytes
-  const bool local = xcd_colocated(rx, a.hello_off + (unsigned)((dir * a.nbg + bg) * PG * 16), g, a.xcd_map, &local_sh,
-                                   a.status);
+  const bool local = group_on_one_xcd<PG, HELLO_SPINS>(rx, a.hello_off + (unsigned)((dir * a.nbg + bg) * PG * 16), g,
+                                                       a.xcd_map, &local_sh, a.status);
   // epilogue ownership: thread (wave i', lane) <-> row l15, local units u0..u0+3 of this slice
   const int u0 = wave * 16 + lg * 4;
   const int j0 = g * PHS + u0;               // global hidden unit of e = 0
@@ -408,8 +335,8 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persist_kernel(LstmPBwd a) {
     n_x1 = *(const uint4*)(gp1 + 8);
   };
   if (a.T > 0) fetch(0);
-  // phase clock, as in the forward kernel (status words [12 + phase])
-  const bool timing = tid == 0 && blockIdx.x == 0 && a.status[2] == 0x54494D45u;
+  // phase clock, as in the forward kernel (status words [PERSIST_ST_TICKS + 4 + phase])
+  const bool timing = tid == 0 && blockIdx.x == 0 && a.status[PERSIST_ST_TIMING] == TIMING_MAGIC;
   unsigned long long tprev = timing ? wall_clock64() : 0ull;
   unsigned tacc[4] = {0, 0, 0, 0};
 #define LSTM_TICK(i)                                  \
@@ -448,7 +375,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persist_kernel(LstmPBwd a) {
             }
           if (__all(ok)) break;
           if (spins > SPIN_LIMIT) {
-            if (lane == 0) atomicMax(a.status, 2u);
+            if (lane == 0) atomicMax(a.status + PERSIST_ST_TIMEOUT, 2u);
             dead = true;
             break;
           }
@@ -557,18 +484,17 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_persist_kernel(LstmPBwd a) {
   }
   if (timing) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) a.status[12 + i] = tacc[i];
+    for (int i = 0; i < 4; ++i) a.status[PERSIST_ST_TICKS + 4 + i] = tacc[i];
   }
 #undef LSTM_TICK
 }
 
-// layout: [granule slots][XCC-id exchange: 2*nbg groups x PG granule pairs of 16 B][status: 256 B, word 0 = timeout
-// code, word 1 = number of workgroups that found their group on one XCD]
+// workspace (persist_xch.h): the larger of the two passes' granule slots, then 2*nbg groups x PG granule pairs of XCC ids
 static long long persist_hello_bytes(int N) { return 2ll * cdiv(N, PR) * PG * 16; }
-static long long persist_ws_bytes(int N) {
+static long long persist_slot_bytes(int N) {
   const long long nbg = cdiv(N, PR);
   const long long fwd = 2 * nbg * 2 * FWD_GRAN * 8, bwd = 2 * nbg * 2 * (long long)BWD_GRAN * 8;
-  return (fwd > bwd ? fwd : bwd) + 256 + persist_hello_bytes(N);
+  return fwd > bwd ? fwd : bwd;
 }
 
 #define g_lstm_xcd (MR_TUNE(lstm_persist) != 2)   // lstm_persist = 2: never use the XCD-colocating block map (A/B knob)
@@ -582,18 +508,12 @@ bool lstm_persist_ok(int dtype, int T, int N, int H) {
 
 int lstm_fwd_persist(const void* xproj, const void* whh, void* out, float* cbuf, void* gates, int T, int N,
                      void* ws, long long ws_bytes, hipStream_t stream) {
-  const bool prezeroed = ws_bytes < 0;   // the caller zeroed it (see mr_lstm_fwd)
-  if (prezeroed) ws_bytes = -ws_bytes;
-  MR_CHECK_ARG(ws_bytes >= persist_ws_bytes(N), "mr_lstm_fwd: workspace too small (%lld < %lld)", ws_bytes,
-               persist_ws_bytes(N));
+  PersistWs w;   // (a negative ws_bytes: the caller zeroed it, see mr_lstm_fwd)
+  if (const int rc = persist_ws_prepare("mr_lstm_fwd", ws, ws_bytes, persist_slot_bytes(N), persist_hello_bytes(N), stream, &w))
+    return rc;
   const int nbg = cdiv(N, PR);
-  const long long xbytes = persist_ws_bytes(N) - 256 - persist_hello_bytes(N), hbytes = persist_hello_bytes(N);
-  if (!prezeroed && hipMemsetAsync(ws, 0, (size_t)persist_ws_bytes(N), stream) != hipSuccess) {
-    set_error("mr_lstm_fwd: memset of the exchange buffer failed");
-    return MR_ERR_LAUNCH;
-  }
-  LstmPFwd a{(const bf16_t*)xproj, (const bf16_t*)whh, (bf16_t*)out, cbuf, (bf16_t*)gates, (u64*)ws,
-             (unsigned*)((char*)ws + xbytes + hbytes), T, N, nbg, persist_xcd_map(nbg), (unsigned)xbytes};
+  LstmPFwd a{(const bf16_t*)xproj, (const bf16_t*)whh, (bf16_t*)out, cbuf, (bf16_t*)gates, w.xch, w.status, T, N, nbg,
+             persist_xcd_map(nbg), w.hello_off};
   hipLaunchKernelGGL(lstm_fwd_persist_kernel, dim3(2 * nbg * PG), dim3(256), 0, stream, a);
   MR_CHECK_LAUNCH();
   return MR_OK;
@@ -603,25 +523,19 @@ void lstm_set_bwd_debug(float*) {}   // debug hook retired with the fix of the b
 
 int lstm_bwd_persist(const void* dout, const void* whhT, const float* cbuf, void* gates, int T, int N, void* ws,
                      long long ws_bytes, hipStream_t stream) {
-  const bool prezeroed = ws_bytes < 0;   // the caller zeroed it (see mr_lstm_fwd)
-  if (prezeroed) ws_bytes = -ws_bytes;
-  MR_CHECK_ARG(ws_bytes >= persist_ws_bytes(N), "mr_lstm_bwd: workspace too small (%lld < %lld)", ws_bytes,
-               persist_ws_bytes(N));
+  PersistWs w;
+  if (const int rc = persist_ws_prepare("mr_lstm_bwd", ws, ws_bytes, persist_slot_bytes(N), persist_hello_bytes(N), stream, &w))
+    return rc;
   const int nbg = cdiv(N, PR);
-  const long long xbytes = persist_ws_bytes(N) - 256 - persist_hello_bytes(N), hbytes = persist_hello_bytes(N);
-  if (!prezeroed && hipMemsetAsync(ws, 0, (size_t)persist_ws_bytes(N), stream) != hipSuccess) {
-    set_error("mr_lstm_bwd: memset of the exchange buffer failed");
-    return MR_ERR_LAUNCH;
-  }
-  LstmPBwd a{(const bf16_t*)dout, (const bf16_t*)whhT, cbuf, (bf16_t*)gates, (u64*)ws,
-             (unsigned*)((char*)ws + xbytes + hbytes), T, N, nbg, persist_xcd_map(nbg), (unsigned)xbytes};
+  LstmPBwd a{(const bf16_t*)dout, (const bf16_t*)whhT, cbuf, (bf16_t*)gates, w.xch, w.status, T, N, nbg, persist_xcd_map(nbg),
+             w.hello_off};
   hipLaunchKernelGGL(lstm_bwd_persist_kernel, dim3(2 * nbg * PG), dim3(256), 0, stream, a);
   MR_CHECK_LAUNCH();
   return MR_OK;
 }
 
 long long lstm_persist_ws(int dtype, int T, int N, int H) {
-  return lstm_persist_ok(dtype, T, N, H) ? persist_ws_bytes(N) : 0;
+  return lstm_persist_ok(dtype, T, N, H) ? persist_ws_total(persist_slot_bytes(N), persist_hello_bytes(N)) : 0;
 }
 
 }  // namespace mr

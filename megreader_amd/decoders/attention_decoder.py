@@ -58,21 +58,10 @@ GREEDY_ROWS = 64            # rows of one launch of the decode kernel (mr_decode
 
 
 def _persist_workspace(N, dev, backward=False):
-    """(exchange buffer, size argument) of mr_decode_persist_fwd / _bwd: zero at launch -- from the pre-zeroed arena (size passed NEGATIVE)
-    or, when that is exhausted, from torch's allocator (the C call zeroes it).  The status word (last 256 bytes) joins the list
-    nn.functional.LSTM_STATUS collects for tests and bench.py."""
+    """nn.functional.persistent_workspace of mr_decode_persist_fwd / _bwd."""
     from ..nn import functional as F_
     nbytes = load().mr_decode_persist_bwd_ws_bytes(N) if backward else load().mr_decode_persist_ws_bytes(N)
-    size = nbytes
-    arena = F_.ZeroArena.take(dev, (nbytes + 7) // 8)
-    if arena is not None:
-        ws = arena.view(torch.uint8)[:nbytes]
-        size = -nbytes
-    else:
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    if F_.LSTM_STATUS is not None:
-        F_.LSTM_STATUS.append(ws[nbytes - 256:nbytes - 252])
-    return ws, size
+    return F_.persistent_workspace(nbytes, dev)
 
 
 def _greedy_persist_ok(dtype, N, T, Hd, Ep, C):
@@ -112,10 +101,7 @@ def _greedy_decode(enc, eproj, v, cat, ic, G, out, blank, max_size, trim=True):
     h0 = torch.zeros((min(N, GREEDY_ROWS), Hd), dtype=dtype, device=dev)
     for r0 in range(0, N, GREEDY_ROWS):
         n = min(GREEDY_ROWS, N - r0)
-        nbytes = load().mr_decode_persist_ws_bytes(n)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        if F_.LSTM_STATUS is not None:
-            F_.LSTM_STATUS.append(ws[nbytes - 256:nbytes - 252])
+        ws, nbytes = F_.persistent_workspace(load().mr_decode_persist_ws_bytes(n), dev, arena=False)
         call("mr_decode_greedy_fwd", ptr(cat.w_n), ptr(cat.bias_d), ptr(ic.w_n), Ep, ptr(G), G.shape[1], ptr(out.w_n),
              ptr(out.bias_d), C, ptr(eproj[r0]), ptr(enc[r0]), ptr(vf), ptr(h0), int(blank), ptr(pred[r0]), max_size, 0, ptr(ws),
              nbytes, max_size, n, T, Ep)

@@ -1279,30 +1279,42 @@ def conv_transpose2x2(x, weight, bias=None):
 # --------------------------------------------------------------------------------------------------
 # Bidirectional LSTM.  reference: nn.LSTM(nIn, nHidden, bidirectional=True) at decoders/crnn.py:13
 # --------------------------------------------------------------------------------------------------
-LSTM_STATUS = None   # tests set this to a list: status words of the persistent-recurrence workspaces handed out
+LSTM_STATUS = None   # tests set this to a list: status words of the persistent-kernel workspaces handed out
 LSTM_LOCAL = None    # ... and this one to a list of word 1 (workgroups that found their batch group on one XCD)
+
+# The status block of a persistent kernel's workspace: its last bytes, as 32-bit words (csrc/persist_xch.h)
+PERSIST_STATUS_BYTES = 256
+PERSIST_ST_TIMEOUT, PERSIST_ST_COLOCATED = 0, 1
+
+
+def persist_status_word(ws, word):
+    """The 4 bytes of status word `word` of the workspace `ws` (uint8, exactly as long as the library asked for)."""
+    o = ws.numel() - PERSIST_STATUS_BYTES + 4 * word
+    return ws[o:o + 4]
+
+
+def persistent_workspace(nbytes, dev, arena=True):
+    """(exchange buffer, size argument) of a persistent kernel (LSTM recurrence, attention decode loop).  The buffer has to be
+    zero at launch: it comes from the pre-zeroed arena (re-zeroed once per step by the fused optimizers' zero_grad; size passed
+    NEGATIVE = "already zeroed") or -- when the arena is exhausted, or with arena=False -- from torch's allocator (the C call then
+    zeroes it with its own memset node).  Its timeout word joins LSTM_STATUS, its co-location count LSTM_LOCAL."""
+    taken = ZeroArena.take(dev, (nbytes + 7) // 8) if arena else None
+    if taken is not None:
+        ws, size = taken.view(torch.uint8)[:nbytes], -nbytes
+    else:
+        ws, size = torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
+    if LSTM_STATUS is not None:
+        LSTM_STATUS.append(persist_status_word(ws, PERSIST_ST_TIMEOUT))
+    if LSTM_LOCAL is not None:
+        LSTM_LOCAL.append(persist_status_word(ws, PERSIST_ST_COLOCATED))
+    return ws, size
 
 
 def _lstm_workspace(dt, T, N, H, dev):
-    """(exchange buffer, size argument) of the persistent (one launch per layer and pass) recurrence, or (None, 0) when the
-    library runs one launch per step for this problem (mr_lstm_ws_bytes == 0).  The buffer has to be zero at launch: it comes
-    from the pre-zeroed arena (re-zeroed once per step by the fused optimizers' zero_grad; size passed NEGATIVE = "already
-    zeroed") or, when the arena is exhausted, from torch's allocator (the C call then zeroes it with its own memset node)."""
+    """persistent_workspace of the persistent (one launch per layer and pass) recurrence, or (None, 0) when the library runs
+    one launch per step for this problem (mr_lstm_ws_bytes == 0)."""
     nbytes = load().mr_lstm_ws_bytes(dt, T, N, H)
-    if nbytes <= 0:
-        return None, 0
-    size = nbytes
-    arena = ZeroArena.take(dev, (nbytes + 7) // 8)
-    if arena is not None:
-        ws = arena.view(torch.uint8)[:nbytes]
-        size = -nbytes
-    else:
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    if LSTM_STATUS is not None:
-        LSTM_STATUS.append(ws[nbytes - 256:nbytes - 252])
-    if LSTM_LOCAL is not None:
-        LSTM_LOCAL.append(ws[nbytes - 252:nbytes - 248])
-    return ws, size
+    return persistent_workspace(nbytes, dev) if nbytes > 0 else (None, 0)
 
 
 class BiLSTMFn(Function):

@@ -190,3 +190,22 @@ def test_decode_persist_host_queries_without_a_gpu():
     if not torch.cuda.is_available():
         assert lib.mr_decode_persist_ok(_lib.dtype_code(torch.bfloat16), 16, 64, 512, 552) == 0
         assert lib.mr_decode_persist_bwd_ok(_lib.dtype_code(torch.bfloat16), 16, 64, 512, 552) == 0
+
+
+def test_persistent_workspace_sizes_are_pinned():
+    """The workspace of the persistent kernels is [granule slots][XCC-id exchange][256 status bytes] (csrc/persist_xch.h); callers
+    size their buffers by these three queries and find the status block at the end, so the values are part of the ABI.  The
+    literals were read from a build of the commit BEFORE the layout moved into one helper, not from the code under test."""
+    lib = _lib.load()
+    lstm = {1: 393600, 4: 393600, 5: 393600, 16: 393600, 17: 786944, 32: 786944, 33: 1180288, 64: 1573632, 250: 6293760,
+            256: 6293760}
+    fwd = {1: 174336, 4: 174336, 5: 344320, 16: 684288, 17: 854272, 32: 1364224, 33: 1704192, 64: 2724096}
+    bwd = {1: 2265344, 4: 2265344, 5: 4526336, 16: 9048320, 17: 11309312, 32: 18092288, 33: 0, 64: 0}   # 0 above 32 rows
+    for n, want in lstm.items():
+        assert lib.mr_lstm_ws_bytes(1, 33, n, 256) == want, n
+        assert lib.mr_lstm_ws_bytes(1, 2, n, 256) == want, n            # the size does not depend on T
+        assert lib.mr_lstm_ws_bytes(0, 33, n, 256) == 0, n              # f32: one launch per step, no workspace
+    for n, want in fwd.items():
+        assert lib.mr_decode_persist_ws_bytes(n) == want, n
+    for n, want in bwd.items():
+        assert lib.mr_decode_persist_bwd_ws_bytes(n) == want, n

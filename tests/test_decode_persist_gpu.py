@@ -13,6 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from megreader_amd._lib import call, dtype_code, load, ptr  # noqa: E402
+from megreader_amd.nn.functional import PERSIST_ST_COLOCATED, persist_status_word  # noqa: E402
 
 DEV = "cuda"
 H = 512
@@ -58,7 +59,7 @@ def _per_step(d, N, T, Ep, S):
     return b
 
 
-def _persistent(d, N, T, Ep, S, prezero):
+def _persistent(d, N, T, Ep, S, prezero, colocated=None):
     b = _buffers(N, T, Ep, S, d["h0"])
     nbytes = load().mr_decode_persist_ws_bytes(N)
     ws = torch.zeros((nbytes,), dtype=torch.uint8, device=DEV) if prezero else \
@@ -68,6 +69,8 @@ def _persistent(d, N, T, Ep, S, prezero):
          ptr(b["CTX_all"]), ptr(b["SAVE_all"]), ptr(ws), -nbytes if prezero else nbytes, S, N, T, Ep)
     torch.cuda.synchronize()
     status = int(ws[nbytes - 256:nbytes - 252].view(torch.int32).item())
+    if colocated is not None:
+        colocated.append(int(persist_status_word(ws, PERSIST_ST_COLOCATED).view(torch.int32).item()))
     return b, status
 
 
@@ -199,7 +202,7 @@ def _bwd_per_step(d, fw, x, N, T, Ep, S):
     return b
 
 
-def _bwd_persistent(d, fw, x, N, T, Ep, S, prezero=True):
+def _bwd_persistent(d, fw, x, N, T, Ep, S, prezero=True, colocated=None):
     b = _bwd_buffers(N, T, Ep, S)
     b["deproj"].fill_(float("nan"))                 # written, not accumulated
     nbytes = load().mr_decode_persist_bwd_ws_bytes(N)
@@ -212,6 +215,8 @@ def _bwd_persistent(d, fw, x, N, T, Ep, S, prezero=True):
          ptr(b["denc"]), ptr(ws), -nbytes if prezero else nbytes, S, N, T, Ep)
     torch.cuda.synchronize()
     status = int(ws[nbytes - 256:nbytes - 252].view(torch.int32).item())
+    if colocated is not None:
+        colocated.append(int(persist_status_word(ws, PERSIST_ST_COLOCATED).view(torch.int32).item()))
     return b, status
 
 
@@ -301,6 +306,37 @@ def test_persistent_decode_backward_repeatable():
         assert torch.equal(a[k], b[k]), k
     assert float((a["dv"] - b["dv"]).abs().max()) <= 1e-5 * float(b["dv"].abs().max())     # atomics: order of the four waves
     assert load().mr_decode_persist_bwd_ok(dtype_code(torch.bfloat16), 33, T, H, Ep) == 0
+
+
+def test_persistent_decode_colocation_count():
+    """Status word 1 of both decode kernels: how many workgroups found their batch group on one XCD and so publish with plain
+    stores (csrc/persist_xch.h: group_on_one_xcd).  One group of 4 rows = the 32 workgroups that reach the check (the block map
+    starts 8 x 32; the other 224 leave at once).  With the map off (decode_persist = 2) nobody may answer yes; with it on the
+    count is a dispatch property (no particular value is demanded) bounded by those 32; the two runs must agree bit for bit
+    (dv is added with float atomics by the four waves of a workgroup: left out)."""
+    from megreader_amd._lib import set_tuning
+    N, T, Ep, S, C = 4, 4, 8, 2, 5
+    d = _inputs(N, T, Ep, S, C, seed=29)
+    fw = _per_step(d, N, T, Ep, S)
+    x = _bwd_inputs(d, fw, N, T, Ep, S, seed=4, with_ga=True)
+    runs = {}
+    try:
+        for knob in (1, 2):
+            set_tuning(decode_persist=knob)
+            count = []
+            f, sf = _persistent(d, N, T, Ep, S, True, colocated=count)
+            b, sb = _bwd_persistent(d, fw, x, N, T, Ep, S, True, colocated=count)
+            runs[knob] = (f, b, (sf, sb), count)
+    finally:
+        set_tuning(decode_persist=1)
+    print("workgroups on one XCD (forward, backward) of 32: map on %s, map off %s" % (runs[1][3], runs[2][3]))
+    assert runs[1][2] == (0, 0) and runs[2][2] == (0, 0), "a hand-off timed out"
+    assert runs[2][3] == [0, 0]
+    assert all(0 <= c <= 32 for c in runs[1][3])
+    for k in ("H_all", "HC_all", "W_att", "CTX_all", "SAVE_all"):
+        assert torch.equal(runs[1][0][k], runs[2][0][k]), k
+    for k in ("DGI", "DHC", "DCTX", "deproj", "denc"):
+        assert torch.equal(runs[1][1][k], runs[2][1][k]), k
 
 
 # ------------------------------------------------------------------------------------------------------- arg-max feedback

@@ -482,6 +482,50 @@ def test_bilstm_persistent_recurrence(T, N, I):
         assert _rel_err(a, getattr(ref, n_).grad) < 4e-2, n_
 
 
+def test_bilstm_persistent_colocation_count():
+    """Status word 1 of the persistent recurrence: how many workgroups found their batch group on one XCD and so publish with
+    plain stores (csrc/persist_xch.h: group_on_one_xcd).  T = 2, N = 64: four batch groups, so the XCD block map is on, 32
+    workgroups per launch, one exchange.  With the map off (lstm_persist = 2) nobody may answer yes; with it on the count is a
+    dispatch property (no particular value is demanded) bounded by the grid; the two runs must agree bit for bit (y and dx:
+    what the two kernels and the deterministic GEMMs behind them produce; the weight gradients add with float atomics)."""
+    from megreader_amd._lib import load
+    from megreader_amd.nn import functional as Fn
+    T, N, I, H = 2, 64, 64, 256
+    dtype = torch.bfloat16
+    mr.set_compute_dtype(dtype)
+    lib = load()
+    torch.manual_seed(5)
+    ref = torch.nn.LSTM(I, H, bidirectional=True)
+    names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0", "weight_ih_l0_reverse",
+             "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse")
+    x = torch.randn(T, N, I).to(dtype)
+    gy = torch.randn(T, N, 2 * H).to(dtype)
+    grid = 2 * (N // 16) * 4
+
+    def run(persist):
+        lib.mr_set_lstm_persist(persist)
+        Fn.LSTM_STATUS, Fn.LSTM_LOCAL = [], []
+        params = [getattr(ref, n_).detach().float().to(DEV).requires_grad_(True) for n_ in names]
+        xd = x.to(DEV).requires_grad_(True)
+        y = F.bilstm(xd, *params)
+        y.backward(gy.to(DEV))
+        torch.cuda.synchronize()
+        words = [[int(w.view(torch.int32).item()) for w in lst] for lst in (Fn.LSTM_STATUS, Fn.LSTM_LOCAL)]
+        return y.detach().cpu(), xd.grad.cpu(), words[0], words[1]
+
+    try:
+        y1, dx1, timeout1, local1 = run(1)
+        y2, dx2, timeout2, local2 = run(2)
+    finally:
+        Fn.LSTM_STATUS = Fn.LSTM_LOCAL = None
+        lib.mr_set_lstm_persist(1)
+    print("workgroups on one XCD (forward, backward) of %d: map on %s, map off %s" % (grid, local1, local2))
+    assert timeout1 == [0, 0] and timeout2 == [0, 0], "a bounded spin timed out"
+    assert local2 == [0, 0]
+    assert len(local1) == 2 and all(0 <= c <= grid for c in local1)
+    assert torch.equal(y1, y2) and torch.equal(dx1, dx2)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_ctc_matches_torch_and_oracle(dtype):
     from oracle.ctc import ctc_1d
