@@ -604,6 +604,29 @@ int mr_quad_match(const int* gt_valid, const int* det_valid, const int* gt_ignor
                   const double* iou, int N, int G, int D, double iou_constraint, double area_precision_constraint, int* counts,
                   double* scores, int* match_det, int* gt_dontcare, int* det_dontcare, hipStream_t stream);
 
+/* ---- DB detector training targets (data/processes/make_seg_detection_data.py:21-99 `MakeSegDetectionData` and
+ * data/processes/make_border_map.py:24-120 `MakeBorderMap` for quadrilaterals; the batch of decoders/seg_detector_loss.py).
+ * All geometry float64, pixel (x, y) = the integer point (x, y).  polys f64 [N][G][4][2] padded per image, count i32 [N] =
+ * used slots, ignore_in i32 [N][G] = the labels' ignore tags.
+ * Per used slot: clip to [0, W-1] x [0, H-1]; a = `polygon_area`; points reordered (0, 3, 2, 1) if a > 0; ignored if
+ * ignore_in, |a| < 1, min(height, width) < min_text_size, or no pixel is inside the polygon (even-odd) at squared distance
+ * >= D^2 from its boundary, D = |a| (1 - shrink_ratio^2) / perimeter (the restatement of `shrinked == []`).
+ * records: scratch of N * G * mr_sizeof_db_record() bytes (the prep kernel's per-slot result; may be NULL when G == 0).
+ * ignore_out i32 [N][G]: the final flags (0 in unused slots); dist f64 [N][G]: D of a kept polygon, else 0.
+ * gt f32 [N][1][H][W]: 1 inside a kept polygon at d^2 >= D^2; mask f32 [N][H][W]: 0 inside, or within half a pixel of an
+ * edge of, an ignored polygon's truncated points, else 1; thresh_mask f32 [N][H][W]: 1 inside a kept polygon or at d^2 <= D^2;
+ * thresh_map f32 [N][H][W] = c * (float)(thresh_max - thresh_min) + (float)thresh_min, c = max(0, max_k 1 - min(1, e_k / D_k))
+ * over the kept polygons whose box [rnd(min - D), rnd(max + D)] holds the pixel, e_k = `MakeBorderMap.distance` minimised
+ * over the non-degenerate edges.  Every element of the six outputs is written (no memset needed); no atomics, deterministic.
+ * G up to 1024, MR_ERR_UNSUPPORTED beyond; G == 0 is valid. */
+int mr_sizeof_db_record(void);
+int mr_db_targets(const double* polys /* [N][G][4][2] */, const int* count /* [N] */,
+                  const int* ignore_in /* [N][G] */, int N, int G, int H, int W,
+                  double min_text_size, double shrink_ratio, double thresh_min, double thresh_max,
+                  void* records, int* ignore_out /* [N][G] */, double* dist /* [N][G], D or 0 */,
+                  float* gt, float* mask, float* thresh_map, float* thresh_mask,
+                  hipStream_t stream);
+
 /* ---- Attention-GRU decoder step kernels (decoders/attention_decoder.py:146-231; the GEMMs use mr_gemm_nt/tn) ----- */
 int mr_attn_step_fwd(int dtype, const void* hproj, const void* eproj, const float* v, const void* enc, float* weights,
                      void* context, int N, int T, int Hd, int Ep, hipStream_t stream);

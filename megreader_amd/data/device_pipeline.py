@@ -168,7 +168,8 @@ class DevicePipeline(object):
 
 
 class Prefetcher(object):
-    """Iterates `(images, texts)` batches from a host loader and yields device batches, keeping one batch in flight:
+    """Iterates `(images, texts)` batches (DevicePipeline; `(images, polygons, ignore_tags)` for DetectionPipeline) from a
+    host loader and yields device batches, keeping one batch in flight:
     the staging copy and the pipeline kernels of batch i+1 run on a side stream while the training step of batch i
     runs on the main stream (replaces the blocking `.to(device)` of structure/model.py:173)."""
 
@@ -183,8 +184,7 @@ class Prefetcher(object):
         pending = None
 
         def launch(item, slot):
-            images, texts = item
-            staged, layout = self.pipe.pack(images, texts, slot)
+            staged, layout = self.pipe.pack(*item, slot=slot)   # (images, texts) / (images, polygons, ignore_tags)
             with torch.cuda.stream(self.stream):
                 batch = self.pipe.upload(staged, layout)
                 ev = torch.cuda.Event()
