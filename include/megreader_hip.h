@@ -790,6 +790,37 @@ int mr_resize_normalize(const unsigned char* src, const void* desc, int N, int H
 int mr_encode_labels(const int* codepoints, const long long* offsets, int N, int max_size, const int* table_cp,
                      const int* table_id, int ntab, int unknown, int* label, int* length, hipStream_t stream);
 
+/* ---- DB detector augmentation (csrc/db_augment.hip): the image half of data/processes/augment_data.py
+ * (`AugmentDetectionData`: Fliplr, Affine rotate, Resize), data/processes/random_crop_data.py (`RandomCropData`) and
+ * data/processes/normalize_image.py in ONE bilinear pass.  The host composes the chain into one affine map per image
+ * (megreader_amd/data/detection_augment.py); the kernel samples the decoded uint8 HWC source once along it and writes the
+ * normalised f32 [N][3][H][W] canvas.  Canvas pixel (u, v), v < dst_h and u < dst_w:
+ *   uc = min(max(u, cu0), cu1), vc = min(max(v, cv0), cv1)
+ *   x = a[0]*uc + a[1]*vc + a[2], y = a[3]*uc + a[4]*vc + a[5]     (float64, left to right, every product and sum rounded)
+ *   ix = floor(x), fx = (float)(x - ix); iy = floor(y), fy = (float)(y - iy)
+ *   p00 = src(ix, iy), p01 = src(ix + 1, iy), p10 = src(ix, iy + 1), p11 = src(ix + 1, iy + 1) as float; a tap outside
+ *   [0, src_w) x [0, src_h), or outside the uploaded window, is 0
+ *   top = p00*(1 - fx) + p01*fx, bot = p10*(1 - fx) + p11*fx, val = top*(1 - fy) + bot*fy        (float32, no fma)
+ *   dst[n][c][v][u] = (float)((double)val - mean[c]) / 255.f                         (as mr_resize_normalize ends)
+ * Every other canvas pixel gets the normalised value of a zero pixel; every element of dst is written.  With a = identity,
+ * the clamp and the valid region the whole canvas, the result equals mr_resize_normalize at identity scale bit for bit.
+ * The kernel reads only bytes src[offset + r*pitch + 3*k + c], 0 <= r < win_h, 0 <= k < win_w: the host may upload the
+ * window alone. */
+typedef struct mr_warp_desc {
+  long long offset;             /* byte offset of the uploaded window's first pixel in the packed source buffer */
+  int pitch;                    /* bytes per row of the uploaded window (>= 3 * win_w) */
+  int src_h, src_w;             /* the full source image: taps outside it read as pixel value 0 (imgaug cval = 0) */
+  int win_x, win_y;             /* source coordinates of the window's first pixel */
+  int win_h, win_w;             /* rows and columns that were uploaded; a tap outside them reads as 0 as well */
+  int dst_h, dst_w;             /* valid canvas region; the rest is the zero canvas of RandomCropData */
+  int reserved;                 /* 0 (keeps the doubles 8-byte aligned) */
+  double cu0, cu1, cv0, cv1;    /* (u, v) is clamped to [cu0, cu1] x [cv0, cv1] before the map: the crop's replicated border */
+  double a[6];                  /* canvas -> source: x = a[0]*uc + a[1]*vc + a[2], y = a[3]*uc + a[4]*vc + a[5] */
+} mr_warp_desc;
+int mr_sizeof_warp_desc(void);
+int mr_warp_normalize(const unsigned char* src, const void* desc /* [N] */, int N, int H, int W,
+                      double mean0, double mean1, double mean2, float* dst /* [N][3][H][W] */, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,5 @@
 """On-device input pipeline."""
 from .device_pipeline import DevicePipeline, Prefetcher  # noqa: F401
+from .detection_augment import AugmentPlan, DetectionAugmenter, WarpDesc  # noqa: F401
 from .detection_pipeline import DetectionPipeline  # noqa: F401
 from .msgpack_records import UnpackMsgpackData, records_to_batch  # noqa: F401

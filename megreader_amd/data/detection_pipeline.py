@@ -30,8 +30,10 @@ Parity unpinned: pyclipper, shapely and cv2 are not dependencies
   * the single pixel where the reference produces NaN for a degenerate edge is not reproduced: a pixel on an end point
     gets distance 0 (its `nan_to_num` path), zero-length edges (clipping makes them) are skipped in every distance, and
     1 - cosin^2 is clamped at 0 where rounding leaves it negative.
-Only quadrilaterals are supported (`validate_polygons` and the size filter index points 0..3); augmentation
-(`AugmentDetectionData`, `RandomCropData`) stays on the host.
+Only quadrilaterals are supported (`validate_polygons` and the size filter index points 0..3).  Augmentation
+(`AugmentDetectionData`, `RandomCropData`) is one more stage of the same pipeline when an `augmenter` is given
+(data/detection_augment.py): the host draws a plan per image from the shape and the quads, uploads only the part of the raw
+photo the plan can touch, and `mr_warp_normalize` (csrc/db_augment.hip) takes the place of `mr_resize_normalize`.
 """
 import ctypes
 
@@ -39,6 +41,7 @@ import numpy as np
 import torch
 
 from .._lib import call, load, ptr
+from .detection_augment import WarpDesc
 from .device_pipeline import RGB_MEAN, ImgDesc
 
 MAX_POLYGONS = 1024     # mr_db_targets: polygon slots per image
@@ -63,7 +66,7 @@ def _align16(n):
 
 class DetectionPipeline(object):
     def __init__(self, image_size=(640, 640), min_text_size=8, shrink_ratio=0.4, thresh_min=0.3, thresh_max=0.7,
-                 max_polygons=None, device=None):
+                 max_polygons=None, device=None, augmenter=None):
         self.image_size = tuple(image_size)
         self.min_text_size = float(min_text_size)
         self.shrink_ratio = float(shrink_ratio)
@@ -73,6 +76,7 @@ class DetectionPipeline(object):
             raise ValueError("max_polygons must be in [0, %d], got %r" % (MAX_POLYGONS, max_polygons))
         self.max_polygons = None if max_polygons is None else int(max_polygons)   # None: the batch's largest count
         self.device = torch.device(device if device is not None else "cuda")
+        self.augmenter = augmenter      # a DetectionAugmenter: pack() takes raw photos of any size (module docstring)
         self._staging = {}
 
     def _pinned(self, key, nbytes):
@@ -82,10 +86,13 @@ class DetectionPipeline(object):
             buf = self._staging[key] = buf.pin_memory() if torch.cuda.is_available() else buf
         return buf
 
-    def pack(self, images, polygons, ignore_tags, slot=0):
+    def pack(self, images, polygons, ignore_tags, slot=0, plans=None):
         """Host side: lay the uint8 HWC images (already of `image_size`), their descriptors, the quads padded to G slots
         per image (float64 [N][G][4][2]), the counts (int32 [N]) and the ignore tags (int32 [N][G]) out in ONE pinned staging
-        buffer (per prefetch slot).  Returns (pinned uint8 tensor, layout tuple)."""
+        buffer (per prefetch slot).  Returns (pinned uint8 tensor, layout tuple).
+        With an augmenter (or ready-made `plans`, one AugmentPlan per image) the images are raw photos of any size: one plan
+        per image is sampled, only each plan's source window is copied, warp descriptors stand in the place of `ImgDesc`,
+        and the quads and tags packed are the plan's surviving, transformed ones."""
         n = len(images)
         H, W = self.image_size
         if len(polygons) != n or len(ignore_tags) != n:
@@ -95,13 +102,28 @@ class DetectionPipeline(object):
         for q, t in zip(quads, tags):
             if len(q) != len(t):
                 raise ValueError("DetectionPipeline: %d polygons with %d ignore tags" % (len(q), len(t)))
+        warp = self.augmenter is not None or plans is not None
+        if warp:
+            for im in images:
+                if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                    raise TypeError("images must be uint8 HWC with 3 channels (cv2.imread(..., IMREAD_COLOR))")
+            if plans is None:
+                plans = [self.augmenter.sample(im.shape, q, t) for im, q, t in zip(images, quads, tags)]
+            if len(plans) != n:
+                raise ValueError("DetectionPipeline: %d images, %d plans" % (n, len(plans)))
+            for im, plan in zip(images, plans):
+                if tuple(plan.canvas) != (H, W) or tuple(plan.shape) != im.shape[:2]:
+                    raise ValueError("DetectionPipeline: a plan from %s onto %s for an image of %s and a canvas of %s"
+                                     % (tuple(plan.shape), tuple(plan.canvas), im.shape[:2], (H, W)))
+            quads = [_quads(plan.polygons) for plan in plans]
+            tags = [np.asarray(plan.ignore_tags).astype(bool).reshape(-1) for plan in plans]
         most = max([len(q) for q in quads] or [0])
         G = most if self.max_polygons is None else self.max_polygons
         if most > G or G > MAX_POLYGONS:
             raise ValueError("DetectionPipeline: %d polygons in one image exceed the %d slots" % (most, min(G, MAX_POLYGONS)))
-        descs = (ImgDesc * n)()
+        descs = ((WarpDesc if warp else ImgDesc) * n)()
         off = 0
-        for i, im in enumerate(images):
+        for i, im in enumerate(() if warp else images):
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
                 raise TypeError("images must be uint8 HWC with 3 channels (cv2.imread(..., IMREAD_COLOR))")
             if im.shape[:2] != (H, W):
@@ -109,16 +131,23 @@ class DetectionPipeline(object):
             descs[i].offset, descs[i].h, descs[i].w, descs[i].pitch, descs[i].dst_w = off, H, W, W * 3, W
             descs[i].scale_x = descs[i].scale_y = 1.0
             off += _align16(H * W * 3)
+        for i, plan in enumerate(plans if warp else ()):
+            plan.fill(descs[i], off)
+            off += _align16(plan.window[2] * plan.window[3] * 3)
         desc_off = off
-        poly_off = desc_off + _align16(ctypes.sizeof(ImgDesc) * n)
+        poly_off = desc_off + _align16(ctypes.sizeof(descs))
         count_off = poly_off + _align16(n * G * 64)
         tag_off = count_off + _align16(n * 4)
         total = tag_off + _align16(n * G * 4)
         buf = self._pinned(slot, total)
         host = buf.numpy()
         for i, im in enumerate(images):
-            host[descs[i].offset:descs[i].offset + H * W * 3] = np.ascontiguousarray(im).reshape(-1)
-        host[desc_off:desc_off + ctypes.sizeof(ImgDesc) * n] = np.frombuffer(bytes(descs), dtype=np.uint8)
+            if warp:
+                x, y, w, h = plans[i].window
+                host[descs[i].offset:descs[i].offset + h * w * 3].reshape(h, w, 3)[...] = im[y:y + h, x:x + w]
+            else:
+                host[descs[i].offset:descs[i].offset + H * W * 3] = np.ascontiguousarray(im).reshape(-1)
+        host[desc_off:desc_off + ctypes.sizeof(descs)] = np.frombuffer(bytes(descs), dtype=np.uint8)
         host[poly_off:total] = 0
         pv = host[poly_off:poly_off + n * G * 64].view(np.float64).reshape(n, G, 4, 2)
         cv = host[count_off:count_off + n * 4].view(np.int32)
@@ -127,18 +156,18 @@ class DetectionPipeline(object):
             pv[i, :len(q)] = q
             cv[i] = len(q)
             tv[i, :len(t)] = t
-        return buf[:total], (n, G, desc_off, poly_off, count_off, tag_off)
+        return buf[:total], (n, G, desc_off, poly_off, count_off, tag_off) + (('warp',) if warp else ())
 
     def upload(self, staged, layout):
         """One async H2D copy of the staging buffer, then the two kernels' launches, on the CURRENT stream."""
-        n, G, desc_off, poly_off, count_off, tag_off = layout
+        n, G, desc_off, poly_off, count_off, tag_off = layout[:6]
         H, W = self.image_size
         dev = self.device
         dbuf = torch.empty((staged.numel(),), dtype=torch.uint8, device=dev)
         dbuf.copy_(staged, non_blocking=True)
         image = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
-        call("mr_resize_normalize", ptr(dbuf), dbuf.data_ptr() + desc_off, n, H, W, RGB_MEAN[0], RGB_MEAN[1],
-             RGB_MEAN[2], ptr(image))
+        call("mr_warp_normalize" if layout[6:] == ('warp',) else "mr_resize_normalize", ptr(dbuf), dbuf.data_ptr() + desc_off,
+             n, H, W, RGB_MEAN[0], RGB_MEAN[1], RGB_MEAN[2], ptr(image))
         records = torch.empty((max(n * G * load().mr_sizeof_db_record(), 8) // 8,), dtype=torch.float64, device=dev)
         ignore = torch.empty((n, G), dtype=torch.int32, device=dev)
         dist = torch.empty((n, G), dtype=torch.float64, device=dev)
@@ -152,6 +181,6 @@ class DetectionPipeline(object):
         return {'image': image, 'gt': gt, 'mask': mask, 'thresh_map': thresh_map, 'thresh_mask': thresh_mask,
                 'ignore_tags': ignore, '_keepalive': dbuf}
 
-    def process(self, images, polygons, ignore_tags):
-        staged, layout = self.pack(images, polygons, ignore_tags)
+    def process(self, images, polygons, ignore_tags, plans=None):
+        staged, layout = self.pack(images, polygons, ignore_tags, plans=plans)
         return self.upload(staged, layout)
