@@ -200,6 +200,224 @@ template <typename T, int CNT> struct EpiColStats {
   }
 };
 
+// ---------------------------------------------------------------------------------------------
+// Store epilogue of the direct-to-LDS NT kernels (16x16 accumulator tiles; igemm_nt_glds_kernel, igemm_nt_big_kernel,
+// igemm_nt_p8_kernel).  A lane owns the 4*TN consecutive channels n .. of rows m + 16 j, j < TM; acc_of(i, j) returns its
+// accumulator tile (column block i, row block j) as f32x4.
+//
+// nt_store_interior: the straight-line path of a wave whose whole WTM x WTN tile lies inside C with 16-byte stores possible.
+// What the run-time switches of the epilogue select (bias, ReLU, addend, statistics) is decided ONCE per wave by nt_epilogue_interior and
+// arrives here as template arguments; no row or column test is left.  The bias -- the same 4*TN floats for every row block --
+// is loaded once, in one batch behind one wait.  (As `epi.bias[n + c]` inside the row loop it was reloaded for every row block,
+// one dword at a time, each behind s_waitcnt vmcnt(0): loads and stores share that counter, so every reload also waited for the
+// stores of the row block before it.)  The addend of row block j + 1 is loaded before the stores of row block j for the same
+// reason (into the registers of row block j's, which are dead by then).  The arithmetic is that of EpiStore::store_run / EpiColStats::add, operation for operation.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void pin_here(uint4& a) {   // what is computed from `a` stays behind this point of the program
+  asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w));
+}
+template <typename T, int TM, int TN, bool BIAS, bool RELU, bool ADD, bool STATS, typename Epi, typename AccF>
+__device__ __forceinline__ void nt_store_interior(const Epi& epi, int m, int n, int l15, AccF&& acc_of) {
+  constexpr int E16 = 16 / (int)sizeof(T), NQ = 4 * TN / E16;
+  // The instantiations a kernel branches between compute the same expressions: merged across that branch by the compiler, the
+  // sums of ALL row blocks were hoisted above it, TM * 4*TN live registers.  The empty asm makes them different values.
+  constexpr int VARIANT = (int)BIAS | (int)RELU << 1 | (int)ADD << 2 | (int)STATS << 3;
+  float bv[4 * TN];
+  if constexpr (BIAS) {
+    const float* __restrict__ bp = epi.bias + n;   // 4-byte aligned only
+#pragma unroll
+    for (int c = 0; c < 4 * TN; ++c) bv[c] = bp[c];
+  }
+  EpiColStats<T, TN> cst;
+  if constexpr (STATS) cst.init();
+  const long long row0 = (long long)m * epi.ldc + n;
+  const long long rstep = 16 * epi.ldc / E16;   // uint4s between row blocks (ldc % E16 == 0 here)
+  uint4* dst = (uint4*)(epi.C + row0);
+  const uint4* asrc = nullptr;
+  uint4 av[NQ];
+  if constexpr (ADD) {
+    asrc = (const uint4*)(epi.addend + row0);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) av[q] = asrc[q];
+  }
+  // The scheduling barriers keep the phases of a row block in program order -- values chunk by chunk, then the loads of the NEXT
+  // row block, then the stores -- and the TM independent row blocks apart: interleaved they cost registers (occupancy) and hide
+  // nothing.
+#pragma unroll
+  for (int j = 0; j < TM; ++j) {
+    uint4 out[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {   // one 16-byte chunk = E16 / 4 accumulator tiles
+      f32x4 v[E16 / 4];
+#pragma unroll
+      for (int i = 0; i < E16 / 4; ++i) {
+        v[i] = acc_of(q * (E16 / 4) + i, j);
+        asm volatile("; nt epilogue variant %1" : "+v"(v[i]) : "n"(VARIANT));
+      }
+      // (pins the unpacking of the addend here: placed next to its load, it would wait for the load ahead of the stores)
+      if constexpr (ADD) pin_here(av[q]);
+      T o[E16];
+#pragma unroll
+      for (int e = 0; e < E16; ++e) {
+        const int c = q * E16 + e;
+        float t = v[e / 4][e % 4];
+        if constexpr (ADD) t += to_f32(((const T*)&av[q])[e]);
+        if constexpr (BIAS) t += bv[c];
+        if constexpr (STATS) {
+          const float r = to_f32(from_f32<T>(t));   // the value the store writes
+          cst.s[c] += r;
+          cst.q[c] += r * r;
+        }
+        if constexpr (RELU) t = fmaxf(t, 0.f);
+        o[e] = from_f32<T>(t);
+      }
+      out[q] = *(const uint4*)o;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (ADD) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (j + 1 < TM) {
+        asrc += rstep;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) av[q] = asrc[q];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) dst[q] = out[q];
+    dst += rstep;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if constexpr (STATS) cst.flush(epi, n, l15);
+}
+
+// BatchNorm-backward statistics epilogue (EpiStoreB) of an interior wave tile: x, y and the addend of row block j + 1 are
+// loaded as 16-byte vectors before the stores of row block j.  Values and order as EpiColStats::add (kBnb) + store_run.
+template <typename T, int TM, int TN, bool ADD, bool HASY, typename Epi, typename AccF>
+__device__ __forceinline__ void nt_store_interior_bnb(const Epi& epi, int m, int n, int l15, AccF&& acc_of) {
+  constexpr int E16 = 16 / (int)sizeof(T), NQ = 4 * TN / E16;
+  constexpr int VARIANT = 16 | (int)ADD | (int)HASY << 1;   // see nt_store_interior
+  EpiColStats<T, TN> cst;
+  cst.init();
+  const long long row0 = (long long)m * epi.ldc + n;
+  const long long rstep = 16 * epi.ldc / E16;
+  uint4* dst = (uint4*)(epi.C + row0);
+  const uint4* xsrc = (const uint4*)(epi.bnb_x + row0);
+  const uint4* ysrc = HASY ? (const uint4*)(epi.bnb_y + row0) : nullptr;
+  const uint4* asrc = ADD ? (const uint4*)(epi.addend + row0) : nullptr;
+  uint4 xv[NQ], yv[NQ], av[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    xv[q] = xsrc[q];
+    if constexpr (HASY) yv[q] = ysrc[q];
+    if constexpr (ADD) av[q] = asrc[q];
+  }
+#pragma unroll
+  for (int j = 0; j < TM; ++j) {
+    uint4 out[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {   // one 16-byte chunk = E16 / 4 accumulator tiles
+      f32x4 v[E16 / 4];
+#pragma unroll
+      for (int i = 0; i < E16 / 4; ++i) {
+        v[i] = acc_of(q * (E16 / 4) + i, j);
+        asm volatile("; nt epilogue variant %1" : "+v"(v[i]) : "n"(VARIANT));
+      }
+      pin_here(xv[q]);   // (as in nt_store_interior: the operands are unpacked here, not next to their loads)
+      if constexpr (HASY) pin_here(yv[q]);
+      if constexpr (ADD) pin_here(av[q]);
+      T o[E16];
+#pragma unroll
+      for (int e = 0; e < E16; ++e) {
+        const int c = q * E16 + e;
+        float t = v[e / 4][e % 4];
+        if constexpr (ADD) t += to_f32(((const T*)&av[q])[e]);
+        o[e] = from_f32<T>(t);
+        float r = to_f32(o[e]);   // the value the store writes
+        if constexpr (HASY)
+          if (!(to_f32(((const T*)&yv[q])[e]) > 0.f)) r = 0.f;
+        cst.s[c] += r;
+        cst.q[c] += r * to_f32(((const T*)&xv[q])[e]);
+      }
+      out[q] = *(const uint4*)o;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (j + 1 < TM) {
+      xsrc += rstep;
+      if constexpr (HASY) ysrc += rstep;
+      if constexpr (ADD) asrc += rstep;
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        xv[q] = xsrc[q];
+        if constexpr (HASY) yv[q] = ysrc[q];
+        if constexpr (ADD) av[q] = asrc[q];
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) dst[q] = out[q];
+    dst += rstep;
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  cst.flush(epi, n, l15);
+}
+
+// wave_m0 / wave_n0: first row / channel of the wave's tile (wave-uniform); l15 / lg: the lane's row and channel group.
+// Returns true when the wave's tile was stored here; false = the caller runs its general (edge-capable) epilogue.
+// PATHS: which straight-line instantiations a kernel carries next to the general code (the kernel's choice, by register budget:
+// every instantiation is inlined, and the kernel's register count is that of its hungriest path).
+constexpr int NT_EPI_PLAIN = 1, NT_EPI_ADD = 2, NT_EPI_STATS = 4, NT_EPI_BNB = 8;   // BNB: EpiStoreB (4-wave kernels) only
+constexpr int NT_EPI_STORE = NT_EPI_PLAIN | NT_EPI_ADD | NT_EPI_STATS;
+template <typename T, int TM, int TN, int PATHS, typename Epi, typename AccF>
+__device__ __forceinline__ bool nt_epilogue_interior(const Epi& epi, int wave_m0, int wave_n0, int l15, int lg, AccF&& acc_of) {
+  constexpr int E16 = 16 / (int)sizeof(T);
+  const int m = wave_m0 + l15, n = wave_n0 + lg * (4 * TN);
+  bool with_stats = false;
+  if constexpr (EpiHasStats<Epi>::value) with_stats = epi.stats != nullptr;
+  if constexpr ((4 * TN) % E16 == 0) {
+    // every term is wave-uniform: one branch per wave to a straight-line instantiation; edge tiles are left to the caller
+    const bool interior = epi.vec_ok && (epi.ldc % E16) == 0 && wave_m0 + 16 * TM <= epi.M && wave_n0 + 16 * TN <= epi.N;
+    const bool has_bias = epi.bias != nullptr, has_add = epi.addend != nullptr;
+    if constexpr (Epi::kBnb) {
+      // (x / y are read as 16-byte vectors there; the general code reads them element by element and asks nothing of them)
+      const bool xy_vec = (((uintptr_t)epi.bnb_x | (uintptr_t)epi.bnb_y) & 15) == 0;
+      if ((PATHS & NT_EPI_BNB) && interior && xy_vec && with_stats && !has_bias && !epi.relu) {
+        const bool has_y = epi.bnb_y != nullptr;
+        if (has_add) {
+          if (has_y) nt_store_interior_bnb<T, TM, TN, true, true>(epi, m, n, l15, acc_of);
+          else nt_store_interior_bnb<T, TM, TN, true, false>(epi, m, n, l15, acc_of);
+        } else {
+          if (has_y) nt_store_interior_bnb<T, TM, TN, false, true>(epi, m, n, l15, acc_of);
+          else nt_store_interior_bnb<T, TM, TN, false, false>(epi, m, n, l15, acc_of);
+        }
+        return true;
+      }
+    } else if (interior && !(with_stats && has_add) && (PATHS & (has_add ? NT_EPI_ADD : with_stats ? NT_EPI_STATS : NT_EPI_PLAIN))) {
+      auto go = [&](auto bias_tag, auto relu_tag) {
+        constexpr bool B = decltype(bias_tag)::value, R = decltype(relu_tag)::value;
+        if (has_add) {
+          if constexpr ((PATHS & NT_EPI_ADD) != 0) nt_store_interior<T, TM, TN, B, R, true, false>(epi, m, n, l15, acc_of);
+        } else if (with_stats) {
+          if constexpr ((PATHS & NT_EPI_STATS) != 0 && EpiHasStats<Epi>::value)
+            nt_store_interior<T, TM, TN, B, R, false, true>(epi, m, n, l15, acc_of);
+        } else {
+          if constexpr ((PATHS & NT_EPI_PLAIN) != 0) nt_store_interior<T, TM, TN, B, R, false, false>(epi, m, n, l15, acc_of);
+        }
+      };
+      if (has_bias) {
+        if (epi.relu) go(std::true_type{}, std::true_type{});
+        else go(std::true_type{}, std::false_type{});
+      } else {
+        if (epi.relu) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
+      }
+      return true;
+    }
+  }
+  return false;
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // NT kernel.  AMODE 0: dense A[M,K] (row stride lda).  AMODE 1/2: A is an NHWC tensor gathered
@@ -947,6 +1165,20 @@ __global__ __launch_bounds__(256) void igemm_nt_glds_kernel(NtArgs a, ConvGeom g
     }
   }
 
+  // Straight-line epilogue paths this instantiation can afford (kernel-resource-usage of every instantiation with each set of
+  // paths, against the same kernel without them): none may cost a wave of occupancy.  The 4-stage kernels at 64 rows run at the
+  // edge of their budget (55-56 registers for 7 waves); the BatchNorm-backward path holds three operand streams.
+  constexpr int EPI_PATHS = Epi::kBnb ? ((sizeof(T) == 2 && NST == 2) ? NT_EPI_BNB : 0)
+                            : NST != 2 ? (BM >= 96 ? (NT_EPI_PLAIN | NT_EPI_ADD) : 0)
+                            : sizeof(T) == 2 ? (NT_EPI_PLAIN | NT_EPI_ADD | ((BM == 64 && BN == 128) ? 0 : NT_EPI_STATS))
+                                             : (NT_EPI_PLAIN | (BM == 128 ? (NT_EPI_ADD | NT_EPI_STATS) : 0));
+  if constexpr (EPI_PATHS != 0) {
+    if (nt_epilogue_interior<T, TM, TN, EPI_PATHS>(epi, m0 + wm_ * WTM, n0 + wn_ * WTN, l15, lg, [&](int i, int j) -> f32x4 {
+          if constexpr (WIDE) return (f32x4){(float)tot[i][j][0], (float)tot[i][j][1], (float)tot[i][j][2], (float)tot[i][j][3]};
+          else return acc[i][j];
+        }))
+      return;
+  }
   // row block outer, column block inner: the TN stores of one output row land back to back, so its 128-byte line is
   // completed in L2 before it can be evicted half-written (the 256x256 kernel wrote 2.5x its output bytes to HBM
   // with the loops the other way round)
@@ -1161,23 +1393,39 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_nt_big_kernel(NtArgs a, Co
     constexpr int CH = BN / 8;
     static_assert((CH & (CH - 1)) == 0 && (4 * TN) % 8 == 0, "pooled epilogue: tile width / lane run in whole 16-byte chunks");
     __syncthreads();                       // every wave is done reading the stage buffers (no LDS-DMA is in flight here)
+    // bias / ReLU are decided once per workgroup; the lane's 4*TN bias values are loaded once, in one batch (see nt_store_interior)
+    auto tile_to_lds = [&](auto bias_tag, auto relu_tag) {
+      constexpr bool BIAS = decltype(bias_tag)::value, RELU = decltype(relu_tag)::value;
+      const int nl = n0 + wn_ * WTN + lg * (4 * TN);
+      float bv[4 * TN];
+      if constexpr (BIAS) {
 #pragma unroll
-    for (int j = 0; j < TM; ++j) {
-      const int r = wm_ * WTM + j * 16 + l15;
-#pragma unroll
-      for (int q = 0; q < TN / 2; ++q) {   // one 16-byte chunk = the 8 channels of accumulator tiles 2q, 2q+1
-        const int n = n0 + wn_ * WTN + lg * (4 * TN) + q * 8;
-        T o[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float t = acc[2 * q + e / 4][j][e % 4];
-          if (epi.bias && n + e < epi.N) t += epi.bias[n + e];
-          if (epi.relu) t = fmaxf(t, 0.f);
-          o[e] = from_f32<T>(t);
-        }
-        const int c = (wn_ * WTN + lg * (4 * TN)) / 8 + q;
-        smem[r * CH + (c ^ (r & (CH - 1)))] = *(const uint4*)o;
+        for (int e = 0; e < 4 * TN; ++e) bv[e] = nl + e < epi.N ? epi.bias[nl + e] : 0.f;   // (channels >= N are never pooled)
       }
+#pragma unroll
+      for (int j = 0; j < TM; ++j) {
+        const int r = wm_ * WTM + j * 16 + l15;
+#pragma unroll
+        for (int q = 0; q < TN / 2; ++q) {   // one 16-byte chunk = the 8 channels of accumulator tiles 2q, 2q+1
+          T o[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float t = acc[2 * q + e / 4][j][e % 4];
+            if constexpr (BIAS) t += bv[q * 8 + e];
+            if constexpr (RELU) t = fmaxf(t, 0.f);
+            o[e] = from_f32<T>(t);
+          }
+          const int c = (wn_ * WTN + lg * (4 * TN)) / 8 + q;
+          smem[r * CH + (c ^ (r & (CH - 1)))] = *(const uint4*)o;
+        }
+      }
+    };
+    if (epi.bias != nullptr) {
+      if (epi.relu) tile_to_lds(std::true_type{}, std::true_type{});
+      else tile_to_lds(std::true_type{}, std::false_type{});
+    } else {
+      if (epi.relu) tile_to_lds(std::false_type{}, std::true_type{});
+      else tile_to_lds(std::false_type{}, std::false_type{});
     }
     __syncthreads();
     // pooled elements of this tile: thread -> channel chunk c = tid % CH (fixed) and pooled pixels tid / CH, + 64 NW / CH, ...
@@ -1242,6 +1490,14 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_nt_big_kernel(NtArgs a, Co
     else pool_one(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
     return;
   } else {
+    // (see igemm_nt_glds_kernel: the paths each tile shape can afford without losing a wave of occupancy or spilling)
+    constexpr bool FLAGSHIP = (WM == 2 && WN == 4 && TM == 8 && TN == 4) || (WM == 1 && WN == 8 && TM == 17 && TN == 2);
+    constexpr int EPI_PATHS = FLAGSHIP ? NT_EPI_STORE : (TN == 2 && !(WM == 4 && TM == 3)) ? (NT_EPI_PLAIN | NT_EPI_ADD) : 0;
+    if constexpr (EPI_PATHS != 0) {
+      if (nt_epilogue_interior<T, TM, TN, EPI_PATHS>(epi, m0 + wm_ * WTM, n0 + wn_ * WTN, l15, lg,
+                                                      [&](int i, int j) -> f32x4 { return acc[i][j]; }))
+        return;
+    }
   // row block outer, column block inner: the TN stores of one output row land back to back, so its 128-byte line is
   // completed in L2 before it can be evicted half-written (the 256x256 kernel wrote 2.5x its output bytes to HBM
   // with the loops the other way round)

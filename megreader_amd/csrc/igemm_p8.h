@@ -251,6 +251,9 @@ __global__ __launch_bounds__(512) void igemm_nt_p8_kernel(NtArgs a, ConvGeom g, 
   }
   if (c < nk) ktile(c, 0);
 
+  if (nt_epilogue_interior<bf16_t, 8, 4, NT_EPI_STORE>(epi, m0 + wm_ * 128, n0 + wn_ * 64, l15, lg,
+                                                      [&](int i, int j) -> f32x4 { return acc[i][j]; }))
+    return;
   EpiColStats<bf16_t, 4> cst;
   bool with_stats = false;
   if constexpr (EpiHasStats<Epi>::value) with_stats = epi.stats != nullptr;
