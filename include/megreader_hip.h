@@ -821,6 +821,41 @@ int mr_sizeof_warp_desc(void);
 int mr_warp_normalize(const unsigned char* src, const void* desc /* [N] */, int N, int H, int W,
                       double mean0, double mean1, double mean2, float* dst /* [N][3][H][W] */, hipStream_t stream);
 
+/* ---- Quad crops (csrc/quad_crop.hip): data/crop_file_dataset.py `ImageCropper.crop` -- getPerspectiveTransform +
+ * warpPerspective of a detected quadrilateral, `ensure_horizontal`, `ResizeImage` (modes "resize" and "pad"), - RGB_MEAN,
+ * / 255 -- in ONE bilinear pass from the resident uint8 HWC photos to the recogniser's f32 [M][3][H][W] batch.  The host
+ * plans each crop in float64 from shapes and points only (megreader_amd/data/quad_crop.py); many crops read from a few
+ * photos, so the photos are a table of their own and a crop names its photo by index.  Canvas pixel (u, v) of crop m,
+ * u < dst_w (float64, left to right, every product and sum rounded on its own):
+ *   cx = min(max((u + 0.5)*sx - 0.5, 0), cu1), cy = min(max((v + 0.5)*sy - 0.5, 0), cv1)      (cv2.resize's sampling point)
+ *   X = h[0]*cx + h[1]*cy + h[2], Y = h[3]*cx + h[4]*cy + h[5], D = h[6]*cx + h[7]*cy + h[8];  x = X / D, y = Y / D
+ *   D <= 0 (or NaN), or x or y not finite: the pixel value is 0.  Otherwise floor, (float) fractions, the four taps and the
+ *   float32 blend top, bot, val of mr_warp_normalize; a tap outside [0, w) x [0, h) of its photo reads as 0
+ *   (warpPerspective's BORDER_CONSTANT)
+ *   dst[m][c][v][u] = (float)((double)val - mean[c]) / 255.f
+ * Columns u >= dst_w, and crops whose `image` is not in [0, I), get the normalised zero pixel; every element of dst is
+ * written.  The kernel reads only bytes src[offset + r*pitch + 3*k + c], 0 <= r < h, 0 <= k < w, of the photos in the table;
+ * `offset` is relative to src and may be negative (a photo resident in another allocation).  The tables live in memory the
+ * device reads; when `crops` is pinned host memory the entry point checks every `image` index before the launch
+ * (MR_ERR_ARG), otherwise only the planner (QuadCropper.pack) and the kernel do.  M == 0 returns MR_OK without a launch. */
+typedef struct mr_crop_image {
+  long long offset;             /* byte offset of the photo's first pixel from src */
+  int pitch;                    /* bytes per row (>= 3 * w) */
+  int h, w;                     /* rows and columns */
+  int reserved;                 /* 0 (pads the entry to 24 bytes) */
+} mr_crop_image;
+typedef struct mr_crop_desc {
+  int image;                    /* index into the mr_crop_image table */
+  int dst_w;                    /* valid canvas columns (mode "pad"); the rest is the zero canvas */
+  double sx, sy;                /* cv2.resize scales: 1. / ((double)dst / src) of the (rotated) crop */
+  double cu1, cv1;              /* the crop-frame coordinate is clamped to [0, cu1] x [0, cv1] (cv2.resize's replicated border) */
+  double h[9];                  /* (rotated) crop frame -> source photo, row major, projective */
+} mr_crop_desc;
+int mr_sizeof_crop_image(void);
+int mr_sizeof_crop_desc(void);
+int mr_quad_crop(const unsigned char* src, const void* images /* [I] */, int I, const void* crops /* [M] */, int M,
+                 int H, int W, double mean0, double mean1, double mean2, float* dst /* [M][3][H][W] */, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,4 +24,16 @@ def get_compute_dtype():
     return _compute_dtype
 
 
-__all__ = ["set_compute_dtype", "get_compute_dtype"]
+def __getattr__(name):
+    """`megreader_amd.TextReader` (reader.py) and `megreader_amd.QuadCropper` (data/quad_crop.py), imported on first use: both
+    load the HIP library, which `import megreader_amd` alone does not."""
+    if name == "TextReader":
+        from .reader import TextReader
+        return TextReader
+    if name == "QuadCropper":
+        from .data.quad_crop import QuadCropper
+        return QuadCropper
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+__all__ = ["set_compute_dtype", "get_compute_dtype", "QuadCropper", "TextReader"]

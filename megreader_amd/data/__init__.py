@@ -2,4 +2,5 @@
 from .device_pipeline import DevicePipeline, Prefetcher  # noqa: F401
 from .detection_augment import AugmentPlan, DetectionAugmenter, WarpDesc  # noqa: F401
 from .detection_pipeline import DetectionPipeline  # noqa: F401
+from .quad_crop import CropPlan, QuadCropper, plan_crop, rect_corners  # noqa: F401
 from .msgpack_records import UnpackMsgpackData, records_to_batch  # noqa: F401

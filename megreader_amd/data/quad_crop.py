@@ -1,0 +1,314 @@
+"""Quad crops: from a detected or annotated quadrilateral in a photo to the recogniser's input, planned on the host and
+sampled ONCE on the GPU.
+
+The reference does it per text line on the host (data/crop_file_dataset.py:105-124, `ImageCropper.crop(image, poly)`):
+
+    box = min_area_rect(poly)                           concern/cv.py:5-12 (cv2.minAreaRect + cv2.boxPoints)
+    w, h = |box[1] - box[0]|, |box[2] - box[1]|
+    mat = getPerspectiveTransform(box, [(0, 0), (w, 0), (w, h), (0, h)]);  image = warpPerspective(image, mat, (w, h))
+    image = ensure_horizontal(image)                    np.flip(np.swapaxes(image, 0, 1), 0) if height > 1.5 * width
+    image = ResizeImage(image_size, mode)(image);  image -= RGB_MEAN;  image /= 255.
+
+None of these decisions reads a pixel.  `plan_crop` composes them, in float64, into one projective map from the (rotated)
+crop frame to the photo plus cv2.resize's sampling rule, and `mr_quad_crop` (csrc/quad_crop.hip, arithmetic in
+include/megreader_hip.h) samples the raw uint8 photo once along it and writes the normalised batch:
+
+    cropper = QuadCropper(image_size=(32, 128))
+    batch = cropper.crop(photos, quads)         # photos: uint8 HWC numpy arrays or CUDA tensors; quads: K x 4 x 2 per photo
+    batch['image'], batch['index'], batch['quad']       # f32 [M, 3, H, W], i32 [M] source photo, f64 [M, 4, 2]
+
+Frames.  The crop frame has `cw = max(int(w), 1)` columns and `ch = max(int(h), 1)` rows (warpPerspective's dsize); its point
+(xc, yc) lies in the photo at p0 + xc / w (p1 - p0) + yc / h (p3 - p0).  When `ch > 1.5 * cw` the frame is rotated as the
+reference rotates the pixels, R[i][j] = crop[j][cw - 1 - i]: the rotated frame has cw rows and ch columns and its point
+(xr, yr) is the crop's (cw - 1 - yr, xr); the rotation is folded into `h[9]`.  The resize samples the (rotated) frame of
+Hr rows and Wr columns at ((u + 0.5) sx - 0.5, (v + 0.5) sy - 0.5) clamped to [0, Wr - 1] x [0, Hr - 1], with
+sx = 1. / ((double)dst_w / Wr) and sy = 1. / ((double)H / Hr) as cv2.resize and `DevicePipeline.pack` compute them; in mode
+'pad' dst_w = `target_width('pad', ...)` of the (rotated) frame and the columns beyond it are the zero canvas.
+
+`rectify='quad'` is an extension: the four corners themselves (no rectangle fitted), made clockwise and started at the
+top edge, are mapped to a frame whose sides are the longer of each pair of opposite sides -- a true homography, for
+annotated word quadrilaterals seen in perspective.
+
+Known differences from the reference (parity unpinned, DESIGN.md §5: cv2 is not a dependency and cannot be run beside
+this code):
+  * ONE bilinear resampling instead of two (warpPerspective, then cv2.resize): sharper, and different at every pixel that
+    is not in a flat region; tests/_quad_crop_ref.py restates the two-pass chain and the tests report the deviation;
+  * warpPerspective's fixed-point weights (1/32 pixel, INTER_BITS = 5) and its rounding of the result to uint8 before the
+    resize are not modelled;
+  * the rectangle comes from the float64 calipers of structure/db_geometry.py, cv2.minAreaRect works in float32 and
+    getPerspectiveTransform on the float32 corners;
+  * the corner order is stated on its own terms (`rect_corners`) after OpenCV 3.4 / 4.0's angle range; OpenCV 4.5.1 changed
+    that range, and the reference's two branches with it.
+"""
+import ctypes
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from .._lib import STRUCTS, call, load, ptr
+from ..structure.db_geometry import min_area_rect
+from .device_pipeline import RGB_MEAN, target_width
+
+
+class CropImage(ctypes.Structure):
+    """struct mr_crop_image of include/megreader_hip.h."""
+    _fields_ = STRUCTS["mr_crop_image"]
+
+
+class CropDesc(ctypes.Structure):
+    """struct mr_crop_desc of include/megreader_hip.h."""
+    _fields_ = STRUCTS["mr_crop_desc"]
+
+
+def top_edge_rule(d):
+    """The corner rule for an edge direction d: d.x > 0 and -d.x <= d.y < d.x (within [-45, 45) degrees of the x axis)."""
+    return bool(d[0] > 0.0 and -d[0] <= d[1] < d[0])
+
+
+def _from_top_edge(corners):
+    """The four corners clockwise on screen (y grows downwards: reversed when the shoelace sum is negative), started so that
+    edge 0 -> 1 satisfies the rule; among several (or none, which rounding at exactly 45 degrees or a general quadrilateral can
+    produce) the edge with the largest d.x / |d|, the first of equal ones.  Plain floats: four points, called per text line."""
+    c = [(float(x), float(y)) for x, y in corners]
+    if len(c) != 4:
+        raise ValueError("expected four corners, got %d" % len(c))
+    if sum(c[k][0] * c[(k + 1) % 4][1] - c[(k + 1) % 4][0] * c[k][1] for k in range(4)) < 0.0:
+        c.reverse()
+    best = None
+    for k in range(4):
+        d = (c[(k + 1) % 4][0] - c[k][0], c[(k + 1) % 4][1] - c[k][1])
+        ln = math.hypot(d[0], d[1])
+        key = (ln > 0.0 and top_edge_rule(d), d[0] / ln if ln > 0.0 else -2.0)
+        if best is None or key > best[0]:
+            best = (key, k)
+    k = best[1]
+    return np.array(c[k:] + c[:k], dtype=np.float64)
+
+
+def rect_corners(quad):
+    """`concern/cv.py::min_area_rect` restated: the minimum-area rectangle of the points as corners [4, 2] float64 in the
+    order top-left, top-right, bottom-right, bottom-left.
+
+    Derivation (OpenCV 3.4 / 4.0).  `minAreaRect` returns (centre, (w, h), angle) with angle in [-90, 0), and
+    `boxPoints((c, (w, h), t))` returns, with a = sin(t) / 2 and b = cos(t) / 2,
+        pt0 = c + (-a h - b w,  b h - a w),  pt1 = c + (a h - b w, -b h - a w),  pt2 = 2 c - pt0,  pt3 = 2 c - pt1,
+    so pt1 - pt0 = h (sin t, -cos t) and pt2 - pt1 = w (cos t, sin t): their cross product is w h > 0, the corners run
+    clockwise on screen (y down) for every t.  The reference calls boxPoints with
+        angle < -45:   (w, h), t = angle + 180 in [90, 135):  d = pt1 - pt0 has d.x = sin t in (0.707, 1], d.y = -cos t in [0, 0.707)
+        otherwise:     (h, w), t = angle + 90  in [45, 90):   d.x = sin t in [0.707, 1),  d.y = -cos t in [-0.707, 0)
+    Both branches give a first edge with d.x > 0 and -d.x <= d.y < d.x (equality at angle = -45 exactly), and of the four
+    edge directions of a rectangle, 90 degrees apart, exactly one lies in that half-open quarter.  So the rule -- clockwise
+    on screen, edge 0 -> 1 within [-45, 45) degrees of the x axis -- picks the reference's order whatever rectangle
+    representation minAreaRect chose.  Parity unpinned: cv2 cannot be run beside this code."""
+    corners, _ = min_area_rect(np.asarray(quad, dtype=np.float64).reshape(-1, 2).tolist())
+    return _from_top_edge(corners)
+
+
+def _homography(src, dst):
+    """The projective map (3 x 3, h[8] = 1) that takes the four points src [4, 2] to dst [4, 2]: an 8 x 8 float64 solve."""
+    A = np.zeros((8, 8), dtype=np.float64)
+    b = np.zeros(8, dtype=np.float64)
+    for k, ((xs, ys), (xd, yd)) in enumerate(zip(src, dst)):
+        A[2 * k] = [xs, ys, 1.0, 0.0, 0.0, 0.0, -xs * xd, -ys * xd]
+        A[2 * k + 1] = [0.0, 0.0, 0.0, xs, ys, 1.0, -xs * yd, -ys * yd]
+        b[2 * k], b[2 * k + 1] = xd, yd
+    return np.append(np.linalg.solve(A, b), 1.0).reshape(3, 3)
+
+
+def crop_frame(quad, rectify='min_area_rect'):
+    """(corners [4, 2] TL TR BR BL, w, h) of the crop frame: `rect_corners` with w = |p1 - p0|, h = |p2 - p1|, or ('quad') the
+    four corners themselves, clockwise on screen and started by the same rule, with the longer of each pair of opposite sides."""
+    if rectify == 'min_area_rect':
+        p = rect_corners(quad)
+        return p, float(np.linalg.norm(p[1] - p[0])), float(np.linalg.norm(p[2] - p[1]))
+    if rectify == 'quad':
+        p = _from_top_edge(np.asarray(quad, dtype=np.float64).reshape(4, 2))
+        return p, float(max(np.linalg.norm(p[1] - p[0]), np.linalg.norm(p[2] - p[3]))), \
+            float(max(np.linalg.norm(p[2] - p[1]), np.linalg.norm(p[3] - p[0])))
+    raise ValueError("rectify must be 'min_area_rect' or 'quad', got %r" % (rectify,))
+
+
+class DegenerateQuad(ValueError):
+    """A quadrilateral with a zero side: there is no frame to crop."""
+
+
+class CropPlan(object):
+    """One crop: `shape` (H, W) of the photo, `corners` [4, 2] (TL, TR, BR, BL in the photo), `w`, `h` (the frame's real
+    sides), `cw`, `ch` (its integer size), `rotated`, `frame` (Hr, Wr) of the (rotated) frame the resize reads, `canvas`
+    (H, W), `dst_w`, `sx`, `sy`, `cu1`, `cv1`, `h9` (the 3 x 3 map from the (rotated) frame to the photo, row major) and
+    `crop_map` (3 x 3, the crop frame before the rotation -> photo: what warpPerspective inverts)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def fill(self, desc, image):
+        """Write this plan into a `CropDesc` that reads photo number `image` of the table."""
+        desc.image, desc.dst_w = int(image), int(self.dst_w)
+        desc.sx, desc.sy, desc.cu1, desc.cv1 = float(self.sx), float(self.sy), float(self.cu1), float(self.cv1)
+        for k in range(9):
+            desc.h[k] = float(self.h9[k])
+        return desc
+
+
+def plan_crop(shape, quad, image_size=(64, 512), mode='resize', rectify='min_area_rect'):
+    """The plan of one quadrilateral `quad` [4, 2] (any point set for 'min_area_rect') of a photo of `shape` (H, W[, C]) onto a
+    canvas `image_size` (H, W).  Raises DegenerateQuad (a ValueError) for a quadrilateral with a zero side."""
+    if mode not in ('resize', 'pad'):
+        raise NotImplementedError("quad crops support the batched modes 'resize' and 'pad' "
+                                  "(keep_size / keep_ratio produce per-sample shapes)")
+    H, W = int(image_size[0]), int(image_size[1])
+    p, w, h = crop_frame(quad, rectify)
+    if not (w > 0.0 and h > 0.0 and math.isfinite(w) and math.isfinite(h)):
+        raise DegenerateQuad("quad crop: the quadrilateral %s has a zero side" % (np.asarray(quad).tolist(),))
+    cw, ch = max(int(w), 1), max(int(h), 1)
+    if rectify == 'min_area_rect':                      # a rectangle: the map is affine, D == 1 exactly
+        ex, ey = (p[1] - p[0]) / w, (p[3] - p[0]) / h
+        m = np.array([[ex[0], ey[0], p[0][0]], [ex[1], ey[1], p[0][1]], [0.0, 0.0, 1.0]], dtype=np.float64)
+    else:
+        m = _homography([(0.0, 0.0), (w, 0.0), (w, h), (0.0, h)], p)
+    crop_map = m
+    rotated = ch > 1.5 * cw                             # is_vertival(height, width): height > width * 1.5
+    if rotated:                                         # (xr, yr) -> (xc, yc) = (cw - 1 - yr, xr)
+        m = m @ np.array([[0.0, -1.0, cw - 1.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]], dtype=np.float64)
+    Hr, Wr = (cw, ch) if rotated else (ch, cw)
+    dst_w = W if mode == 'resize' else target_width('pad', (H, W), (Hr, Wr))
+    return CropPlan(shape=(int(shape[0]), int(shape[1])), corners=p, w=w, h=h, cw=cw, ch=ch, rotated=bool(rotated),
+                    frame=(Hr, Wr), canvas=(H, W), dst_w=int(dst_w),
+                    # cv2: inv_scale = (double)dsize / ssize; scale = 1. / inv_scale
+                    sx=1.0 / (float(dst_w) / float(Wr)), sy=1.0 / (float(H) / float(Hr)),
+                    cu1=float(Wr - 1), cv1=float(Hr - 1), h9=m.reshape(9).copy(), crop_map=crop_map)
+
+
+def _quads(items):
+    """One photo's quadrilaterals (K x 4 x 2 array, list or tensor; K may be 0) -> float64 array [K, 4, 2]."""
+    if isinstance(items, torch.Tensor):
+        items = items.detach().cpu().numpy()
+    a = np.asarray(items, dtype=np.float64)
+    if a.size == 0 and a.ndim < 3:
+        return np.zeros((0, 4, 2), dtype=np.float64)
+    if a.ndim != 3 or a.shape[1:] != (4, 2):
+        raise ValueError("QuadCropper takes quadrilaterals: expected K x 4 x 2 points per image, got shape %s" % (a.shape,))
+    return a
+
+
+def _align16(n):
+    return (n + 15) // 16 * 16
+
+
+CropLayout = namedtuple("CropLayout", "M I table_off desc_off index_off quad_off resident plans dropped")
+
+
+class QuadCropper(object):
+    """`ImageCropper` on the GPU (the defaults are its defaults); see the module docstring."""
+
+    def __init__(self, image_size=(64, 512), mode='resize', rectify='min_area_rect', device=None):
+        if mode not in ('resize', 'pad'):
+            raise NotImplementedError("QuadCropper supports the batched modes 'resize' and 'pad' "
+                                      "(keep_size / keep_ratio produce per-sample shapes)")
+        if rectify not in ('min_area_rect', 'quad'):
+            raise ValueError("rectify must be 'min_area_rect' or 'quad', got %r" % (rectify,))
+        self.image_size = (int(image_size[0]), int(image_size[1]))
+        self.mode = mode
+        self.rectify = rectify
+        self.device = torch.device(device if device is not None else "cuda")
+        load()
+        self._staging = {}
+
+    def _pinned(self, key, nbytes):
+        buf = self._staging.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty((max(nbytes, 1),), dtype=torch.uint8)
+            buf = self._staging[key] = buf.pin_memory() if torch.cuda.is_available() else buf
+        return buf
+
+    def pack(self, images, quads, slot=0, plans=None):
+        """Host side: plan every quadrilateral and lay the numpy photos, the photo table, the crop descriptors, the source
+        indices (int32 [M]) and the quads (float64 [M][4][2]) out in ONE pinned staging buffer (per prefetch slot).  Photos that
+        are CUDA tensors are not copied: their table entries are completed by `upload`.  `plans`: ready-made
+        [(photo index, CropPlan)] in the place of the planning (the quads are then recorded as the plans' corners).
+        Returns (pinned uint8 tensor, CropLayout)."""
+        n = len(images)
+        if plans is None and len(quads) != n:
+            raise ValueError("QuadCropper: %d images, %d quad lists" % (n, len(quads)))
+        for im in images:
+            if im.dtype != (torch.uint8 if isinstance(im, torch.Tensor) else np.uint8) or im.ndim != 3 or im.shape[2] != 3:
+                raise TypeError("images must be uint8 HWC with 3 channels (cv2.imread(..., IMREAD_COLOR))")
+            if isinstance(im, torch.Tensor) and not im.is_cuda:
+                raise TypeError("images are numpy arrays (staged and uploaded) or CUDA tensors (used in place)")
+        kept, dropped = [], []
+        if plans is None:
+            for i, q in enumerate(quads):
+                for k, quad in enumerate(_quads(q)):
+                    try:
+                        kept.append((i, plan_crop(images[i].shape, quad, self.image_size, self.mode, self.rectify), quad))
+                    except DegenerateQuad:
+                        dropped.append((i, k))
+        else:
+            kept = [(int(i), plan, plan.corners) for i, plan in plans]
+        for i, plan, _ in kept:
+            if not 0 <= i < n:
+                raise ValueError("QuadCropper: a crop names photo %d of %d" % (i, n))
+            if tuple(plan.canvas) != self.image_size:
+                raise ValueError("QuadCropper: a plan onto %s for a canvas of %s" % (tuple(plan.canvas), self.image_size))
+        M = len(kept)
+        table = (CropImage * max(n, 1))()
+        off, resident = 0, []
+        for i, im in enumerate(images):
+            table[i].h, table[i].w, table[i].reserved = int(im.shape[0]), int(im.shape[1]), 0
+            if isinstance(im, torch.Tensor):
+                if im.stride(2) != 1 or im.stride(1) != 3 or im.stride(0) < 3 * im.shape[1]:
+                    im = im.contiguous()
+                table[i].pitch = int(im.stride(0))
+                resident.append((i, im))                # .offset: relative to the device buffer `upload` allocates
+            else:
+                table[i].offset, table[i].pitch = off, int(im.shape[1]) * 3
+                off += _align16(im.shape[0] * im.shape[1] * 3)
+        descs = (CropDesc * max(M, 1))()
+        for m, (i, plan, _) in enumerate(kept):
+            plan.fill(descs[m], i)
+        table_off = off
+        desc_off = table_off + _align16(ctypes.sizeof(table))
+        index_off = desc_off + _align16(ctypes.sizeof(descs))
+        quad_off = index_off + _align16(4 * M)
+        total = quad_off + _align16(64 * M)
+        buf = self._pinned(slot, total)
+        host = buf.numpy()
+        for i, im in enumerate(images):
+            if not isinstance(im, torch.Tensor):
+                nb = im.shape[0] * im.shape[1] * 3
+                host[table[i].offset:table[i].offset + nb] = np.ascontiguousarray(im).reshape(-1)
+        host[table_off:table_off + ctypes.sizeof(table)] = np.frombuffer(bytes(table), dtype=np.uint8)
+        host[desc_off:desc_off + ctypes.sizeof(descs)] = np.frombuffer(bytes(descs), dtype=np.uint8)
+        host[index_off:index_off + 4 * M].view(np.int32)[:] = [i for i, _, _ in kept]
+        host[quad_off:quad_off + 64 * M].view(np.float64)[:] = \
+            np.asarray([q for _, _, q in kept], dtype=np.float64).reshape(-1)
+        return buf[:total], CropLayout(M, n, table_off, desc_off, index_off, quad_off, resident,
+                                       [plan for _, plan, _ in kept], dropped)
+
+    def upload(self, staged, layout):
+        """One async H2D copy of the staging buffer, then the one launch, on the CURRENT stream (resident photos must be
+        ready on it)."""
+        H, W = self.image_size
+        M = layout.M
+        dbuf = torch.empty((staged.numel(),), dtype=torch.uint8, device=self.device)
+        if layout.resident:
+            table = staged.numpy()[layout.table_off:layout.table_off + layout.I * ctypes.sizeof(CropImage)]
+            offsets = table.view(np.int64).reshape(layout.I, ctypes.sizeof(CropImage) // 8)[:, 0]
+            for i, im in layout.resident:
+                offsets[i] = im.data_ptr() - dbuf.data_ptr()
+        dbuf.copy_(staged, non_blocking=True)
+        image = torch.empty((M, 3, H, W), dtype=torch.float32, device=self.device)
+        call("mr_quad_crop", ptr(dbuf), dbuf.data_ptr() + layout.table_off, layout.I, dbuf.data_ptr() + layout.desc_off, M,
+             H, W, RGB_MEAN[0], RGB_MEAN[1], RGB_MEAN[2], ptr(image))
+        index = dbuf[layout.index_off:layout.index_off + 4 * M].view(torch.int32)
+        quad = dbuf[layout.quad_off:layout.quad_off + 64 * M].view(torch.float64).view(M, 4, 2)
+        return {'image': image, 'index': index, 'quad': quad, 'dropped': list(layout.dropped),
+                '_keepalive': (dbuf, [im for _, im in layout.resident])}
+
+    def crop(self, images, quads):
+        """images: uint8 HWC numpy arrays or uint8 HWC CUDA tensors; quads: one K x 4 x 2 array, list or tensor per image.
+        Returns {'image': f32 [M, 3, H, W], 'index': i32 [M], 'quad': f64 [M, 4, 2], 'dropped': [(image, k)]} in input order."""
+        staged, layout = self.pack(images, quads)
+        return self.upload(staged, layout)

@@ -1,0 +1,111 @@
+"""Read text end to end: photos in, per photo a list of {'quad', 'text'} out.
+
+The reference has the pieces in separate programs -- the DB detector with `SegDetectorRepresenter`
+(structure/representers/seg_detector_representer.py), `ImageCropper` (data/crop_file_dataset.py:85-124) and the recognisers --
+and joins them through files of cropped images.  Here the photo is uploaded once and never leaves the device between the two
+models:
+
+    reader = TextReader(detector, recognizer, charset)
+    for found in reader.read(photos):               # photos: uint8 HWC numpy arrays (cv2.imread(..., IMREAD_COLOR))
+        for item in found:
+            item['quad'], item['text']
+
+  1. `DevicePipeline(det_size, 'resize')` stages and uploads the photos and makes the detector's input from them
+     (`det_size` = the validate `Resize` of experiments/seg_detector/community-base.yaml: 1024 x 576);
+  2. `detector(image)` in eval mode under no_grad, `representer.represent` with the photos' own shapes (boxes in photo pixels);
+  3. `QuadCropper.crop` samples the recognition batch out of the photos still resident in the pipeline's device buffer;
+  4. `recognizer` in chunks of `max_crops`, greedy decoding, `charset.label_to_string`.
+Only the boxes (a few hundred points) and the decoded ids cross to the host."""
+import ctypes
+
+import numpy as np
+import torch
+
+from .data.device_pipeline import DevicePipeline, ImgDesc
+from .data.quad_crop import QuadCropper
+from .ops.decode import ctc_greedy_decode
+from .structure.seg_detector_representer import SegDetectorRepresenter
+
+
+class TextReader(object):
+    def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
+                 rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256):
+        if not (decode in ('ctc', 'ids') or callable(decode)):
+            raise ValueError("decode must be 'ctc', 'ids' or a callable pred -> (ids, lengths), got %r" % (decode,))
+        if int(max_crops) < 1:
+            raise ValueError("max_crops must be at least 1, got %r" % (max_crops,))
+        self.detector = detector
+        self.recognizer = recognizer
+        self.charset = charset
+        self.representer = representer if representer is not None else SegDetectorRepresenter(resize=True)
+        self.decode = decode
+        self.max_crops = int(max_crops)
+        self.det_pipeline = DevicePipeline(image_size=det_size, mode='resize', charset=charset)
+        self.cropper = QuadCropper(image_size=rec_size, mode=rec_mode, rectify=rectify)
+
+    def _upload(self, images):
+        """The detector's input batch and the photos as uint8 HWC views of the device buffer the pipeline uploaded."""
+        staged, layout = self.det_pipeline.pack(images, [''] * len(images))
+        n, desc_off = layout[0], layout[1]
+        descs = (ImgDesc * n).from_buffer_copy(staged.numpy()[desc_off:desc_off + n * ctypes.sizeof(ImgDesc)].tobytes())
+        batch = self.det_pipeline.upload(staged, layout)
+        dbuf = batch['_keepalive']
+        photos = [dbuf[d.offset:d.offset + d.h * d.w * 3].view(d.h, d.w, 3) for d in descs]
+        return batch, photos
+
+    def _ids(self, pred):
+        """(ids [M, S], lengths [M] or None) of one chunk's prediction."""
+        if callable(self.decode):
+            return self.decode(pred)
+        if self.decode == 'ids':
+            return pred, None
+        if isinstance(pred, (tuple, list)):
+            pred = pred[0]
+        return ctc_greedy_decode(pred, blank=getattr(self.charset, 'blank', 0), unknown=getattr(self.charset, 'unknown', 1))
+
+    @staticmethod
+    def _eval(module, x):
+        """module(x) under no_grad, in eval mode for the call (a module that was training is put back)."""
+        was_training = bool(getattr(module, 'training', False))
+        if was_training:
+            module.eval()
+        try:
+            with torch.no_grad():
+                return module(x)
+        finally:
+            if was_training:
+                module.train()
+
+    def recognize(self, crops):
+        """crops: f32 [M, 3, H, W] on the device -> M strings."""
+        texts = []
+        for lo in range(0, crops.shape[0], self.max_crops):
+            ids, lengths = self._ids(self._eval(self.recognizer, crops[lo:lo + self.max_crops]))
+            ids = ids.cpu().numpy()
+            lengths = np.full(len(ids), ids.shape[1]) if lengths is None else lengths.cpu().numpy()
+            texts.extend(self.charset.label_to_string(row[:int(k)]) for row, k in zip(ids, lengths))
+        return texts
+
+    def read(self, images):
+        """images: a list of uint8 HWC numpy arrays.  Returns, per image, a list of {'quad': [[x, y] * 4], 'text': str} in the
+        representer's box order; [] for an image without boxes."""
+        images = list(images)
+        results = [[] for _ in images]
+        if not images:
+            return results
+        batch, photos = self._upload(images)
+        pred = self._eval(self.detector, batch['image'])
+        if not isinstance(pred, dict):
+            pred = {'binary': pred}
+        boxes, _ = self.representer.represent({'image': batch['image'], 'shape': [im.shape[:2] for im in images]}, pred)
+        staged, layout = self.cropper.pack(photos, boxes)
+        if layout.M == 0:
+            return results
+        crops = self.cropper.upload(staged, layout)
+        texts = self.recognize(crops['image'])
+        host = staged.numpy()
+        index = host[layout.index_off:layout.index_off + 4 * layout.M].view(np.int32)
+        quads = host[layout.quad_off:layout.quad_off + 64 * layout.M].view(np.float64).reshape(layout.M, 4, 2)
+        for i, quad, text in zip(index.tolist(), quads.tolist(), texts):       # boxes with a zero side were dropped by the cropper
+            results[i].append({'quad': quad, 'text': text})
+        return results
