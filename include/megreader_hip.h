@@ -582,6 +582,25 @@ int mr_deform_psroi_bwd(const float* out_grad, const float* data, const float* r
 int mr_db_components(const float* prob, float thresh, int* labels, void* points, int* count, int cap, int N, int H, int W,
                      hipStream_t stream);
 int mr_db_box_scores(const float* prob, const float* boxes, float* out, int B, int N, int H, int W, hipStream_t stream);
+/* mr_db_boxes: the whole of `boxes_from_bitmap` for a batch on the device, no host synchronisation; float64 geometry that restates
+ * megreader_amd/structure/db_geometry.py operation for operation (math.hypot of non-integers as sqrt(x*x + y*y)); integer atomics
+ * only, the same bits every run.  prob f32 [N][H][W] is scored, seg f32 [N][H][W] is thresholded (> thresh) into regions (may be
+ * prob); dest i32 [N][2] = (width, height) the boxes of image n are scaled to.  Candidate k of image n = its k-th 8-connected
+ * component in raster order of its first pixel, k < K; components i32 [N] = how many the image has (> K: truncated).
+ * Per candidate: `mini_box` of its pixels, dropped when the short side < min_size; score = sum / count of prob over the
+ * truncated box (the arithmetic of mr_db_box_scores), dropped when box_thresh > score; `unclip` and `mini_box` again, dropped
+ * when the short side < min_size + 2; corners scaled by dest / (W, H), rounded half-even, clamped to [0, dest].
+ * boxes f64 [N][K][4][2] / scores f32 [N][K]: the surviving boxes in candidate order, count i32 [N] of them, zeros behind.
+ * Optional (NULL = not wanted), per candidate slot: cand f64 [N][K][4][2] the ordered rectangle before unclip, cand_sums
+ * f32 [N][K][2] its (sum, count) (zeros when not scored), status i32 [N][K]: 0 no such component, 1 short side < min_size,
+ * 2 below box_thresh, 3 too small after unclip, 4 kept.
+ * ws: *bytes of mr_db_boxes_ws_bytes (labels, rank map, row counts, the table of row extremes i32 [N][K][H][2], uncompacted
+ * results), 16-byte aligned, not initialised.  1 <= K <= 1024; H <= 2048 (a candidate's 2 H hull points are staged in LDS);
+ * H * W < 2^31; MR_ERR_ARG otherwise. */
+int mr_db_boxes_ws_bytes(int N, int H, int W, int K, long long* bytes);
+int mr_db_boxes(const float* prob, const float* seg, float thresh, const int* dest, int N, int H, int W, int K,
+                double box_thresh, double min_size, void* ws, double* boxes, float* scores, int* count, int* components,
+                double* cand, float* cand_sums, int* status, hipStream_t stream);
 
 /* ---- DB detector metrics (concern/icdar2015_eval/detection/iou.py:13-179 `evaluate_image` for quadrilaterals, the
  * evaluator of structure/measurers/quad_measurer.py).  All arithmetic float64.  gt f64 [N][G][4][2] / det f64 [N][D][4][2]

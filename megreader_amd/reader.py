@@ -1,4 +1,5 @@
-"""Read text end to end: photos in, per photo a list of {'quad', 'text'} out.
+"""Read text end to end: photos in, per photo a list of {'quad', 'text'} out (with `scores=True` also 'score', the detector's
+confidence in the box).
 
 The reference has the pieces in separate programs -- the DB detector with `SegDetectorRepresenter`
 (structure/representers/seg_detector_representer.py), `ImageCropper` (data/crop_file_dataset.py:85-124) and the recognisers --
@@ -29,7 +30,7 @@ from .structure.seg_detector_representer import SegDetectorRepresenter
 
 class TextReader(object):
     def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
-                 rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256):
+                 rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False):
         if not (decode in ('ctc', 'ids') or callable(decode)):
             raise ValueError("decode must be 'ctc', 'ids' or a callable pred -> (ids, lengths), got %r" % (decode,))
         if int(max_crops) < 1:
@@ -40,6 +41,7 @@ class TextReader(object):
         self.representer = representer if representer is not None else SegDetectorRepresenter(resize=True)
         self.decode = decode
         self.max_crops = int(max_crops)
+        self.scores = bool(scores)
         self.det_pipeline = DevicePipeline(image_size=det_size, mode='resize', charset=charset)
         self.cropper = QuadCropper(image_size=rec_size, mode=rec_mode, rectify=rectify)
 
@@ -88,7 +90,8 @@ class TextReader(object):
 
     def read(self, images):
         """images: a list of uint8 HWC numpy arrays.  Returns, per image, a list of {'quad': [[x, y] * 4], 'text': str} in the
-        representer's box order; [] for an image without boxes."""
+        representer's box order; [] for an image without boxes.  With `scores=True` every item also has 'score': the mean of the
+        detector's probability map inside the box (`SegDetectorRepresenter.represent_scored`)."""
         images = list(images)
         results = [[] for _ in images]
         if not images:
@@ -97,7 +100,11 @@ class TextReader(object):
         pred = self._eval(self.detector, batch['image'])
         if not isinstance(pred, dict):
             pred = {'binary': pred}
-        boxes, _ = self.representer.represent({'image': batch['image'], 'shape': [im.shape[:2] for im in images]}, pred)
+        det_batch = {'image': batch['image'], 'shape': [im.shape[:2] for im in images]}
+        if self.scores:
+            boxes, box_scores, _ = self.representer.represent_scored(det_batch, pred)
+        else:
+            boxes, _ = self.representer.represent(det_batch, pred)
         staged, layout = self.cropper.pack(photos, boxes)
         if layout.M == 0:
             return results
@@ -108,4 +115,10 @@ class TextReader(object):
         quads = host[layout.quad_off:layout.quad_off + 64 * layout.M].view(np.float64).reshape(layout.M, 4, 2)
         for i, quad, text in zip(index.tolist(), quads.tolist(), texts):       # boxes with a zero side were dropped by the cropper
             results[i].append({'quad': quad, 'text': text})
+        if self.scores:                                                        # ... and so are their scores
+            dropped = set(layout.dropped)
+            for i, found in enumerate(results):
+                kept = [s for k, s in enumerate(box_scores[i]) if (i, k) not in dropped]
+                for item, s in zip(found, kept):
+                    item['score'] = s
         return results

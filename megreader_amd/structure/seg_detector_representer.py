@@ -4,6 +4,10 @@ with the per-pixel stages on the GPU (csrc/db_post.hip: connected components + h
 per-box geometry on the host (db_geometry.py).  Same constructor states, `represent(batch, pred)` contract and box
 format (a list per image of [[x, y] * 4] lists, corners ordered top-left, top-right, bottom-right, bottom-left).
 
+`device_geometry=True` runs the per-box geometry on the GPU as well (`mr_db_boxes`: hull, calipers, score, unclip and scaling
+in one chain of launches that restates db_geometry.py in float64) and copies the finished boxes back once; the lists are the
+same.  `boxes_on_device` is that chain without any copy, `represent_scored` also returns each box's confidence.
+
 Differences, all forced by the build image having neither cv2 nor pyclipper to run the reference against ("parity
 unpinned"; the restatement in oracle/db_post.py is the checker):
   * cv2.findContours(RETR_LIST) also returns the contours of HOLES; here a candidate is an 8-connected component (its
@@ -11,17 +15,21 @@ unpinned"; the restatement in oracle/db_post.py is the checker):
     matters when an image has more than `max_candidates` components.
   * rectangles come from exact float64 calipers (cv2 works in float32), box scores count pixels inside or on the border
     of the integer-truncated box (cv2.fillPoly's scan conversion), unclip is the closed form for rectangles."""
+import ctypes
+
 import numpy as np
 import torch
 
-from .._lib import call, ptr, require_cuda
+from .._lib import call, load, ptr, require_cuda
 from .db_geometry import mini_box, unclip
 
 
 class SegDetectorRepresenter(object):
-    def __init__(self, thresh=0.3, box_thresh=0.7, max_candidates=100, resize=False, dest='binary', cmd={}, **kwargs):
+    def __init__(self, thresh=0.3, box_thresh=0.7, max_candidates=100, resize=False, dest='binary', cmd={},
+                 device_geometry=False, **kwargs):
         self.thresh, self.box_thresh, self.max_candidates = thresh, box_thresh, max_candidates
         self.resize, self.dest = resize, dest
+        self.device_geometry = bool(device_geometry)
         self.min_size = 3
         self.scale_ratio = 0.4
         self.debug = cmd.get('debug', False)
@@ -37,6 +45,14 @@ class SegDetectorRepresenter(object):
         boxes_batch = self.boxes_from_maps(_pred['binary'], pred, shapes)
         return boxes_batch, _pred
 
+    def represent_scored(self, batch, _pred):
+        """`represent` with the confidence of every box (the mean of `binary` inside the box before unclip, the number
+        `box_thresh` is compared with): (boxes_batch, scores_batch, _pred).  Always the device path; ONE device-to-host copy
+        of one packed buffer."""
+        shapes = [tuple(int(v) for v in s) for s in batch['shape']]
+        boxes, scores, _ = self._fetch(self.boxes_on_device(_pred['binary'], _pred[self.dest], shapes))
+        return boxes, scores, _pred
+
     def binarize(self, pred):
         return pred > self.thresh
 
@@ -47,16 +63,59 @@ class SegDetectorRepresenter(object):
                                      bitmap=_bitmap.reshape(1, 1, *_bitmap.shape[-2:]))[0]
         return boxes, _bitmap[0]
 
+    def _maps(self, binary, dest_map, bitmap):
+        """(map that is scored, map that is thresholded, threshold) as contiguous f32 tensors."""
+        prob = binary.detach().float().contiguous()
+        if bitmap is not None:
+            return prob, bitmap.detach().float().contiguous(), 0.5
+        return prob, (prob if dest_map is None else dest_map.detach().float().contiguous()), float(self.thresh)
+
+    def boxes_on_device(self, binary, dest_map, shapes, bitmap=None):
+        """The arguments of `boxes_from_maps`; everything stays on the device and nothing waits for it.  Returns
+        {'boxes': f64 [N, K, 4, 2] the boxes of image n in its first count[n] slots (zeros behind), 'scores': f32 [N, K],
+        'count': i32 [N], 'components': i32 [N] connected components of the image (more than K = max_candidates: the rest was
+        not looked at), 'packed': the uint8 buffer all four are views of}."""
+        require_cuda(binary)
+        prob, seg, thr = self._maps(binary, dest_map, bitmap)
+        N, H, W = prob.shape[0], prob.shape[2], prob.shape[3]
+        K = int(self.max_candidates)
+        nbytes = ctypes.c_longlong(0)
+        if load().mr_db_boxes_ws_bytes(N, H, W, K, ctypes.byref(nbytes)) != 0:
+            raise RuntimeError("mr_db_boxes_ws_bytes failed: %s" % load().mr_last_error().decode())
+        dev = prob.device
+        dest = [(shapes[n][1], shapes[n][0]) if self.resize else (W, H) for n in range(N)]
+        dest = torch.tensor(dest, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+        packed = torch.empty((N * K * 68 + N * 8,), dtype=torch.uint8, device=dev)
+        out = self._views(packed, N, K)
+        call("mr_db_boxes", ptr(prob), ptr(seg), thr, ptr(dest), N, H, W, K, float(self.box_thresh), float(self.min_size),
+             ptr(ws), ptr(out['boxes']), ptr(out['scores']), ptr(out['count']), ptr(out['components']), 0, 0, 0)
+        out['packed'] = packed
+        return out
+
+    @staticmethod
+    def _views(packed, N, K):
+        """The four results as views of one byte buffer: boxes | scores | count | components."""
+        o1, o2, o3 = N * K * 64, N * K * 68, N * K * 68 + N * 4
+        return {'boxes': packed[:o1].view(torch.float64).view(N, K, 4, 2), 'scores': packed[o1:o2].view(torch.float32).view(N, K),
+                'count': packed[o2:o3].view(torch.int32), 'components': packed[o3:].view(torch.int32)}
+
+    def _fetch(self, out):
+        """One copy of the packed results to the host -> (boxes_batch, scores_batch, components per image)."""
+        N, K = out['scores'].shape
+        host = self._views(out['packed'].cpu(), N, K)
+        counts = host['count'].tolist()
+        return ([host['boxes'][n, :counts[n]].tolist() for n in range(N)],
+                [host['scores'][n, :counts[n]].tolist() for n in range(N)], host['components'].tolist())
+
     def boxes_from_maps(self, binary, dest_map, shapes, bitmap=None):
         """binary: the probability map scored for box confidence (N,1,H,W); dest_map: the map that is thresholded into
         regions (defaults to `binary`); bitmap: an already binarised map instead of dest_map."""
         require_cuda(binary)
-        prob = binary.detach().float().contiguous()
-        N, _, H, W = prob.shape
-        if bitmap is not None:
-            seg, thr = bitmap.detach().float().contiguous(), 0.5
-        else:
-            seg, thr = (prob if dest_map is None else dest_map.detach().float().contiguous()), float(self.thresh)
+        if self.device_geometry:
+            return self._fetch(self.boxes_on_device(binary, dest_map, shapes, bitmap=bitmap))[0]
+        prob, seg, thr = self._maps(binary, dest_map, bitmap)
+        N, H, W = prob.shape[0], prob.shape[2], prob.shape[3]
         dev = prob.device
         labels = torch.empty((N, H, W), dtype=torch.int32, device=dev)
         cap = max(4096, N * H * W // 8)
