@@ -875,6 +875,33 @@ int mr_sizeof_crop_desc(void);
 int mr_quad_crop(const unsigned char* src, const void* images /* [I] */, int I, const void* crops /* [M] */, int M,
                  int H, int W, double mean0, double mean1, double mean2, float* dst /* [M][3][H][W] */, hipStream_t stream);
 
+/* ---- Lexicon-constrained reading (csrc/lexicon.hip): the nearest lexicon word of every predicted id sequence, the rule of the
+ * recognition benchmarks that are reported with lexicons (50 words per image, 1 k per set, "full"), and the membership test of
+ * structure/measurers/sequence_recognition_measurer.py:59-64 (`in_lexicon`: distance 0).
+ *   preds: i32 [N, S], S <= MR_SEQ_MEASURE_MAX.  Row n's sequence is its S entries with `blank` and `unknown` dropped, then mapped
+ *     through `fold` (nullable; id -> canonical id, C entries) -- exactly how mr_seq_measure reads a row.  pred_len[n] = m, the
+ *     number of symbols left.
+ *   word l = lex_sym[lex_off[l] .. lex_off[l+1]), 0..MR_LEXICON_MAX_WORD symbols, already folded by the host, no blank.  It may
+ *     hold `unknown`, which matches nothing.  lex_off lives on the device, so the entry point cannot check the word lengths without
+ *     a synchronising copy: the caller guarantees them (megreader_amd/ops/lexicon.py raises on a longer word); the kernel reads at
+ *     most MR_LEXICON_MAX_WORD symbols of a word whatever lex_off says.
+ *   span: nullable i32 [N, 2]: row n's candidates are the words [span[n][0], span[n][1]) (clamped to [0, L]); NULL: [0, L).
+ *     Per-image lexicons laid end to end and one shared lexicon go through the same entry point.
+ *   C: number of classes.  An id outside [0, C) on either side matches nothing and indexes no table.
+ *   best_dist[n] = the smallest Levenshtein distance between row n and a candidate, best_index[n] = the lowest word index that
+ *     reaches it; -1 / -1 for an empty candidate range.  All three outputs are written for every row; nothing has to be zeroed.
+ * Rows of m <= 64 symbols run the bit-parallel recurrence (Myers 1999 / Hyyro) with the prediction as the pattern, one thread per
+ * candidate word, the match masks of the prediction in LDS: a table of C entries up to C = 8192, the <= 64 distinct symbols of the
+ * prediction beyond.  Longer rows swap the roles (the word is the pattern) in the same launch: slow, exact.  The per-row minimum
+ * of (distance << 32 | index) is taken with 64-bit atomics in a key buffer the library owns per device (8 bytes per row, grown
+ * outside stream capture only: under capture, N must not exceed the largest N of an earlier call on that device); calls on one
+ * device must therefore be stream-ordered with each other.  Deterministic.  N == 0 returns MR_OK without a launch; S == 0 reads
+ * no element of preds.  MR_ERR_ARG, nothing written: S above the cap, C < 2, a negative size. */
+#define MR_LEXICON_MAX_WORD 64      /* symbols per lexicon word */
+int mr_lexicon_nearest(const int* preds, int S, int N, int blank, int unknown, const int* fold,
+                       const int* lex_sym, const int* lex_off, int L, const int* span, int C,
+                       int* best_index, int* best_dist, int* pred_len, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,3 +88,17 @@ class ChineseCharset(Charset):
 
 
 DefaultCharset = EnglishCharset
+
+
+def upper_fold_table(charset):
+    """id -> canonical id under `.upper()` of the characters: ids whose characters upper-case to the same character get the id of
+    the first of them, so that comparing folded id sequences is comparing the upper-cased strings (what
+    SequenceRecognitionMeasurer and Lexicon do).  A list of len(charset) ints, or None when the table would be the identity or the
+    object has no `_charset` list to read."""
+    if charset is None or not hasattr(charset, "_charset"):
+        return None
+    canon, fold = {}, []
+    for i, ch in enumerate(charset._charset):
+        key = ch.upper() if isinstance(ch, str) else ("#", i)
+        fold.append(canon.setdefault(key, i))
+    return fold if any(f != i for i, f in enumerate(fold)) else None

@@ -1,5 +1,5 @@
 """Read text end to end: photos in, per photo a list of {'quad', 'text'} out (with `scores=True` also 'score', the detector's
-confidence in the box).
+confidence in the box; with `lexicon=` also 'raw_text' and 'lexicon_distance', and 'text' is the nearest lexicon word).
 
 The reference has the pieces in separate programs -- the DB detector with `SegDetectorRepresenter`
 (structure/representers/seg_detector_representer.py), `ImageCropper` (data/crop_file_dataset.py:85-124) and the recognisers --
@@ -25,12 +25,14 @@ import torch
 from .data.device_pipeline import DevicePipeline, ImgDesc
 from .data.quad_crop import QuadCropper
 from .ops.decode import ctc_greedy_decode
+from .ops.lexicon import Lexicon
 from .structure.seg_detector_representer import SegDetectorRepresenter
 
 
 class TextReader(object):
     def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
-                 rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False):
+                 rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
+                 lexicon_max_distance=None):
         if not (decode in ('ctc', 'ids') or callable(decode)):
             raise ValueError("decode must be 'ctc', 'ids' or a callable pred -> (ids, lengths), got %r" % (decode,))
         if int(max_crops) < 1:
@@ -42,6 +44,10 @@ class TextReader(object):
         self.decode = decode
         self.max_crops = int(max_crops)
         self.scores = bool(scores)
+        if lexicon is not None and not isinstance(lexicon, Lexicon):
+            lexicon = Lexicon(lexicon, charset)
+        self.lexicon = lexicon
+        self.lexicon_max_distance = None if lexicon_max_distance is None else int(lexicon_max_distance)
         self.det_pipeline = DevicePipeline(image_size=det_size, mode='resize', charset=charset)
         self.cropper = QuadCropper(image_size=rec_size, mode=rec_mode, rectify=rectify)
 
@@ -79,19 +85,42 @@ class TextReader(object):
                 module.train()
 
     def recognize(self, crops):
-        """crops: f32 [M, 3, H, W] on the device -> M strings."""
+        """crops: f32 [M, 3, H, W] on the device -> M strings (with a lexicon: the nearest words, see `read`)."""
+        texts = self._recognize(crops)
+        return texts if self.lexicon is None else [t[0] for t in texts]
+
+    def _recognize(self, crops):
+        """M strings; with a lexicon M (text, raw text, distance) triples, the text the nearest lexicon word where its distance
+        is within `lexicon_max_distance`."""
         texts = []
         for lo in range(0, crops.shape[0], self.max_crops):
             ids, lengths = self._ids(self._eval(self.recognizer, crops[lo:lo + self.max_crops]))
+            found = None
+            if self.lexicon is not None:                        # on the device ids, before they are copied
+                rows = ids.to(torch.int32)
+                if lengths is not None:
+                    beyond = torch.arange(rows.shape[1], device=rows.device)[None, :] >= lengths.to(rows.device)[:, None]
+                    rows = rows.masked_fill(beyond, getattr(self.charset, 'blank', 0))
+                found = self.lexicon.nearest(rows)
             ids = ids.cpu().numpy()
             lengths = np.full(len(ids), ids.shape[1]) if lengths is None else lengths.cpu().numpy()
-            texts.extend(self.charset.label_to_string(row[:int(k)]) for row, k in zip(ids, lengths))
+            raw = [self.charset.label_to_string(row[:int(k)]) for row, k in zip(ids, lengths)]
+            if found is None:
+                texts.extend(raw)
+                continue
+            index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
+            for text, i, d in zip(raw, index, distance):
+                near = i >= 0 and (self.lexicon_max_distance is None or d <= self.lexicon_max_distance)
+                texts.append((self.lexicon.words[i] if near else text, text, d))
         return texts
 
     def read(self, images):
         """images: a list of uint8 HWC numpy arrays.  Returns, per image, a list of {'quad': [[x, y] * 4], 'text': str} in the
         representer's box order; [] for an image without boxes.  With `scores=True` every item also has 'score': the mean of the
-        detector's probability map inside the box (`SegDetectorRepresenter.represent_scored`)."""
+        detector's probability map inside the box (`SegDetectorRepresenter.represent_scored`).  With a lexicon (a `Lexicon` or a
+        list of words, encoded with the reader's charset) 'text' is the lexicon word nearest to the greedy string when its edit
+        distance is at most `lexicon_max_distance` (None: always), and every item also has 'raw_text', the greedy string, and
+        'lexicon_distance' (-1 for an empty lexicon)."""
         images = list(images)
         results = [[] for _ in images]
         if not images:
@@ -109,12 +138,15 @@ class TextReader(object):
         if layout.M == 0:
             return results
         crops = self.cropper.upload(staged, layout)
-        texts = self.recognize(crops['image'])
+        texts = self._recognize(crops['image'])
         host = staged.numpy()
         index = host[layout.index_off:layout.index_off + 4 * layout.M].view(np.int32)
         quads = host[layout.quad_off:layout.quad_off + 64 * layout.M].view(np.float64).reshape(layout.M, 4, 2)
         for i, quad, text in zip(index.tolist(), quads.tolist(), texts):       # boxes with a zero side were dropped by the cropper
-            results[i].append({'quad': quad, 'text': text})
+            if self.lexicon is None:
+                results[i].append({'quad': quad, 'text': text})
+            else:
+                results[i].append({'quad': quad, 'text': text[0], 'raw_text': text[1], 'lexicon_distance': text[2]})
         if self.scores:                                                        # ... and so are their scores
             dropped = set(layout.dropped)
             for i, found in enumerate(results):
