@@ -796,20 +796,25 @@ int mr_seq_measure(const int* labels, int S, const int* preds, int S2, int N, in
 /* ---- input pipeline on the GPU ----------------------------------------------------------------
  * mr_resize_normalize: data/processes/resize_image.py:29-38,48-53 (cv2.resize of the float32 image, INTER_LINEAR;
  *   modes "resize" and "pad") fused with data/processes/normalize_image.py:8-17 (-= RGB_MEAN in double, /= 255 in f32,
- *   HWC -> CHW).  src: packed uint8 HWC (3 channel) images; desc: device array of
- *   struct { long long offset; int h, w, pitch, dst_w; double scale_x, scale_y; } (mr_sizeof_img_desc() bytes
- *   each; scale = 1. / ((double)dst / src) as cv2 computes it); dst: f32 [N,3,H,W].
+ *   HWC -> CHW).  src: packed uint8 HWC (3 channel) images; desc: device array of mr_img_desc (mr_sizeof_img_desc()
+ *   bytes each); dst: f32 [N,3,H,W].  The kernel is in csrc/image_sample.hip with mr_warp_normalize and mr_quad_crop, which
+ *   share its normalising store.
  * mr_encode_labels: concern/charsets.py:37-58 + data/processes/make_recognition_label.py:11-24.  codepoints: i32
  *   UTF-32 text of all strings back to back, offsets: i64 [N+1]; table_cp (sorted) / table_id: the charset's
  *   codepoint -> id map (case folding baked in by the host); label: i32 [N, max_size] zero padded,
  *   length: i32 [N] = min(len, max_size). */
+typedef struct mr_img_desc {
+  long long offset;             /* byte offset of the image's first pixel in the packed source buffer */
+  int h, w, pitch, dst_w;       /* rows, columns, bytes per row; columns of the resized image inside the canvas (== W for "resize") */
+  double scale_x, scale_y;      /* cv2: scale = 1. / ((double)dsize / ssize), evaluated by the host (not ssize / dsize, which rounds differently) */
+} mr_img_desc;
 int mr_sizeof_img_desc(void);
 int mr_resize_normalize(const unsigned char* src, const void* desc, int N, int H, int W, double mean0, double mean1,
                         double mean2, float* dst, hipStream_t stream);
 int mr_encode_labels(const int* codepoints, const long long* offsets, int N, int max_size, const int* table_cp,
                      const int* table_id, int ntab, int unknown, int* label, int* length, hipStream_t stream);
 
-/* ---- DB detector augmentation (csrc/db_augment.hip): the image half of data/processes/augment_data.py
+/* ---- DB detector augmentation (csrc/image_sample.hip): the image half of data/processes/augment_data.py
  * (`AugmentDetectionData`: Fliplr, Affine rotate, Resize), data/processes/random_crop_data.py (`RandomCropData`) and
  * data/processes/normalize_image.py in ONE bilinear pass.  The host composes the chain into one affine map per image
  * (megreader_amd/data/detection_augment.py); the kernel samples the decoded uint8 HWC source once along it and writes the
@@ -840,7 +845,7 @@ int mr_sizeof_warp_desc(void);
 int mr_warp_normalize(const unsigned char* src, const void* desc /* [N] */, int N, int H, int W,
                       double mean0, double mean1, double mean2, float* dst /* [N][3][H][W] */, hipStream_t stream);
 
-/* ---- Quad crops (csrc/quad_crop.hip): data/crop_file_dataset.py `ImageCropper.crop` -- getPerspectiveTransform +
+/* ---- Quad crops (csrc/image_sample.hip): data/crop_file_dataset.py `ImageCropper.crop` -- getPerspectiveTransform +
  * warpPerspective of a detected quadrilateral, `ensure_horizontal`, `ResizeImage` (modes "resize" and "pad"), - RGB_MEAN,
  * / 255 -- in ONE bilinear pass from the resident uint8 HWC photos to the recogniser's f32 [M][3][H][W] batch.  The host
  * plans each crop in float64 from shapes and points only (megreader_amd/data/quad_crop.py); many crops read from a few

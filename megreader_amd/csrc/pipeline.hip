@@ -4,9 +4,8 @@
 //   mr_ctc_greedy_decode    structure/representers/ctc_representer.py:20-34      (python double loop per sample, step)
 //   mr_ctc2d_greedy_decode  structure/representers/ctc_representer2d.py:27-51
 //   mr_seq_measure          structure/measurers/sequence_recognition_measurer.py:66-72,101-112 (+ editdistance.eval)
-//   mr_resize_normalize     data/processes/resize_image.py:29-38 (cv2.resize on float32, INTER_LINEAR) +
-//                           data/processes/normalize_image.py:8-17 (-= RGB_MEAN, /= 255, HWC -> CHW)
 //   mr_encode_labels        concern/charsets.py:37-58 (index / string_to_label) + make_recognition_label.py:11-24
+// (mr_resize_normalize, the other half of the input pipeline, is in image_sample.hip with the kernels that share its arithmetic.)
 #include "common.h"
 #include "../../include/megreader_hip.h"
 
@@ -219,66 +218,6 @@ __global__ __launch_bounds__(64) void seq_measure_kernel(const int* labels, int 
   }
 }
 
-struct ImgDesc {        // one source image (uint8, HWC, 3 channels)
-  long long offset;     // byte offset into the packed source buffer
-  int h, w, pitch;      // rows, columns, bytes per row
-  int dst_w;            // columns of the resized image inside the canvas (== canvas width for mode "resize")
-  double scale_x, scale_y;  // cv2: scale = 1. / ((double)dsize / ssize), evaluated by the host (one IEEE division
-                            // sequence for the kernel and its oracle; not ssize / dsize, which rounds differently)
-};
-
-// dst[n, c, y, x] = ((double)resize(src_n)[y, x, c] - mean[c]) -> f32, / 255.f ; canvas columns >= dst_w hold the
-// normalised value of a zero pixel (mode "pad": resize_image.py:48-53 pastes into a zero canvas BEFORE normalising).
-// cv2.resize float32 INTER_LINEAR: fx = (float)((x + 0.5) * scale - 0.5) with scale in double, taps clamped with the
-// weight of the out-of-range tap forced to 0, horizontal pass then vertical pass, plain float mul/add (no fma).
-__global__ __launch_bounds__(256) void resize_normalize_kernel(const unsigned char* src, const ImgDesc* desc, int N,
-                                                               int Hd, int Wd, double m0, double m1, double m2,
-                                                               float* dst) {
-  // bit-exactness against the host arithmetic: every product and sum below is rounded separately (hipcc contracts
-  // a*b + c*d into an fma by default, and HIP's __fmul_rn / __fadd_rn are plain operators that get contracted too)
-#pragma clang fp contract(off)
-  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long per = (long long)Hd * Wd;
-  if (gid >= per * N) return;
-  const int n = (int)(gid / per);
-  const int y = (int)((gid % per) / Wd), x = (int)(gid % Wd);
-  const ImgDesc d = desc[n];
-  float v[3] = {0.f, 0.f, 0.f};
-  if (x < d.dst_w) {
-    const unsigned char* s = src + d.offset;
-    if (d.h == Hd && d.w == d.dst_w) {   // cv2.resize returns a copy when the size already matches
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = (float)s[(long long)y * d.pitch + 3 * x + c];
-    } else {
-      const double sx_scale = d.scale_x, sy_scale = d.scale_y;
-      float fx = (float)((x + 0.5) * sx_scale - 0.5);   // rounded product, then rounded sum (contraction is off)
-      int sx = (int)floorf(fx);
-      fx -= sx;
-      if (sx < 0) { sx = 0; fx = 0.f; }
-      if (sx >= d.w - 1) { sx = d.w - 1; fx = 0.f; }
-      float fy = (float)((y + 0.5) * sy_scale - 0.5);
-      int sy = (int)floorf(fy);
-      fy -= sy;
-      if (sy < 0) { sy = 0; fy = 0.f; }
-      if (sy >= d.h - 1) { sy = d.h - 1; fy = 0.f; }
-      const int sx1 = min(sx + 1, d.w - 1), sy1 = min(sy + 1, d.h - 1);
-      const float a0 = 1.f - fx, a1 = fx, b0 = 1.f - fy, b1 = fy;
-      const unsigned char* r0 = s + (long long)sy * d.pitch;
-      const unsigned char* r1 = s + (long long)sy1 * d.pitch;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float top = (float)r0[3 * sx + c] * a0 + (float)r0[3 * sx1 + c] * a1;
-        const float bot = (float)r1[3 * sx + c] * a0 + (float)r1[3 * sx1 + c] * a1;
-        v[c] = top * b0 + bot * b1;
-      }
-    }
-  }
-  const double mean[3] = {m0, m1, m2};
-  float* o = dst + (long long)n * 3 * per + (long long)y * Wd + x;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) o[c * per] = (float)((double)v[c] - mean[c]) / 255.f;
-}
-
 // label[n, p] = id of codepoint cp[off[n] + p] (binary search in the sorted table; missing -> unknown), 0 beyond the
 // string; length[n] = min(len, max_size).  charsets.py:52-58 + make_recognition_label.py:21-24.
 __global__ __launch_bounds__(256) void encode_labels_kernel(const int* cps, const long long* offs, int N, int max_size,
@@ -309,8 +248,6 @@ __global__ __launch_bounds__(256) void encode_labels_kernel(const int* cps, cons
 using namespace mr;
 
 extern "C" {
-
-int mr_sizeof_img_desc(void) { return (int)sizeof(ImgDesc); }
 
 int mr_ctc_greedy_decode(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T,
                          int blank, int unknown, int* out, int* out_len, hipStream_t stream) {
@@ -353,17 +290,6 @@ int mr_seq_measure(const int* labels, int S, const int* preds, int S2, int N, in
   const size_t lds = ((size_t)S + 2 * (size_t)S2) * sizeof(int);   // a_s[S], b_s[S2], row[S2]: <= 48 KiB at the cap
   hipLaunchKernelGGL(seq_measure_kernel, dim3(N), dim3(64), lds, stream, labels, S, preds, S2, N, blank, unknown, fold,
                      acc, ed, label_len, score);
-  MR_CHECK_LAUNCH();
-  return MR_OK;
-}
-
-int mr_resize_normalize(const unsigned char* src, const void* desc, int N, int H, int W, double mean0, double mean1,
-                        double mean2, float* dst, hipStream_t stream) {
-  MR_CHECK_ARG(N >= 0 && H > 0 && W > 0, "mr_resize_normalize: bad shape N=%d H=%d W=%d", N, H, W);
-  if (N == 0) return MR_OK;
-  const long long total = (long long)N * H * W;
-  hipLaunchKernelGGL(resize_normalize_kernel, dim3((unsigned)cdivll(total, 256)), dim3(256), 0, stream, src,
-                     (const ImgDesc*)desc, N, H, W, mean0, mean1, mean2, dst);
   MR_CHECK_LAUNCH();
   return MR_OK;
 }

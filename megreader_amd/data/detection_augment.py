@@ -8,7 +8,7 @@ The reference augments every sample in its DataLoader workers (experiments/seg_d
 resampling the image three times.  None of the decisions looks at a pixel: the flip, the angle, the scale and the crop
 rectangle depend on the image shape and the polygons only (`crop_area` reads `img.shape` and the polygon boxes).  So the
 chain collapses to a plan -- a few drawn numbers, one affine map for the polygon points (source -> canvas) and one inverse
-affine map (canvas -> source) along which `mr_warp_normalize` (csrc/db_augment.hip) samples the decoded source once and
+affine map (canvas -> source) along which `mr_warp_normalize` (csrc/image_sample.hip) samples the decoded source once and
 writes the normalised canvas:
 
     aug = DetectionAugmenter(size=(640, 640), seed=0)
@@ -57,6 +57,7 @@ import math
 import numpy as np
 
 from .._lib import STRUCTS
+from .staging import as_quads
 
 
 class WarpDesc(ctypes.Structure):
@@ -168,10 +169,8 @@ def source_window(shape, valid, clamp, a):
 
 
 def _quads(polygons):
-    a = np.asarray(polygons, dtype=np.float64)
-    if a.size == 0:
-        return np.zeros((0, 4, 2), dtype=np.float64)
-    return a.reshape(-1, 4, 2)
+    """Any array of 8 K numbers is K quadrilaterals here: reshaped before the shared check, which then never refuses."""
+    return as_quads(np.asarray(polygons, dtype=np.float64).reshape(-1, 4, 2), "DetectionAugmenter takes")
 
 
 class DetectionAugmenter(object):

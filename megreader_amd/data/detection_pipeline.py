@@ -33,35 +33,17 @@ Parity unpinned: pyclipper, shapely and cv2 are not dependencies
 Only quadrilaterals are supported (`validate_polygons` and the size filter index points 0..3).  Augmentation
 (`AugmentDetectionData`, `RandomCropData`) is one more stage of the same pipeline when an `augmenter` is given
 (data/detection_augment.py): the host draws a plan per image from the shape and the quads, uploads only the part of the raw
-photo the plan can touch, and `mr_warp_normalize` (csrc/db_augment.hip) takes the place of `mr_resize_normalize`.
+photo the plan can touch, and `mr_warp_normalize` (csrc/image_sample.hip) takes the place of `mr_resize_normalize`.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from .._lib import call, load, ptr
 from .detection_augment import WarpDesc
 from .device_pipeline import RGB_MEAN, ImgDesc
+from .staging import Sections, Staging, as_quads, check_images, upload
 
 MAX_POLYGONS = 1024     # mr_db_targets: polygon slots per image
-
-
-def _quads(items):
-    """One image's polygons (K x 4 x 2 array, list or tensor; K may be 0) -> float64 array [K, 4, 2]."""
-    if isinstance(items, torch.Tensor):
-        items = items.detach().cpu().numpy()
-    a = np.asarray(items, dtype=np.float64)
-    if a.size == 0 and a.ndim < 3:
-        return np.zeros((0, 4, 2), dtype=np.float64)
-    if a.ndim != 3 or a.shape[1:] != (4, 2):
-        raise ValueError("DetectionPipeline takes quadrilaterals: expected K x 4 x 2 points per image, got shape %s"
-                         % (a.shape,))
-    return a
-
-
-def _align16(n):
-    return (n + 15) // 16 * 16
 
 
 class DetectionPipeline(object):
@@ -77,14 +59,7 @@ class DetectionPipeline(object):
         self.max_polygons = None if max_polygons is None else int(max_polygons)   # None: the batch's largest count
         self.device = torch.device(device if device is not None else "cuda")
         self.augmenter = augmenter      # a DetectionAugmenter: pack() takes raw photos of any size (module docstring)
-        self._staging = {}
-
-    def _pinned(self, key, nbytes):
-        buf = self._staging.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty((max(nbytes, 1),), dtype=torch.uint8)
-            buf = self._staging[key] = buf.pin_memory() if torch.cuda.is_available() else buf
-        return buf
+        self._staging = Staging()
 
     def pack(self, images, polygons, ignore_tags, slot=0, plans=None):
         """Host side: lay the uint8 HWC images (already of `image_size`), their descriptors, the quads padded to G slots
@@ -97,16 +72,14 @@ class DetectionPipeline(object):
         H, W = self.image_size
         if len(polygons) != n or len(ignore_tags) != n:
             raise ValueError("DetectionPipeline: %d images, %d polygon lists, %d tag lists" % (n, len(polygons), len(ignore_tags)))
-        quads = [_quads(p) for p in polygons]
+        quads = [as_quads(p, "DetectionPipeline takes") for p in polygons]
         tags = [np.asarray(t).astype(bool).reshape(-1) for t in ignore_tags]
         for q, t in zip(quads, tags):
             if len(q) != len(t):
                 raise ValueError("DetectionPipeline: %d polygons with %d ignore tags" % (len(q), len(t)))
+        check_images(images)
         warp = self.augmenter is not None or plans is not None
         if warp:
-            for im in images:
-                if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                    raise TypeError("images must be uint8 HWC with 3 channels (cv2.imread(..., IMREAD_COLOR))")
             if plans is None:
                 plans = [self.augmenter.sample(im.shape, q, t) for im, q, t in zip(images, quads, tags)]
             if len(plans) != n:
@@ -115,56 +88,45 @@ class DetectionPipeline(object):
                 if tuple(plan.canvas) != (H, W) or tuple(plan.shape) != im.shape[:2]:
                     raise ValueError("DetectionPipeline: a plan from %s onto %s for an image of %s and a canvas of %s"
                                      % (tuple(plan.shape), tuple(plan.canvas), im.shape[:2], (H, W)))
-            quads = [_quads(plan.polygons) for plan in plans]
+            quads = [as_quads(plan.polygons, "DetectionPipeline takes") for plan in plans]
             tags = [np.asarray(plan.ignore_tags).astype(bool).reshape(-1) for plan in plans]
         most = max([len(q) for q in quads] or [0])
         G = most if self.max_polygons is None else self.max_polygons
         if most > G or G > MAX_POLYGONS:
             raise ValueError("DetectionPipeline: %d polygons in one image exceed the %d slots" % (most, min(G, MAX_POLYGONS)))
         descs = ((WarpDesc if warp else ImgDesc) * n)()
-        off = 0
-        for i, im in enumerate(() if warp else images):
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise TypeError("images must be uint8 HWC with 3 channels (cv2.imread(..., IMREAD_COLOR))")
-            if im.shape[:2] != (H, W):
-                raise ValueError("DetectionPipeline takes images already cropped to %s, got %s" % ((H, W), im.shape[:2]))
-            descs[i].offset, descs[i].h, descs[i].w, descs[i].pitch, descs[i].dst_w = off, H, W, W * 3, W
-            descs[i].scale_x = descs[i].scale_y = 1.0
-            off += _align16(H * W * 3)
-        for i, plan in enumerate(plans if warp else ()):
-            plan.fill(descs[i], off)
-            off += _align16(plan.window[2] * plan.window[3] * 3)
-        desc_off = off
-        poly_off = desc_off + _align16(ctypes.sizeof(descs))
-        count_off = poly_off + _align16(n * G * 64)
-        tag_off = count_off + _align16(n * 4)
-        total = tag_off + _align16(n * G * 4)
-        buf = self._pinned(slot, total)
-        host = buf.numpy()
-        for i, im in enumerate(images):
+        if warp:                                        # only each plan's source window is uploaded
+            pixels = [im[y:y + h, x:x + w] for im, (x, y, w, h) in zip(images, (plan.window for plan in plans))]
+        else:
+            pixels = list(images)
+            for im in images:
+                if im.shape[:2] != (H, W):
+                    raise ValueError("DetectionPipeline takes images already cropped to %s, got %s" % ((H, W), im.shape[:2]))
+        lay = Sections(pixels + [descs, n * G * 64, n * 4, n * G * 4], pad_end=True)
+        for i, off in enumerate(lay.offsets[:n]):
             if warp:
-                x, y, w, h = plans[i].window
-                host[descs[i].offset:descs[i].offset + h * w * 3].reshape(h, w, 3)[...] = im[y:y + h, x:x + w]
+                plans[i].fill(descs[i], off)
             else:
-                host[descs[i].offset:descs[i].offset + H * W * 3] = np.ascontiguousarray(im).reshape(-1)
-        host[desc_off:desc_off + ctypes.sizeof(descs)] = np.frombuffer(bytes(descs), dtype=np.uint8)
-        host[poly_off:total] = 0
-        pv = host[poly_off:poly_off + n * G * 64].view(np.float64).reshape(n, G, 4, 2)
-        cv = host[count_off:count_off + n * 4].view(np.int32)
-        tv = host[tag_off:tag_off + n * G * 4].view(np.int32).reshape(n, G)
+                descs[i].offset, descs[i].h, descs[i].w, descs[i].pitch, descs[i].dst_w = off, H, W, W * 3, W
+                descs[i].scale_x = descs[i].scale_y = 1.0
+        desc_off, poly_off, count_off, tag_off = lay.offsets[n:]
+        staged, views = self._staging.stage(slot, lay)
+        staged.numpy()[poly_off:] = 0                   # the empty polygon slots and the padding between the sections
+        pv = views[n + 1].view(np.float64).reshape(n, G, 4, 2)
+        cv = views[n + 2].view(np.int32)
+        tv = views[n + 3].view(np.int32).reshape(n, G)
         for i, (q, t) in enumerate(zip(quads, tags)):
             pv[i, :len(q)] = q
             cv[i] = len(q)
             tv[i, :len(t)] = t
-        return buf[:total], (n, G, desc_off, poly_off, count_off, tag_off) + (('warp',) if warp else ())
+        return staged, (n, G, desc_off, poly_off, count_off, tag_off) + (('warp',) if warp else ())
 
     def upload(self, staged, layout):
         """One async H2D copy of the staging buffer, then the two kernels' launches, on the CURRENT stream."""
         n, G, desc_off, poly_off, count_off, tag_off = layout[:6]
         H, W = self.image_size
         dev = self.device
-        dbuf = torch.empty((staged.numel(),), dtype=torch.uint8, device=dev)
-        dbuf.copy_(staged, non_blocking=True)
+        dbuf = upload(staged, dev)
         image = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
         call("mr_warp_normalize" if layout[6:] == ('warp',) else "mr_resize_normalize", ptr(dbuf), dbuf.data_ptr() + desc_off,
              n, H, W, RGB_MEAN[0], RGB_MEAN[1], RGB_MEAN[2], ptr(image))

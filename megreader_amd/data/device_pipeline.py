@@ -11,7 +11,7 @@ Here the host only hands over the DECODED uint8 pixels (4x fewer bytes than the 
         step.copy_inputs(batch['image'], batch['label'], batch['length']); loss = step()
 
 `process()` = one pinned staging copy (async, side stream) + mr_resize_normalize + mr_encode_labels.
-Resize arithmetic follows cv2's float32 INTER_LINEAR path (csrc/pipeline.hip); cv2 itself is not available in the build
+Resize arithmetic follows cv2's float32 INTER_LINEAR path (csrc/image_sample.hip); cv2 itself is not available in the build
 image, so that one piece is checked against the numpy restatement in oracle/pipeline.py ("parity unpinned").
 """
 import ctypes
@@ -19,16 +19,16 @@ import ctypes
 import numpy as np
 import torch
 
-from .._lib import call, load, ptr
+from .._lib import STRUCTS, call, load, ptr
 from ..charsets import EnglishCharset
+from .staging import Sections, Staging, check_images, upload
 
 RGB_MEAN = (122.67891434, 116.66876762, 104.00698793)   # data/processes/normalize_image.py:9 (applied to BGR as is)
 
 
 class ImgDesc(ctypes.Structure):
-    """struct ImgDesc of csrc/pipeline.hip."""
-    _fields_ = [("offset", ctypes.c_longlong), ("h", ctypes.c_int), ("w", ctypes.c_int), ("pitch", ctypes.c_int),
-                ("dst_w", ctypes.c_int), ("scale_x", ctypes.c_double), ("scale_y", ctypes.c_double)]
+    """struct mr_img_desc of include/megreader_hip.h."""
+    _fields_ = STRUCTS["mr_img_desc"]
 
 
 _FOLDS_TO = None
@@ -102,57 +102,36 @@ class DevicePipeline(object):
         self.tab_cp = torch.from_numpy(cps).to(self.device)
         self.tab_id = torch.from_numpy(ids).to(self.device)
         self.unknown = getattr(self.charset, "unknown", 1)
-        self._staging = {}
-
-    def _pinned(self, key, nbytes):
-        buf = self._staging.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = self._staging[key] = torch.empty((max(nbytes, 1),), dtype=torch.uint8).pin_memory()
-        return buf
+        self._staging = Staging()
 
     def pack(self, images, texts, slot=0):
         """Host side: lay the decoded uint8 HWC images, their descriptors and the UTF-32 text out in ONE pinned
-        staging buffer (per prefetch slot).  Returns (pinned uint8 tensor, layout tuple)."""
+        staging buffer (per prefetch slot).  Returns (pinned uint8 tensor, layout tuple); the layout's last element is the
+        `ImgDesc` array that was staged (`photos` reads it)."""
         n = len(images)
         H, W = self.image_size
+        check_images(images)
         descs = (ImgDesc * n)()
-        off = 0
-        for i, im in enumerate(images):
-            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-                raise TypeError("images must be uint8 HWC with 3 channels (cv2.imread(..., IMREAD_COLOR))")
-            descs[i].offset, descs[i].h, descs[i].w, descs[i].pitch = off, im.shape[0], im.shape[1], im.shape[1] * 3
-            descs[i].dst_w = W if self.mode == 'resize' else target_width('pad', self.image_size, im.shape)
+        for d, im in zip(descs, images):
+            d.h, d.w, d.pitch = im.shape[0], im.shape[1], im.shape[1] * 3
+            d.dst_w = W if self.mode == 'resize' else target_width('pad', self.image_size, im.shape)
             # cv2: inv_scale = (double)dsize / ssize; scale = 1. / inv_scale
-            descs[i].scale_x = 1.0 / (float(descs[i].dst_w) / float(im.shape[1]))
-            descs[i].scale_y = 1.0 / (float(H) / float(im.shape[0]))
-            off += (im.shape[0] * im.shape[1] * 3 + 15) // 16 * 16
-        pix_bytes = off
-        desc_off = pix_bytes
-        desc_bytes = (ctypes.sizeof(ImgDesc) * n + 15) // 16 * 16
+            d.scale_x = 1.0 / (float(d.dst_w) / float(im.shape[1]))
+            d.scale_y = 1.0 / (float(H) / float(im.shape[0]))
         cp = [np.frombuffer(t.encode('utf-32-le'), dtype=np.int32) for t in texts]
         offs = np.zeros(n + 1, dtype=np.int64)
         offs[1:] = np.cumsum([len(c) for c in cp])
-        text_off = desc_off + desc_bytes
-        text_bytes = (int(offs[-1]) * 4 + 15) // 16 * 16
-        offs_off = text_off + text_bytes
-        total = offs_off + 8 * (n + 1)
-        buf = self._pinned(slot, total)
-        host = buf.numpy()
-        for i, im in enumerate(images):
-            nb = im.shape[0] * im.shape[1] * 3
-            host[descs[i].offset:descs[i].offset + nb] = np.ascontiguousarray(im).reshape(-1)
-        host[desc_off:desc_off + ctypes.sizeof(ImgDesc) * n] = np.frombuffer(bytes(descs), dtype=np.uint8)
-        if int(offs[-1]):
-            host[text_off:text_off + int(offs[-1]) * 4] = np.concatenate(cp).view(np.uint8)
-        host[offs_off:offs_off + 8 * (n + 1)] = offs.view(np.uint8)
-        return buf[:total], (n, desc_off, text_off, offs_off)
+        lay = Sections(list(images) + [descs, np.concatenate(cp + [np.zeros(0, dtype=np.int32)]), offs])
+        for d, off in zip(descs, lay.offsets):
+            d.offset = off
+        staged, _ = self._staging.stage(slot, lay)
+        return staged, (n,) + tuple(lay.offsets[n:]) + (descs,)
 
     def upload(self, staged, layout):
         """One async H2D copy of the staging buffer, then the two kernels, on the CURRENT stream."""
-        n, desc_off, text_off, offs_off = layout
+        n, desc_off, text_off, offs_off = layout[:4]
         H, W = self.image_size
-        dbuf = torch.empty((staged.numel(),), dtype=torch.uint8, device=self.device)
-        dbuf.copy_(staged, non_blocking=True)
+        dbuf = upload(staged, self.device)
         image = torch.empty((n, 3, H, W), dtype=torch.float32, device=self.device)
         call("mr_resize_normalize", ptr(dbuf), dbuf.data_ptr() + desc_off, n, H, W, RGB_MEAN[0], RGB_MEAN[1],
              RGB_MEAN[2], ptr(image))
@@ -161,6 +140,12 @@ class DevicePipeline(object):
         call("mr_encode_labels", dbuf.data_ptr() + text_off, dbuf.data_ptr() + offs_off, n, self.max_size,
              ptr(self.tab_cp), ptr(self.tab_id), self.tab_cp.numel(), int(self.unknown), ptr(label), ptr(length))
         return {'image': image, 'label': label, 'length': length, '_keepalive': dbuf}
+
+    @staticmethod
+    def photos(batch, layout):
+        """The uploaded photos as uint8 HWC views of the device buffer `upload` filled (batch: what it returned)."""
+        dbuf = batch['_keepalive']
+        return [dbuf[d.offset:d.offset + d.h * d.w * 3].view(d.h, d.w, 3) for d in layout[4]]
 
     def process(self, images, texts):
         staged, layout = self.pack(images, texts)

@@ -10,7 +10,7 @@ The reference does it per text line on the host (data/crop_file_dataset.py:105-1
     image = ResizeImage(image_size, mode)(image);  image -= RGB_MEAN;  image /= 255.
 
 None of these decisions reads a pixel.  `plan_crop` composes them, in float64, into one projective map from the (rotated)
-crop frame to the photo plus cv2.resize's sampling rule, and `mr_quad_crop` (csrc/quad_crop.hip, arithmetic in
+crop frame to the photo plus cv2.resize's sampling rule, and `mr_quad_crop` (csrc/image_sample.hip, arithmetic in
 include/megreader_hip.h) samples the raw uint8 photo once along it and writes the normalised batch:
 
     cropper = QuadCropper(image_size=(32, 128))
@@ -50,6 +50,7 @@ import torch
 from .._lib import STRUCTS, call, load, ptr
 from ..structure.db_geometry import min_area_rect
 from .device_pipeline import RGB_MEAN, target_width
+from .staging import Sections, Staging, as_quads, check_images, upload
 
 
 class CropImage(ctypes.Structure):
@@ -181,22 +182,6 @@ def plan_crop(shape, quad, image_size=(64, 512), mode='resize', rectify='min_are
                     cu1=float(Wr - 1), cv1=float(Hr - 1), h9=m.reshape(9).copy(), crop_map=crop_map)
 
 
-def _quads(items):
-    """One photo's quadrilaterals (K x 4 x 2 array, list or tensor; K may be 0) -> float64 array [K, 4, 2]."""
-    if isinstance(items, torch.Tensor):
-        items = items.detach().cpu().numpy()
-    a = np.asarray(items, dtype=np.float64)
-    if a.size == 0 and a.ndim < 3:
-        return np.zeros((0, 4, 2), dtype=np.float64)
-    if a.ndim != 3 or a.shape[1:] != (4, 2):
-        raise ValueError("QuadCropper takes quadrilaterals: expected K x 4 x 2 points per image, got shape %s" % (a.shape,))
-    return a
-
-
-def _align16(n):
-    return (n + 15) // 16 * 16
-
-
 CropLayout = namedtuple("CropLayout", "M I table_off desc_off index_off quad_off resident plans dropped")
 
 
@@ -214,14 +199,7 @@ class QuadCropper(object):
         self.rectify = rectify
         self.device = torch.device(device if device is not None else "cuda")
         load()
-        self._staging = {}
-
-    def _pinned(self, key, nbytes):
-        buf = self._staging.get(key)
-        if buf is None or buf.numel() < nbytes:
-            buf = torch.empty((max(nbytes, 1),), dtype=torch.uint8)
-            buf = self._staging[key] = buf.pin_memory() if torch.cuda.is_available() else buf
-        return buf
+        self._staging = Staging()
 
     def pack(self, images, quads, slot=0, plans=None):
         """Host side: plan every quadrilateral and lay the numpy photos, the photo table, the crop descriptors, the source
@@ -232,15 +210,14 @@ class QuadCropper(object):
         n = len(images)
         if plans is None and len(quads) != n:
             raise ValueError("QuadCropper: %d images, %d quad lists" % (n, len(quads)))
+        check_images(images, tensors=True)
         for im in images:
-            if im.dtype != (torch.uint8 if isinstance(im, torch.Tensor) else np.uint8) or im.ndim != 3 or im.shape[2] != 3:
-                raise TypeError("images must be uint8 HWC with 3 channels (cv2.imread(..., IMREAD_COLOR))")
             if isinstance(im, torch.Tensor) and not im.is_cuda:
                 raise TypeError("images are numpy arrays (staged and uploaded) or CUDA tensors (used in place)")
         kept, dropped = [], []
         if plans is None:
             for i, q in enumerate(quads):
-                for k, quad in enumerate(_quads(q)):
+                for k, quad in enumerate(as_quads(q, "QuadCropper takes")):
                     try:
                         kept.append((i, plan_crop(images[i].shape, quad, self.image_size, self.mode, self.rectify), quad))
                     except DegenerateQuad:
@@ -254,7 +231,7 @@ class QuadCropper(object):
                 raise ValueError("QuadCropper: a plan onto %s for a canvas of %s" % (tuple(plan.canvas), self.image_size))
         M = len(kept)
         table = (CropImage * max(n, 1))()
-        off, resident = 0, []
+        staged_photos, resident = [], []
         for i, im in enumerate(images):
             table[i].h, table[i].w, table[i].reserved = int(im.shape[0]), int(im.shape[1]), 0
             if isinstance(im, torch.Tensor):
@@ -263,42 +240,33 @@ class QuadCropper(object):
                 table[i].pitch = int(im.stride(0))
                 resident.append((i, im))                # .offset: relative to the device buffer `upload` allocates
             else:
-                table[i].offset, table[i].pitch = off, int(im.shape[1]) * 3
-                off += _align16(im.shape[0] * im.shape[1] * 3)
+                table[i].pitch = int(im.shape[1]) * 3
+                staged_photos.append((i, im))
         descs = (CropDesc * max(M, 1))()
         for m, (i, plan, _) in enumerate(kept):
             plan.fill(descs[m], i)
-        table_off = off
-        desc_off = table_off + _align16(ctypes.sizeof(table))
-        index_off = desc_off + _align16(ctypes.sizeof(descs))
-        quad_off = index_off + _align16(4 * M)
-        total = quad_off + _align16(64 * M)
-        buf = self._pinned(slot, total)
-        host = buf.numpy()
-        for i, im in enumerate(images):
-            if not isinstance(im, torch.Tensor):
-                nb = im.shape[0] * im.shape[1] * 3
-                host[table[i].offset:table[i].offset + nb] = np.ascontiguousarray(im).reshape(-1)
-        host[table_off:table_off + ctypes.sizeof(table)] = np.frombuffer(bytes(table), dtype=np.uint8)
-        host[desc_off:desc_off + ctypes.sizeof(descs)] = np.frombuffer(bytes(descs), dtype=np.uint8)
-        host[index_off:index_off + 4 * M].view(np.int32)[:] = [i for i, _, _ in kept]
-        host[quad_off:quad_off + 64 * M].view(np.float64)[:] = \
-            np.asarray([q for _, _, q in kept], dtype=np.float64).reshape(-1)
-        return buf[:total], CropLayout(M, n, table_off, desc_off, index_off, quad_off, resident,
-                                       [plan for _, plan, _ in kept], dropped)
+        lay = Sections([im for _, im in staged_photos] + [
+            table, descs, np.array([i for i, _, _ in kept], dtype=np.int32),
+            np.asarray([q for _, _, q in kept], dtype=np.float64).reshape(-1)], pad_end=True)
+        for (i, _), off in zip(staged_photos, lay.offsets):
+            table[i].offset = off
+        staged, _ = self._staging.stage(slot, lay)
+        table_off, desc_off, index_off, quad_off = lay.offsets[len(staged_photos):]
+        return staged, CropLayout(M, n, table_off, desc_off, index_off, quad_off, resident,
+                                  [plan for _, plan, _ in kept], dropped)
 
     def upload(self, staged, layout):
         """One async H2D copy of the staging buffer, then the one launch, on the CURRENT stream (resident photos must be
         ready on it)."""
         H, W = self.image_size
         M = layout.M
-        dbuf = torch.empty((staged.numel(),), dtype=torch.uint8, device=self.device)
-        if layout.resident:
+
+        def place_resident(dbuf):
             table = staged.numpy()[layout.table_off:layout.table_off + layout.I * ctypes.sizeof(CropImage)]
             offsets = table.view(np.int64).reshape(layout.I, ctypes.sizeof(CropImage) // 8)[:, 0]
             for i, im in layout.resident:
                 offsets[i] = im.data_ptr() - dbuf.data_ptr()
-        dbuf.copy_(staged, non_blocking=True)
+        dbuf = upload(staged, self.device, place_resident if layout.resident else None)
         image = torch.empty((M, 3, H, W), dtype=torch.float32, device=self.device)
         call("mr_quad_crop", ptr(dbuf), dbuf.data_ptr() + layout.table_off, layout.I, dbuf.data_ptr() + layout.desc_off, M,
              H, W, RGB_MEAN[0], RGB_MEAN[1], RGB_MEAN[2], ptr(image))

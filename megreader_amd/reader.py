@@ -17,12 +17,10 @@ models:
   3. `QuadCropper.crop` samples the recognition batch out of the photos still resident in the pipeline's device buffer;
   4. `recognizer` in chunks of `max_crops`, greedy decoding, `charset.label_to_string`.
 Only the boxes (a few hundred points) and the decoded ids cross to the host."""
-import ctypes
-
 import numpy as np
 import torch
 
-from .data.device_pipeline import DevicePipeline, ImgDesc
+from .data.device_pipeline import DevicePipeline
 from .data.quad_crop import QuadCropper
 from .ops.decode import ctc_greedy_decode
 from .ops.lexicon import Lexicon
@@ -54,12 +52,8 @@ class TextReader(object):
     def _upload(self, images):
         """The detector's input batch and the photos as uint8 HWC views of the device buffer the pipeline uploaded."""
         staged, layout = self.det_pipeline.pack(images, [''] * len(images))
-        n, desc_off = layout[0], layout[1]
-        descs = (ImgDesc * n).from_buffer_copy(staged.numpy()[desc_off:desc_off + n * ctypes.sizeof(ImgDesc)].tobytes())
         batch = self.det_pipeline.upload(staged, layout)
-        dbuf = batch['_keepalive']
-        photos = [dbuf[d.offset:d.offset + d.h * d.w * 3].view(d.h, d.w, 3) for d in descs]
-        return batch, photos
+        return batch, self.det_pipeline.photos(batch, layout)
 
     def _ids(self, pred):
         """(ids [M, S], lengths [M] or None) of one chunk's prediction."""

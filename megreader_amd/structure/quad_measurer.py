@@ -16,21 +16,15 @@ uninitialised 1 x 1 array there."""
 import numpy as np
 import torch
 
+from ..data.staging import as_array, as_quads
 from ..ops.detection_measure import quad_measure
 from .measurers import AverageMeter
 
 
 def _quads(items):
-    """One image's polygons (K x 4 x 2 array, list or tensor; K may be 0) -> float64 array [K, 4, 2]."""
-    if isinstance(items, torch.Tensor):
-        items = items.detach().cpu().numpy()
-    a = np.asarray(items, dtype=np.float64)
-    if a.size == 0:
-        return np.zeros((0, 4, 2), dtype=np.float64)
-    if a.ndim != 3 or a.shape[1:] != (4, 2):
-        raise ValueError("QuadMeasurer measures quadrilaterals: expected K x 4 x 2 points per image, got shape %s"
-                         % (a.shape,))
-    return a
+    """`as_quads`, except that an empty array of ANY shape is no quadrilaterals (the strict rule refuses an empty `(0, 5, 2)`)."""
+    a = as_array(items)
+    return as_quads(a if a.size else (), "QuadMeasurer measures")
 
 
 def _pad(per_image, width):

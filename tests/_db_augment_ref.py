@@ -1,4 +1,4 @@
-"""numpy restatement of `warp_normalize_kernel` (megreader_amd/csrc/db_augment.hip) in the kernel's own operation order:
+"""numpy restatement of `warp_normalize_kernel` (megreader_amd/csrc/image_sample.hip) in the kernel's own operation order:
 float64 coordinates, each product and sum rounded on its own (numpy never contracts), float32 blends, the normalisation of
 `mr_resize_normalize`.  Every operation is an IEEE basic operation, so the device result must equal this one bit for bit.
 Beside the image it reports every tap's source index, so that tests/test_db_augment_cpu.py can check the plan's window."""

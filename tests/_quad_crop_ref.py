@@ -1,4 +1,4 @@
-"""numpy restatements for the quad crops (megreader_amd/data/quad_crop.py, megreader_amd/csrc/quad_crop.hip).
+"""numpy restatements for the quad crops (megreader_amd/data/quad_crop.py, megreader_amd/csrc/image_sample.hip).
 
 `quad_crop_ref` is `quad_crop_kernel` in the kernel's own operation order: float64 coordinates with every product and sum
 rounded on its own (numpy never contracts), two correctly rounded float64 divisions, float32 blends, the normalisation of

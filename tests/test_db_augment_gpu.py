@@ -1,4 +1,4 @@
-"""mr_warp_normalize (csrc/db_augment.hip) against the numpy restatement of tests/_db_augment_ref.py (itself checked on the
+"""mr_warp_normalize (csrc/image_sample.hip) against the numpy restatement of tests/_db_augment_ref.py (itself checked on the
 host in tests/test_db_augment_cpu.py), BIT FOR BIT: every operation of the kernel is an IEEE basic operation with contraction
 off, so a mismatch is a wrong operation order, not a tolerance.  Outputs are pre-filled with NaN: none may survive.  Bytes of
 the source buffer that belong to no window are 255: a read outside a window changes the result."""

@@ -1,4 +1,4 @@
-"""On-device input pipeline (csrc/pipeline.hip, megreader_amd.data.DevicePipeline) against oracle/pipeline.py: resize
+"""On-device input pipeline (csrc/image_sample.hip and csrc/pipeline.hip, megreader_amd.data.DevicePipeline) against oracle/pipeline.py: resize
 (up / down / identity, both modes) + normalise + CHW bit-exact with the numpy restatement of cv2's float32 path, label
 encoding identical to charsets.string_to_label, and the prefetcher delivering batches in order.  Second half: degenerate and
 large source shapes, the copy branch, the padding columns, hand-built descriptors (pitch, offsets) through the C ABI; label
@@ -111,7 +111,11 @@ def test_pipeline_edge_shapes_match_oracle(mode, size):
 def test_resize_normalize_abi_pitch_offsets_and_empty_batch():
     """mr_resize_normalize on a hand-built descriptor array: rows padded to a pitch above 3 * w, images at non-zero 16-byte
     aligned offsets in an order that is not the batch order, every byte that is not a pixel set to 0xA5; and N = 0"""
-    assert ctypes.sizeof(ImgDesc) == _lib.load().mr_sizeof_img_desc()
+    assert ctypes.sizeof(ImgDesc) == 40 == _lib.load().mr_sizeof_img_desc()
+    # written out by hand, independent of any reading of the header (as tests/test_tuning_cpu.py does for mr_tuning)
+    assert [(name, getattr(ImgDesc, name).offset) for name, _ in ImgDesc._fields_] == [
+        ("offset", 0), ("h", 8), ("w", 12), ("pitch", 16), ("dst_w", 20), ("scale_x", 24), ("scale_y", 32)]
+    assert ImgDesc._fields_ == _lib.STRUCTS["mr_img_desc"]
     H, W = 32, 128
     rng = np.random.RandomState(3)
     #          shape     pitch                 offset   dst_w
@@ -152,6 +156,25 @@ def test_resize_normalize_abi_pitch_offsets_and_empty_batch():
     assert tuple(batch['image'].shape) == (0, 3, H, W) and tuple(batch['label'].shape) == (0, 32)
     assert tuple(batch['length'].shape) == (0,)
     torch.cuda.synchronize()
+
+
+def test_pack_bytes_are_the_parents():
+    """The staged byte stream of `DevicePipeline.pack` (mode 'pad', three sizes, one empty text) and its layout: LITERALS recorded
+    from a build of the commit before `pack` moved onto data/staging.py, not from the code under test.  Packed twice into one
+    slot with the buffer set to 0xA5 in between: the bytes between the sections are nobody's (tests/test_staging_cpu.py)."""
+    import hashlib
+    rng = np.random.RandomState(2)
+    images = [rng.randint(0, 256, s + (3,)).astype(np.uint8) for s in ((5, 7), (12, 9), (32, 40))]
+    pipe = DevicePipeline(image_size=(32, 128), mode='pad')
+    staged, _ = pipe.pack(images, ["Ab", "", "xyz9"])
+    staged.fill_(0xA5)
+    staged, layout = pipe.pack(images, ["Ab", "", "xyz9"])
+    assert staged.is_pinned() and staged.numel() == 4480 and tuple(layout[:4]) == (3, 4288, 4416, 4448)
+    assert hashlib.sha256(staged.numpy().tobytes()).hexdigest() == \
+        "1951074ccd5555ad3dc0248cca6a398b4fdd5fcd715c6b76caf17a7fbc937a94"
+    batch = pipe.upload(staged, layout)                                  # ... and the photos come back as views of the upload
+    for im, photo in zip(images, pipe.photos(batch, layout)):
+        assert np.array_equal(photo.cpu().numpy(), im)
 
 
 # ------------------------------------------------------------------------------------------------- label encoding

@@ -1,4 +1,4 @@
-"""mr_quad_crop (csrc/quad_crop.hip) and QuadCropper (data/quad_crop.py) against the numpy restatement of
+"""mr_quad_crop (csrc/image_sample.hip) and QuadCropper (data/quad_crop.py) against the numpy restatement of
 tests/_quad_crop_ref.py (itself checked on the host in tests/test_quad_crop_cpu.py), BIT FOR BIT: every operation of the kernel
 is an IEEE basic operation with contraction off -- the two float64 divisions included, which are correctly rounded on both sides
 -- so a mismatch is a wrong operation, not a tolerance.  Outputs are pre-filled with NaN where the test owns them: none may

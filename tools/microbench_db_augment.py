@@ -1,4 +1,4 @@
-"""Time of one `mr_warp_normalize` call (csrc/db_augment.hip) at the DB detector's training size: a 640 x 640 canvas from
+"""Time of one `mr_warp_normalize` call (csrc/image_sample.hip) at the DB detector's training size: a 640 x 640 canvas from
 1280 x 720 photos, N = 2 (the batch of bench.py's DB workload) and N = 16, for plans at scale 0.5, 1 and 3 with +-10 degrees
 and a flip, and for the identity plan (640 x 640 sources) next to `mr_resize_normalize` at identity on the same canvas.
   python tools/microbench_db_augment.py [--out FILE]

@@ -1,4 +1,4 @@
-"""Time of `QuadCropper.crop` (data/quad_crop.py over csrc/quad_crop.hip) for 256 crops at 32 x 128 out of ONE resident
+"""Time of `QuadCropper.crop` (data/quad_crop.py over csrc/image_sample.hip) for 256 crops at 32 x 128 out of ONE resident
 720 x 1280 photo, next to the two-pass numpy restatement of the reference's `ImageCropper.crop` on the host for the same crops.
   python tools/microbench_quad_crop.py [--out FILE]
 Three figures.  (a) the whole call -- planning on the host, one staging copy of the tables, the launch -- between two device
