@@ -907,6 +907,46 @@ int mr_lexicon_nearest(const int* preds, int S, int N, int blank, int unknown, c
                        const int* lex_sym, const int* lex_off, int L, const int* span, int C,
                        int* best_index, int* best_dist, int* pred_len, hipStream_t stream);
 
+/* ---- Lexicon transcription by CTC likelihood (csrc/lexicon.hip): the lexicon-based transcription of the CRNN paper (Shi et al.,
+ * "An End-to-End Trainable Neural Network for Image-based Sequence Recognition", section 2.3.2): l* = argmax over the lexicon words
+ * l within edit distance delta of the greedy string of p(l | y), the CTC probability of the word summed over all alignments.
+ *   Posterior.  Row n has T columns and C classes; y[t, c] is read from pred + n*sn + c*sc + t*st (element strides; dtype
+ *     MR_DTYPE_F32 or MR_DTYPE_BF16, converted to f32 on load).  With log_probs == 0 (probabilities, the eval head's softmax)
+ *     lp[t, c] = the f32 nearest to log y[t, c] (the log taken in f64 and rounded once; y = 0 gives -inf); otherwise y[t, c]
+ *     itself -- logs rounded that way give the same scores bit for bit as the probabilities they were taken from.  The classes are the folded ones: a caller whose charset
+ *     folds case sums the posterior over each fold class first (megreader_amd/ops/lexicon.py).
+ *   Words, span, C, blank, unknown, fold: as mr_lexicon_nearest; 0 <= blank < C.
+ *   Score.  score(n, l) = log of the sum, over all paths of T classes that collapse to the word (merge repeats, then drop blanks),
+ *     of the product of y[t, path_t], by the alpha recursion over the blank-extended word e (e[2i] = blank, e[2i+1] = symbol i,
+ *     2K + 1 positions) in f32 logs:
+ *       alpha_0(0) = lp[0, blank], alpha_0(1) = lp[0, e[1]], every other position -inf
+ *       alpha_t(s) = lp[t, e[s]] + lse(alpha_{t-1}(s), alpha_{t-1}(s-1), alpha_{t-1}(s-2) if s is odd and e[s] != e[s-2])
+ *       score = lse(alpha_{T-1}(2K), alpha_{T-1}(2K-1));  K = 0: alpha_{T-1}(0), the sum over t of lp[t, blank]
+ *     lse(a, b, ..) = m + log(exp(a - m) + exp(b - m) + ..) with m the greatest term, and -inf when every term is -inf: a zero
+ *     probability flows through without a NaN.  A word that cannot fit -- K + (number of adjacent equal symbol pairs) > T -- and a
+ *     word that holds `unknown` or an id outside [0, C) score -inf without a recursion.  score(n, l) is a function of row n's
+ *     values and the word's symbols alone, bit for bit: not of the word's index, the span, max_distance, N or the launch.
+ *   Candidates.  The words of row n's span; with max_distance >= 0 only those whose Levenshtein distance to the row of `preds` is
+ *     <= max_distance.  preds: i32 [N, S], the greedy ids (mr_ctc_greedy_decode on the same pred; S = T), read exactly as
+ *     mr_lexicon_nearest reads a row: blank / unknown dropped, then `fold`.  max_distance < 0: every word of the span, and no
+ *     distance is taken for the selection.
+ *   Outputs, all written for every row, nothing to be zeroed: best_index[n] the candidate with the greatest score, the lowest
+ *     index among bit-equal scores; best_score[n] (f32) its score; best_dist[n] its edit distance to the row; -1 / -inf / -1 when no
+ *     candidate has a finite score.  pred_len[n] as mr_lexicon_nearest.  n_cand[n] the number of candidates after the distance
+ *     filter, whether or not their score is finite.  all_scores (nullable f32 [N, L]): score(n, l) of every candidate, -inf for
+ *     every other word.
+ * Lane i of a word's lanes holds symbol i and the two positions 2i, 2i+1, one value crosses lanes per column; a wave scores four
+ * words of at most 15 symbols side by side, longer ones one at a time.  A row's [C, T] log-probabilities are staged in LDS when
+ * C * (T | 1) <= 8192 and read from global memory otherwise.  The per-row maximum is taken with 64-bit atomics in the key buffer of mr_lexicon_nearest, so the same rules hold: calls of either entry
+ * point on one device are stream-ordered with each other, and under stream capture N must not exceed the largest N of an earlier
+ * call on that device.  Deterministic.  N == 0 returns MR_OK without a launch.  MR_ERR_ARG, nothing written: T < 1, S above the
+ * cap, C < 2, blank outside [0, C), a negative size; MR_ERR_DTYPE: another dtype code. */
+int mr_lexicon_transcribe(int dtype, const void* pred, long long sn, long long sc, long long st, int T, int log_probs,
+                          const int* preds, int S, int N, int blank, int unknown, const int* fold,
+                          const int* lex_sym, const int* lex_off, int L, const int* span, int C, int max_distance,
+                          int* best_index, float* best_score, int* best_dist, int* pred_len, int* n_cand,
+                          float* all_scores, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,9 @@
-"""Lexicon-constrained reading on the GPU (mr_lexicon_nearest, csrc/lexicon.hip): the nearest lexicon word, by Levenshtein distance,
-of every predicted id sequence.  The recognition benchmarks the reference's YAML files name (IIIT5K, SVT, IC03 / IC13) are reported
+"""Lexicon-constrained reading on the GPU (csrc/lexicon.hip).  Two rules:
+  `Lexicon.nearest` (mr_lexicon_nearest): the nearest lexicon word, by Levenshtein distance, of every predicted id sequence;
+  `Lexicon.transcribe` (mr_lexicon_transcribe): the CRNN paper's lexicon-based transcription (Shi et al., section 2.3.2) for CTC
+  posteriors -- among the words within edit distance delta of the greedy string the one with the greatest CTC probability
+  p(word | y), which is also a per-word confidence.
+  The recognition benchmarks the reference's YAML files name (IIIT5K, SVT, IC03 / IC13) are reported
 with lexicons -- 50 words per image, 1 k words per set, the "full" lexicon of ~90 k words -- and the rule is the same in all of
 them: replace the prediction by the lexicon word with the smallest edit distance.  The reference itself only tests membership
 (structure/measurers/sequence_recognition_measurer.py:59-64), on the host; `Lexicon.contains` is that test on id sequences.
@@ -7,6 +11,8 @@ them: replace the prediction by the lexicon word with the smallest edit distance
     lexicon = Lexicon(words, charset)                       # or Lexicon.from_file(path, charset)
     found = lexicon.nearest(ids)                            # ids: i32 [N, S] on the device (greedy-decode output, blank padded)
     lexicon.strings(found['index']), found['distance']
+    found = lexicon.transcribe(pred, max_distance=2)        # pred: [N, C, 1, T] posteriors of a CTC head, on the device
+    lexicon.strings(found['index']), found['score']         # log p(word | pred); -1 / -inf where no word is possible
 
 Words and predictions are compared as the measurer compares strings: case folded like `Charset.index`, then through the `.upper()`
 canonical-id table (charsets.upper_fold_table).  There is no CPU fallback; the host half (`encode`) needs no GPU."""
@@ -15,6 +21,7 @@ import torch
 
 from .._lib import _DEFINES, call, ptr, require_cuda
 from ..charsets import DefaultCharset, upper_fold_table
+from .decode import ctc_greedy_decode
 
 MAX_WORD = _DEFINES["MR_LEXICON_MAX_WORD"]
 
@@ -102,6 +109,70 @@ class Lexicon(object):
             call("mr_lexicon_nearest", ptr(ids), S, N, int(self.blank), int(self.unknown), ptr(fold), ptr(sym), ptr(off),
                  len(self.words), ptr(spans), int(self.classes), ptr(index), ptr(distance), ptr(length))
         return {'index': index, 'distance': distance, 'length': length}
+
+    def _folded(self, pred, fold, log_probs):
+        """The f32 posterior over the folded alphabet: q[n, k, t] = the sum of pred[n, c, t] over fold[c] == k (log input: the
+        log of the sum of the exponentials, shifted by the column's maximum).  Classes that are nobody's canonical id get 0 / -inf."""
+        index = fold.long()
+        pred = pred.float()
+        if not log_probs:
+            return torch.zeros_like(pred).index_add_(1, index, pred)
+        top = pred.amax(dim=1, keepdim=True)
+        top = torch.where(torch.isfinite(top), top, torch.zeros_like(top))
+        return torch.zeros_like(pred).index_add_(1, index, (pred - top).exp()).log() + top
+
+    def transcribe(self, pred, spans=None, max_distance=None, log_probs=False, all_scores=False):
+        """pred: [N, C, 1, T] or [N, C, T] on the device, any strides, C == len(charset): the class probabilities of a CTC head
+        (the eval head's softmax), or their logs with `log_probs=True`; f32 and bf16 are read as they are, other types through
+        f32.  Row n's candidates are the words of spans[n] (None: every word) within `max_distance` edits of the row's greedy
+        string (None: all of them).  Returns i32 / f32 [N] device tensors: 'index' the candidate with the greatest CTC
+        log-probability (the lowest index among equal scores), 'score' that log-probability, 'distance' the winner's edit distance
+        to the greedy string (-1 / -inf / -1 when no candidate is possible), 'length' the symbols of the greedy string,
+        'candidates' the number of candidates; with `all_scores=True` also 'scores', f32 [N, L]: every candidate's score, -inf
+        elsewhere.  With a case-folding charset the likelihood is taken over the folded alphabet.  Greedy decode, (fold) and one
+        call of mr_lexicon_transcribe; no host work that depends on device data (capturable in a graph after one call outside)."""
+        require_cuda(pred)
+        if pred.dim() == 4:
+            if pred.shape[2] != 1:
+                raise ValueError("pred must be [N, C, 1, T] or [N, C, T], got %s" % (tuple(pred.shape),))
+            pred = pred.select(2, 0)
+        if pred.dim() != 3:
+            raise ValueError("pred must be [N, C, 1, T] or [N, C, T], got %s" % (tuple(pred.shape),))
+        N, C, T = pred.shape
+        if C != self.classes:
+            raise ValueError("pred has %d classes, the lexicon's charset %d" % (C, self.classes))
+        dev = pred.device
+        if self.device is not None and self.device.index is not None and self.device != dev:
+            raise ValueError("pred is on %s, the lexicon was made for %s" % (dev, self.device))
+        if pred.dtype not in (torch.float32, torch.bfloat16):
+            pred = pred.float()
+        sym, off, fold = self._tensors(dev)
+        if spans is not None:
+            spans = spans.to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(spans.shape) != (N, 2):
+                raise ValueError("spans must be [%d, 2], got %s" % (N, tuple(spans.shape)))
+        L = len(self.words)
+        out = {'index': torch.empty((N,), dtype=torch.int32, device=dev),
+               'score': torch.empty((N,), dtype=torch.float32, device=dev),
+               'distance': torch.empty((N,), dtype=torch.int32, device=dev),
+               'length': torch.empty((N,), dtype=torch.int32, device=dev),
+               'candidates': torch.empty((N,), dtype=torch.int32, device=dev)}
+        if all_scores:
+            out['scores'] = torch.empty((N, L), dtype=torch.float32, device=dev)
+        if N == 0:
+            return out
+        if T < 1:
+            raise ValueError("pred has no columns: %s" % (tuple(pred.shape),))
+        with torch.cuda.device(dev):
+            ids, _ = ctc_greedy_decode(pred, blank=self.blank, unknown=self.unknown)
+            if fold is not None:
+                pred = self._folded(pred, fold, log_probs)
+            sn, sc, st = pred.stride()
+            call("mr_lexicon_transcribe", 0 if pred.dtype == torch.float32 else 1, ptr(pred), sn, sc, st, T, int(bool(log_probs)),
+                 ptr(ids), T, N, int(self.blank), int(self.unknown), ptr(fold), ptr(sym), ptr(off), L, ptr(spans), C,
+                 -1 if max_distance is None else int(max_distance), ptr(out['index']), ptr(out['score']), ptr(out['distance']),
+                 ptr(out['length']), ptr(out['candidates']), ptr(out.get('scores')) if all_scores and L else 0)
+        return out
 
     def contains(self, ids, spans=None):
         """bool [N] on the device: the row, read as the measurer reads a label, is a word of the lexicon."""

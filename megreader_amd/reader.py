@@ -1,5 +1,6 @@
 """Read text end to end: photos in, per photo a list of {'quad', 'text'} out (with `scores=True` also 'score', the detector's
-confidence in the box; with `lexicon=` also 'raw_text' and 'lexicon_distance', and 'text' is the nearest lexicon word).
+confidence in the box; with `lexicon=` also 'raw_text' and 'lexicon_distance', and 'text' is the nearest lexicon word, or with
+`lexicon_rule='likelihood'` the word with the greatest CTC probability, its log-probability in 'lexicon_score').
 
 The reference has the pieces in separate programs -- the DB detector with `SegDetectorRepresenter`
 (structure/representers/seg_detector_representer.py), `ImageCropper` (data/crop_file_dataset.py:85-124) and the recognisers --
@@ -30,7 +31,11 @@ from .structure.seg_detector_representer import SegDetectorRepresenter
 class TextReader(object):
     def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
                  rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
-                 lexicon_max_distance=None):
+                 lexicon_max_distance=None, lexicon_rule='nearest'):
+        if lexicon_rule not in ('nearest', 'likelihood'):
+            raise ValueError("lexicon_rule must be 'nearest' or 'likelihood', got %r" % (lexicon_rule,))
+        if lexicon_rule == 'likelihood' and decode != 'ctc':
+            raise ValueError("lexicon_rule='likelihood' scores CTC posteriors: it needs decode='ctc', got %r" % (decode,))
         if not (decode in ('ctc', 'ids') or callable(decode)):
             raise ValueError("decode must be 'ctc', 'ids' or a callable pred -> (ids, lengths), got %r" % (decode,))
         if int(max_crops) < 1:
@@ -46,6 +51,7 @@ class TextReader(object):
             lexicon = Lexicon(lexicon, charset)
         self.lexicon = lexicon
         self.lexicon_max_distance = None if lexicon_max_distance is None else int(lexicon_max_distance)
+        self.lexicon_rule = lexicon_rule
         self.det_pipeline = DevicePipeline(image_size=det_size, mode='resize', charset=charset)
         self.cropper = QuadCropper(image_size=rec_size, mode=rec_mode, rectify=rectify)
 
@@ -85,12 +91,18 @@ class TextReader(object):
 
     def _recognize(self, crops):
         """M strings; with a lexicon M (text, raw text, distance) triples, the text the nearest lexicon word where its distance
-        is within `lexicon_max_distance`."""
+        is within `lexicon_max_distance`; with the likelihood rule (text, raw text, distance, score), the text the most probable
+        word among those within `lexicon_max_distance` of the greedy string."""
         texts = []
+        likelihood = self.lexicon is not None and self.lexicon_rule == 'likelihood'
         for lo in range(0, crops.shape[0], self.max_crops):
-            ids, lengths = self._ids(self._eval(self.recognizer, crops[lo:lo + self.max_crops]))
+            pred = self._eval(self.recognizer, crops[lo:lo + self.max_crops])
+            ids, lengths = self._ids(pred)
             found = None
-            if self.lexicon is not None:                        # on the device ids, before they are copied
+            if likelihood:                                      # on the device posterior
+                found = self.lexicon.transcribe(pred[0] if isinstance(pred, (tuple, list)) else pred,
+                                                max_distance=self.lexicon_max_distance)
+            elif self.lexicon is not None:                      # on the device ids, before they are copied
                 rows = ids.to(torch.int32)
                 if lengths is not None:
                     beyond = torch.arange(rows.shape[1], device=rows.device)[None, :] >= lengths.to(rows.device)[:, None]
@@ -101,6 +113,11 @@ class TextReader(object):
             raw = [self.charset.label_to_string(row[:int(k)]) for row, k in zip(ids, lengths)]
             if found is None:
                 texts.extend(raw)
+                continue
+            if likelihood:
+                index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
+                for text, i, d, score in zip(raw, index, distance, found['score'].cpu().tolist()):
+                    texts.append((self.lexicon.words[i] if i >= 0 else text, text, d, score))
                 continue
             index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
             for text, i, d in zip(raw, index, distance):
@@ -114,7 +131,11 @@ class TextReader(object):
         detector's probability map inside the box (`SegDetectorRepresenter.represent_scored`).  With a lexicon (a `Lexicon` or a
         list of words, encoded with the reader's charset) 'text' is the lexicon word nearest to the greedy string when its edit
         distance is at most `lexicon_max_distance` (None: always), and every item also has 'raw_text', the greedy string, and
-        'lexicon_distance' (-1 for an empty lexicon)."""
+        'lexicon_distance' (-1 for an empty lexicon).  With `lexicon_rule='likelihood'` (CTC recognisers, `decode='ctc'`) 'text' is
+        instead the word with the greatest CTC probability under the recogniser's posterior among the words within
+        `lexicon_max_distance` edits of the greedy string (None: the whole lexicon), 'lexicon_distance' that word's distance, and
+        every item also has 'lexicon_score', log p(word | posterior); where no word is possible the greedy string is kept with
+        -1 and -inf."""
         images = list(images)
         results = [[] for _ in images]
         if not images:
@@ -141,6 +162,8 @@ class TextReader(object):
                 results[i].append({'quad': quad, 'text': text})
             else:
                 results[i].append({'quad': quad, 'text': text[0], 'raw_text': text[1], 'lexicon_distance': text[2]})
+                if len(text) > 3:
+                    results[i][-1]['lexicon_score'] = text[3]
         if self.scores:                                                        # ... and so are their scores
             dropped = set(layout.dropped)
             for i, found in enumerate(results):
