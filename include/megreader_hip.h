@@ -947,6 +947,55 @@ int mr_lexicon_transcribe(int dtype, const void* pred, long long sn, long long s
                           int* best_index, float* best_score, int* best_dist, int* pred_len, int* n_cand,
                           float* all_scores, hipStream_t stream);
 
+/* ---- CTC prefix beam search (csrc/ctc_beam.hip): the most probable STRINGS of a CTC posterior with their log-probabilities, where
+ * mr_ctc_greedy_decode gives the most probable path (Graves; Hannun et al., "First-pass large vocabulary continuous speech
+ * recognition using bi-directional recurrent DNNs", Algorithm 1, without the language model).  Two columns `blank 0.6 / A 0.4`:
+ * the best path spells "" (0.36), the string "A" has probability 0.64.
+ *   Posterior.  Row n has T columns and C classes; lp[t, c] is defined exactly as for mr_lexicon_transcribe: y[t, c] read from
+ *     pred + n*sn + c*sc + t*st (element strides; MR_DTYPE_F32 or MR_DTYPE_BF16, converted to f32 on load); with log_probs == 0
+ *     lp[t, c] = the f32 nearest to log y[t, c] (the log taken in f64 and rounded once; y = 0 gives -inf), otherwise y[t, c] itself.
+ *   Parameters.  beam B in 1..MR_CTC_BEAM_MAX; nbest K in 1..B; top_classes Kc in 1..MR_CTC_BEAM_TOP_MAX; blank in [0, C);
+ *     unknown: any int, outside [0, C) means "there is none".
+ *   Hypotheses.  A hypothesis is a prefix: a tuple of class ids with neither blank nor `unknown`.  It carries two f32 log masses:
+ *     pb, the alignments that end in blank, and pnb, those that end in its last symbol; total = lse(pb, pnb).  The start state is
+ *     the empty prefix with pb = 0, pnb = -inf.  lse(a, b) = m + log(exp(a - m) + exp(b - m)) with m the greater term, and -inf
+ *     when both are -inf: a zero probability flows through without a NaN.  `+=` below is lse; every right-hand side is the value
+ *     from before column t.  Per column t:
+ *       1. Symbols of the column: the min(Kc, eligible) classes with the greatest lp[t, c] among c != blank, c != unknown,
+ *          lp[t, c] > -inf; among bit-equal values the lower id wins.  `unknown` is never emitted and its mass is lost, as in
+ *          mr_lexicon_transcribe, where a word that holds `unknown` matches nothing.
+ *       2. Stay.  For every prefix p of the beam: pb'(p) += total(p) + lp[t, blank]; if p is not empty, pnb'(p) += pnb(p) +
+ *          lp[t, last(p)] -- always, whether or not last(p) is among the column's symbols (it is read from the posterior itself).
+ *       3. Extend.  For every prefix p and column symbol c: pnb'(p + c) += (pb(p) if c == last(p) else total(p)) + lp[t, c].
+ *       4. Merge.  Contributions to the same prefix are added, and sameness is by CONTENT: an extension p + c that spells a prefix
+ *          already in the beam joins that prefix's stay masses, also when p had left the beam and came back meanwhile.
+ *       5. Keep.  The B prefixes with the greatest total survive; a prefix whose total is -inf is dropped, so the beam may hold
+ *          fewer than B, or none.
+ *   Outputs.  After the last column the K greatest by total, in descending order: ids i32 [N, K, T] blank padded, lengths i32
+ *     [N, K], scores f32 [N, K] (the totals), count i32 [N] = the number of hypotheses returned, 0..K.  Slots past count get length
+ *     0, score -inf and all blank; the empty string is a legitimate hypothesis (length 0, a finite score).  Every output is written
+ *     for every row, nothing has to be zeroed.  The order among bit-equal totals is unspecified (step 5 and the output), the
+ *     result is deterministic all the same: a function of the row's values and the parameters alone, bit for bit, not of N, the
+ *     row's position or the launch.
+ *   What follows.  With Kc >= the eligible classes and B >= the number of distinct labelings nothing is pruned and the scores are
+ *     the exact log p(string | y) of EVERY string (to f32 rounding); otherwise every score is a LOWER BOUND of its string's
+ *     log p(string | y): the pruned alignments are missing.
+ *   Workspace.  The caller passes ws of at least mr_ctc_beam_ws_bytes(N, T, beam, top_classes) bytes, 8-byte aligned, contents
+ *     arbitrary: the column lists (id, lp) [N, T, Kc] and, per row, the trie of its prefixes (an open-addressing table keyed by the
+ *     exact pair (parent node, symbol), 2 * T * beam + 64 entries of 8 bytes).  The query is host only, works without a GPU and
+ *     returns 0 for arguments the entry point refuses -- a workspace above INT_MAX bytes among them: split the batch.  The call
+ *     allocates nothing, does not synchronise and does no host work that depends on device data: two launches on `stream`
+ *     (one wave per column, then one wave per row), capturable in a graph.
+ * N == 0 returns MR_OK without a launch.  MR_ERR_ARG, nothing written: T < 1 or above MR_SEQ_MEASURE_MAX, C < 2, blank outside
+ * [0, C), beam / nbest / top_classes out of range, a workspace that is too small, misaligned or null, a negative size;
+ * MR_ERR_DTYPE: another dtype code. */
+#define MR_CTC_BEAM_MAX 64          /* hypotheses kept per row */
+#define MR_CTC_BEAM_TOP_MAX 64      /* symbols considered per column */
+int mr_ctc_beam_ws_bytes(int N, int T, int beam, int top_classes);  /* host only */
+int mr_ctc_beam_search(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T,
+                       int log_probs, int blank, int unknown, int beam, int nbest, int top_classes,
+                       int* ids, int* lengths, float* scores, int* count, void* ws, long long ws_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ structure/measurers/sequence_recognition_measurer.py:66-112).  Same rules, bit-e
 (tests/test_decode_gpu.py against oracle/decode.py, which is pinned to the reference)."""
 import torch
 
-from .._lib import call, ptr, require_cuda
+from .._lib import _DEFINES, call, load, ptr, require_cuda
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float64: 2}
 
@@ -26,6 +26,58 @@ def ctc_greedy_decode(pred, blank=0, unknown=1):
     call("mr_ctc_greedy_decode", _DT[pred.dtype], ptr(pred), sn, sc, st, N, C, T, int(blank), int(unknown), ptr(out),
          ptr(lengths))
     return out, lengths
+
+
+def ctc_beam_search_decode(pred, beam=8, nbest=1, top_classes=16, blank=0, unknown=1, log_probs=False):
+    """CTC prefix beam search (mr_ctc_beam_search, include/megreader_hip.h): the `nbest` most probable STRINGS of every row with
+    their log-probabilities, where `ctc_greedy_decode` returns the most probable path.  pred: [N, C, 1, T] or [N, C, T] on the GPU,
+    any strides; probabilities (the eval head's softmax) or, with log_probs=True, their logs; f32 and bf16 are read as they are,
+    other types go through f32.  Decoding is over the classes as given (no case folding: sum the posterior first, as
+    `Lexicon` does).  `beam` hypotheses survive a column (1..64), each column offers its `top_classes` best symbols (1..64).
+    Returns a dict of device tensors: ids i32 [N, nbest, T] blank padded, lengths i32 [N, nbest], scores f32 [N, nbest]
+    (descending; a lower bound of log p(string | pred), exact when nothing was pruned), count i32 [N] (hypotheses returned; slots
+    past it: length 0, score -inf).  One call, no host work that depends on device data (capturable in a graph after one call
+    outside); the workspace is a fresh tensor per call."""
+    if pred.dim() == 4:
+        if pred.shape[2] != 1:
+            raise RuntimeError("ctc_beam_search_decode expects [N, C, 1, T]")
+        pred = pred.select(2, 0)
+    if pred.dim() != 3:
+        raise RuntimeError("ctc_beam_search_decode expects [N, C, 1, T] or [N, C, T], got %d dimensions" % pred.dim())
+    N, C, T = pred.shape
+    defines = _DEFINES
+    beam, nbest, top_classes, blank = int(beam), int(nbest), int(top_classes), int(blank)
+    if not 1 <= beam <= defines["MR_CTC_BEAM_MAX"]:
+        raise ValueError("ctc_beam_search_decode: beam must be in 1..%d, got %d" % (defines["MR_CTC_BEAM_MAX"], beam))
+    if not 1 <= nbest <= beam:
+        raise ValueError("ctc_beam_search_decode: nbest must be in 1..beam=%d, got %d" % (beam, nbest))
+    if not 1 <= top_classes <= defines["MR_CTC_BEAM_TOP_MAX"]:
+        raise ValueError("ctc_beam_search_decode: top_classes must be in 1..%d, got %d"
+                         % (defines["MR_CTC_BEAM_TOP_MAX"], top_classes))
+    if C < 2 or not 0 <= blank < C:
+        raise ValueError("ctc_beam_search_decode: blank=%d is not one of C=%d classes (C >= 2)" % (blank, C))
+    if not 1 <= T <= defines["MR_SEQ_MEASURE_MAX"]:
+        raise ValueError("ctc_beam_search_decode: T=%d columns, 1..%d are taken" % (T, defines["MR_SEQ_MEASURE_MAX"]))
+    require_cuda(pred)
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        pred = pred.float()
+    dev = pred.device
+    ids = torch.empty((N, nbest, T), dtype=torch.int32, device=dev)
+    lengths = torch.empty((N, nbest), dtype=torch.int32, device=dev)
+    scores = torch.empty((N, nbest), dtype=torch.float32, device=dev)
+    count = torch.empty((N,), dtype=torch.int32, device=dev)
+    out = {'ids': ids, 'lengths': lengths, 'scores': scores, 'count': count}
+    if N == 0:
+        return out
+    nbytes = load().mr_ctc_beam_ws_bytes(N, T, beam, top_classes)
+    if nbytes <= 0:
+        raise ValueError("ctc_beam_search_decode: N=%d T=%d beam=%d top_classes=%d need a workspace above 2 GiB; split the batch"
+                         % (N, T, beam, top_classes))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    sn, sc, st = pred.stride()
+    call("mr_ctc_beam_search", 0 if pred.dtype == torch.float32 else 1, ptr(pred), sn, sc, st, N, C, T, int(bool(log_probs)),
+         blank, int(unknown), beam, nbest, top_classes, ptr(ids), ptr(lengths), ptr(scores), ptr(count), ptr(ws), ws.numel() * 8)
+    return out
 
 
 def ctc2d_greedy_decode(classify, mask, blank=0, unknown=1):
