@@ -996,6 +996,52 @@ int mr_ctc_beam_search(int dtype, const void* pred, long long sn, long long sc, 
                        int log_probs, int blank, int unknown, int beam, int nbest, int top_classes,
                        int* ids, int* lengths, float* scores, int* count, void* ws, long long ws_bytes, hipStream_t stream);
 
+/* ---- Forced CTC alignment (csrc/ctc_align.hip): WHERE the symbols of a given string lie in a CTC posterior and how probable each
+ * is there -- the single most probable alignment of the string (Viterbi), where mr_lexicon_transcribe sums over all of them.  It
+ * answers what neither a lexicon word nor a beam hypothesis can: which columns carry which character (character boxes, per-
+ * character confidence).
+ *   Posterior.  Row n has T columns and C classes; lp[t, c] is defined exactly as for mr_lexicon_transcribe: y[t, c] read from
+ *     pred + n*sn + c*sc + t*st (element strides; MR_DTYPE_F32 or MR_DTYPE_BF16, converted to f32 on load); with log_probs == 0
+ *     lp[t, c] = the f32 nearest to log y[t, c] (the log taken in f64 and rounded once; y = 0 gives -inf), otherwise y[t, c] itself.
+ *   Target.  targets: i32 [N, S], S in 0..MR_CTC_ALIGN_MAX_SYMBOLS; target_len: i32 [N], on the device, not nullable.  Row n's
+ *     string is targets[n, 0 .. K) with K = target_len[n]; entries past K are not read.  The classes are taken as given (a caller
+ *     whose charset folds case folds the posterior first, as megreader_amd/ops/lexicon.py does).  The row is UNALIGNABLE when K is
+ *     outside [0, S], when a symbol equals `blank` or `unknown` or lies outside [0, C), or when the string cannot fit:
+ *     K + (number of adjacent equal symbol pairs) > T.
+ *   Recursion, over the blank-extended string e (e[2i] = blank, e[2i+1] = symbol i, 2K + 1 positions), in f32:
+ *       d_0(0) = lp[0, blank], d_0(1) = lp[0, e[1]], every other position -inf
+ *       d_t(s) = lp[t, e[s]] + max(d_{t-1}(s), d_{t-1}(s-1), d_{t-1}(s-2) if s is odd and e[s] != e[s-2])
+ *     one f32 addition per cell, nothing fused; -inf flows through and no NaN appears.  The back-pointer of a cell is the
+ *     predecessor that supplied the maximum; among equal candidates (all -inf included) the smallest step wins: s before s-1
+ *     before s-2.  End position: 0 when K == 0; otherwise 2K if d_{T-1}(2K) >= d_{T-1}(2K-1), else 2K-1.  score[n] (f32) is d_{T-1}
+ *     at the end position: the log-probability of the best alignment.
+ *   Outputs, all written for every row, nothing to be zeroed.  pos i32 [N, T]: the position of every column on the path traced back
+ *     from the end position.  For symbol i < K: begin[n, i] / end[n, i] (i32 [N, S]) the first column and one past the last column
+ *     with pos == 2i + 1 (one run by construction, never empty); sym_lp[n, i] (f32 [N, S]) the sum of lp[t, symbol i] over those
+ *     columns, added in ascending t starting from the first term; peak[n, i] (i32 [N, S]) the column of the run with the greatest
+ *     lp, the lowest t among equal values.  Slots i >= K: begin = end = peak = -1, sym_lp = -inf.  An unalignable row, and a row
+ *     whose score is -inf (the string is reachable only through zero-probability cells): score = -inf, every pos = -1, every slot
+ *     filled as a slot past K.  A row's outputs are a function of that row's values and its target alone, bit for bit: not of N, S,
+ *     the row's index or the launch.
+ *   Workspace.  The caller passes ws of at least mr_ctc_align_ws_bytes(N, T, S) bytes, 8-byte aligned, contents arbitrary: the
+ *     back-pointers, 4 bits per (column, symbol).  The query is host only, works without a GPU and returns 0 for arguments the entry
+ *     point refuses and for a size above INT_MAX (split the batch).  The call allocates nothing, does not synchronise and does no
+ *     host work that depends on device data: one launch on `stream`, capturable in a graph.
+ * One wave per row.  Lane i holds symbol i and the positions 2i, 2i + 1 in registers (strings of 64 symbols and more: the symbols
+ * i, i + 64, .. in further register slots), ONE value crosses lanes per column and slot; the blank after the last symbol sits with
+ * "symbol" K.  Only the K + 1 classes the string names are read, and their logs taken, whatever C is.  A lane keeps its own
+ * back-pointers (in LDS when the row's fit 16 KiB, else in the workspace) and later reads only those back, so the back-trace
+ * loads whole columns ahead of the path it walks.
+ * N == 0 returns MR_OK without a launch; S == 0 reads no element of targets.  MR_ERR_ARG, nothing written: S outside
+ * 0..MR_CTC_ALIGN_MAX_SYMBOLS, T < 1 or above MR_SEQ_MEASURE_MAX, C < 2, blank outside [0, C), a negative size, a workspace that is
+ * too small, misaligned or null; MR_ERR_DTYPE: another dtype code. */
+#define MR_CTC_ALIGN_MAX_SYMBOLS 256  /* symbols per target string */
+int mr_ctc_align_ws_bytes(int N, int T, int S);  /* host only */
+int mr_ctc_align(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T, int log_probs,
+                 int blank, int unknown, const int* targets, int S, const int* target_len,
+                 float* score, int* pos, int* begin, int* end, float* sym_lp, int* peak,
+                 void* ws, long long ws_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

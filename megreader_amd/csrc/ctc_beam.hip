@@ -22,6 +22,7 @@
 // on the probing order and never reach an output.  The strings are unwound once at the end.
 #include <limits.h>
 #include "device.h"
+#include "ctc_posterior.h"
 #include "../../include/megreader_hip.h"
 
 namespace mr {
@@ -45,8 +46,7 @@ __device__ __forceinline__ float ctcb_lse2(float a, float b) {
 // lp[t, c] as the header defines it: the value itself, or the f32 nearest to the f64 log of the probability
 template <typename PT>
 __device__ __forceinline__ float ctcb_lp(const PT* col, long long sc, int c, bool log_probs) {
-  const float v = to_f32(col[(long long)c * sc]);
-  return log_probs ? v : (float)log((double)v);
+  return ctc_lp(to_f32(col[(long long)c * sc]), log_probs);
 }
 
 __device__ __forceinline__ unsigned ctcb_ordered(float x) {
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64) void ctc_beam_columns_kernel(const PT* pred, lo
     for (int u = 0; u < CTCB_AHEAD; ++u) {
       const int c = c0 + 64 * u;
       if (c < C) {
-        const float lp = log_probs ? v[u] : (float)log((double)v[u]);
+        const float lp = ctc_lp(v[u], log_probs != 0);
         if (staged) ctcb_col[c] = lp;
         const u64 k = (c != blank && c != unknown) ? ctcb_key(lp, (unsigned)c) : 0ull;
         mine = k > mine ? k : mine;

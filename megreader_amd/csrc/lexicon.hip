@@ -30,6 +30,7 @@
 #include <limits.h>
 #include <mutex>
 #include "device.h"
+#include "ctc_posterior.h"
 #include "../../include/megreader_hip.h"
 
 namespace mr {
@@ -232,10 +233,6 @@ __device__ __forceinline__ float lex_lse3(float a, float b, float c) {
   return m == LEX_NEG_INF ? m : r;
 }
 
-// The log of a probability as the header defines it: taken in f64 and rounded once, the f32 nearest to log y whichever library
-// computes it -- so a caller who passes such logs gets the same bits.  (logf is within 1 ulp, not the nearest.)
-__device__ __forceinline__ float lex_log(float y) { return (float)log((double)y); }
-
 // lane i <- lane i - 1 (DPP wave_shr:1, no LDS); the first lane of a word's group (gl == 0) <- -inf
 __device__ __forceinline__ float lex_from_lane_below(float v, int gl) {
   const int got = __builtin_amdgcn_update_dpp(__float_as_int(LEX_NEG_INF), __float_as_int(v), 0x138, 0xf, 0xf, false);
@@ -294,8 +291,8 @@ __device__ float lex_ctc_score(const PT* row, long long sc, long long st, int T,
     if (!lpt) lb = lane < nt ? to_f32(pb[(long long)(t0 + lane) * st]) : 1.f;
     if (!lpt && !log_probs) {
 #pragma unroll
-      for (int j = 0; j < LEX_AHEAD; ++j) v[j] = lex_log(v[j]);
-      lb = lex_log(lb);
+      for (int j = 0; j < LEX_AHEAD; ++j) v[j] = ctc_log_prob(v[j]);
+      lb = ctc_log_prob(lb);
     }
 #pragma unroll
     for (int j = 0; j < LEX_AHEAD; ++j) {
@@ -414,7 +411,7 @@ __global__ __launch_bounds__(256) void lexicon_transcribe_kernel(const PT* pred,
     for (int i = tid; i < C * T; i += LEX_BLOCK) {
       const int c = i / T, t = i - c * T;
       const float v = to_f32(row[(long long)c * sc + (long long)t * st]);
-      lpt[c * pitch + t] = log_probs ? v : lex_log(v);
+      lpt[c * pitch + t] = log_probs ? v : ctc_log_prob(v);
     }
   }
   int nd;

@@ -152,6 +152,24 @@ class CropPlan(object):
             desc.h[k] = float(self.h9[k])
         return desc
 
+    def canvas_to_photo(self, points):
+        """Continuous canvas coordinates (U, V), points [..., 2] with pixel u covering [u, u + 1), to photo coordinates (x, y),
+        float64 [..., 2]: the sampling rule of mr_quad_crop (include/megreader_hip.h) continued beyond the pixel centres and
+        without its clamp -- cx = U sx - 0.5, cy = V sy - 0.5, then `h9` with the division by D.  At a pixel centre
+        (u + 0.5, v + 0.5) it is the (x, y) that pixel is sampled at wherever the clamp is inactive; the rectangle
+        [0, dst_w] x [0, H] is the outline of the (rotated) frame, [-0.5, Wr - 0.5] x [-0.5, Hr - 0.5].  The rotation of a vertical
+        crop is inside `h9`: boxes on the canvas come out rotated with it."""
+        pts = np.asarray(points, dtype=np.float64)
+        if pts.shape[-1:] != (2,):
+            raise ValueError("canvas_to_photo takes points [..., 2], got %s" % (pts.shape,))
+        cx = pts[..., 0] * self.sx - 0.5
+        cy = pts[..., 1] * self.sy - 0.5
+        h = [float(v) for v in self.h9]
+        X = h[0] * cx + h[1] * cy + h[2]
+        Y = h[3] * cx + h[4] * cy + h[5]
+        D = h[6] * cx + h[7] * cy + h[8]
+        return np.stack([X / D, Y / D], axis=-1)
+
 
 def plan_crop(shape, quad, image_size=(64, 512), mode='resize', rectify='min_area_rect'):
     """The plan of one quadrilateral `quad` [4, 2] (any point set for 'min_area_rect') of a photo of `shape` (H, W[, C]) onto a

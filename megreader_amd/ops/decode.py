@@ -80,6 +80,67 @@ def ctc_beam_search_decode(pred, beam=8, nbest=1, top_classes=16, blank=0, unkno
     return out
 
 
+def ctc_forced_align(pred, targets, target_lengths, blank=0, unknown=1, log_probs=False):
+    """Forced CTC alignment (mr_ctc_align, include/megreader_hip.h): WHERE the symbols of a given string lie in the posterior -- the
+    single most probable alignment of row n's string targets[n, :target_lengths[n]], traced back.  pred: [N, C, 1, T] or [N, C, T]
+    on the GPU, any strides; probabilities (the eval head's softmax) or, with log_probs=True, their logs; f32 and bf16 are read as
+    they are, other types go through f32.  targets: i32 [N, S] and target_lengths: i32 [N], on the device (S up to 256); the
+    classes are taken as given (no case folding: sum the posterior first, as `Lexicon` does).  Returns a dict of device tensors:
+    score f32 [N], the log-probability of the best alignment; pos i32 [N, T], the position of every column in the blank-extended
+    string (2i + 1: symbol i, even: a blank); begin, end i32 [N, S], the columns [begin, end) of symbol i; sym_lp f32 [N, S], the
+    sum of the symbol's log-probabilities over them; peak i32 [N, S], its most probable column.  Slots past the string: -1, -1,
+    -inf, -1.  A row that cannot be aligned (a symbol that is blank, `unknown` or no class, a length outside [0, S], more symbols
+    than columns) or only through zero probabilities: score -inf, pos -1, every slot as one past the string.  One call, no host
+    work that depends on device data (capturable in a graph); the workspace is a fresh tensor per call."""
+    if pred.dim() == 4:
+        if pred.shape[2] != 1:
+            raise RuntimeError("ctc_forced_align expects [N, C, 1, T]")
+        pred = pred.select(2, 0)
+    if pred.dim() != 3:
+        raise RuntimeError("ctc_forced_align expects [N, C, 1, T] or [N, C, T], got %d dimensions" % pred.dim())
+    N, C, T = pred.shape
+    defines = _DEFINES
+    blank = int(blank)
+    if targets.dim() != 2 or targets.shape[0] != N:
+        raise ValueError("ctc_forced_align: targets must be [N=%d, S], got %s" % (N, tuple(targets.shape)))
+    if tuple(target_lengths.shape) != (N,):
+        raise ValueError("ctc_forced_align: target_lengths must be [N=%d], got %s" % (N, tuple(target_lengths.shape)))
+    S = targets.shape[1]
+    if S > defines["MR_CTC_ALIGN_MAX_SYMBOLS"]:
+        raise ValueError("ctc_forced_align: S=%d symbols per row, 0..%d are taken" % (S, defines["MR_CTC_ALIGN_MAX_SYMBOLS"]))
+    if C < 2 or not 0 <= blank < C:
+        raise ValueError("ctc_forced_align: blank=%d is not one of C=%d classes (C >= 2)" % (blank, C))
+    if not 1 <= T <= defines["MR_SEQ_MEASURE_MAX"]:
+        raise ValueError("ctc_forced_align: T=%d columns, 1..%d are taken" % (T, defines["MR_SEQ_MEASURE_MAX"]))
+    require_cuda(pred, targets, target_lengths)
+    if targets.device != pred.device or target_lengths.device != pred.device:
+        raise ValueError("ctc_forced_align: pred is on %s, targets on %s, target_lengths on %s"
+                         % (pred.device, targets.device, target_lengths.device))
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        pred = pred.float()
+    targets = targets.to(torch.int32).contiguous()
+    target_lengths = target_lengths.to(torch.int32).contiguous()
+    dev = pred.device
+    out = {'score': torch.empty((N,), dtype=torch.float32, device=dev),
+           'pos': torch.empty((N, T), dtype=torch.int32, device=dev),
+           'begin': torch.empty((N, S), dtype=torch.int32, device=dev),
+           'end': torch.empty((N, S), dtype=torch.int32, device=dev),
+           'sym_lp': torch.empty((N, S), dtype=torch.float32, device=dev),
+           'peak': torch.empty((N, S), dtype=torch.int32, device=dev)}
+    if N == 0:
+        return out
+    nbytes = load().mr_ctc_align_ws_bytes(N, T, S)
+    if nbytes <= 0:
+        raise ValueError("ctc_forced_align: N=%d T=%d S=%d need a workspace above 2 GiB; split the batch" % (N, T, S))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    sn, sc, st = pred.stride()
+    with torch.cuda.device(dev):
+        call("mr_ctc_align", 0 if pred.dtype == torch.float32 else 1, ptr(pred), sn, sc, st, N, C, T, int(bool(log_probs)),
+             blank, int(unknown), ptr(targets), S, ptr(target_lengths), ptr(out['score']), ptr(out['pos']), ptr(out['begin']),
+             ptr(out['end']), ptr(out['sym_lp']), ptr(out['peak']), ptr(ws), ws.numel() * 8)
+    return out
+
+
 def ctc2d_greedy_decode(classify, mask, blank=0, unknown=1):
     """classify [N, C, H, W], mask [N, 1, H, W] on the GPU (any strides; converted to f32 if needed).
     Returns (ids i32 [N, W], lengths i32 [N])."""

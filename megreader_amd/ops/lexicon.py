@@ -178,6 +178,27 @@ class Lexicon(object):
         """bool [N] on the device: the row, read as the measurer reads a label, is a word of the lexicon."""
         return self.nearest(ids, spans)['distance'] == 0
 
+    def ids(self, index):
+        """index: integer [N] on the device (what `nearest` / `transcribe` return).  Returns (i32 [N, Smax] blank padded, i32 [N]),
+        both on the device: the folded symbols of the words index[n] and their lengths, length 0 where index[n] < 0; Smax is the
+        longest word of the lexicon (at least 1).  Tensor indexing on the resident word table: nothing is copied to the host."""
+        require_cuda(index)
+        if index.dim() != 1:
+            raise ValueError("index must be [N], got %s" % (tuple(index.shape),))
+        dev = index.device
+        sym, off, _ = self._tensors(dev)
+        L = len(self.words)
+        smax = max(int(np.diff(self.off).max()) if L else 0, 1)
+        index = index.long()
+        have = (index >= 0) & (index < L)
+        word = index.clamp(0, max(L - 1, 0))
+        lo = off[word].long()
+        length = torch.where(have, off[(word + 1).clamp(max=L)].long() - lo, torch.zeros_like(lo))
+        cols = torch.arange(smax, device=dev)
+        take = (lo[:, None] + cols[None, :]).clamp(max=sym.numel() - 1)
+        out = torch.where(cols[None, :] < length[:, None], sym[take], torch.full_like(take, int(self.blank), dtype=torch.int32))
+        return out.to(torch.int32), length.to(torch.int32)
+
     def strings(self, index):
         """Host side: the words of an index tensor / sequence; None for -1."""
         if torch.is_tensor(index):

@@ -2,7 +2,8 @@
 confidence in the box; with `lexicon=` also 'raw_text' and 'lexicon_distance', and 'text' is the nearest lexicon word, or with
 `lexicon_rule='likelihood'` the word with the greatest CTC probability, its log-probability in 'lexicon_score'; with
 `decode='beam'` 'text' is the most probable string of the CTC posterior, its log-probability in 'text_score', and with
-`nbest > 1` the other readings in 'alternatives').
+`nbest > 1` the other readings in 'alternatives'; with `chars=True` also 'chars': where every character of 'text' lies in the photo
+and how sure the recogniser is of it, by forced alignment of the final string to the CTC posterior).
 
 The reference has the pieces in separate programs -- the DB detector with `SegDetectorRepresenter`
 (structure/representers/seg_detector_representer.py), `ImageCropper` (data/crop_file_dataset.py:85-124) and the recognisers --
@@ -19,21 +20,26 @@ models:
   2. `detector(image)` in eval mode under no_grad, `representer.represent` with the photos' own shapes (boxes in photo pixels);
   3. `QuadCropper.crop` samples the recognition batch out of the photos still resident in the pipeline's device buffer;
   4. `recognizer` in chunks of `max_crops`, greedy decoding (or prefix beam search), `charset.label_to_string`.
-Only the boxes (a few hundred points) and the decoded ids (with the beam: ids, lengths and scores) cross to the host."""
+Only the boxes (a few hundred points) and the decoded ids (with the beam: ids, lengths and scores; with `chars=True` the first and
+last column and the summed log-probability of every character) cross to the host."""
+import math
+
 import numpy as np
 import torch
 
 from .data.device_pipeline import DevicePipeline
 from .data.quad_crop import QuadCropper
-from .ops.decode import ctc_beam_search_decode, ctc_greedy_decode
+from .ops.decode import ctc_beam_search_decode, ctc_forced_align, ctc_greedy_decode
 from .ops.lexicon import Lexicon
+from ._lib import _DEFINES
 from .structure.seg_detector_representer import SegDetectorRepresenter
 
 
 class TextReader(object):
     def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
                  rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
-                 lexicon_max_distance=None, lexicon_rule='nearest', beam_width=8, nbest=1, beam_top_classes=16):
+                 lexicon_max_distance=None, lexicon_rule='nearest', beam_width=8, nbest=1, beam_top_classes=16, chars=False,
+                 column_geometry=None):
         if lexicon_rule not in ('nearest', 'likelihood'):
             raise ValueError("lexicon_rule must be 'nearest' or 'likelihood', got %r" % (lexicon_rule,))
         if lexicon_rule == 'likelihood' and decode != 'ctc':
@@ -45,6 +51,13 @@ class TextReader(object):
                              "beam_width=%r beam_top_classes=%r" % (nbest, beam_width, beam_top_classes))
         if int(max_crops) < 1:
             raise ValueError("max_crops must be at least 1, got %r" % (max_crops,))
+        if chars and decode not in ('ctc', 'beam'):
+            raise ValueError("chars=True aligns the text to a CTC posterior: it needs decode='ctc' or 'beam', got %r" % (decode,))
+        if column_geometry is not None:
+            stride, offset = (float(v) for v in column_geometry)
+            if not (stride > 0.0 and math.isfinite(stride) and math.isfinite(offset)):
+                raise ValueError("column_geometry must be (stride > 0, offset) in canvas pixels, got %r" % (column_geometry,))
+            column_geometry = (stride, offset)
         self.detector = detector
         self.recognizer = recognizer
         self.charset = charset
@@ -53,6 +66,8 @@ class TextReader(object):
         self.beam_width, self.nbest, self.beam_top_classes = int(beam_width), int(nbest), int(beam_top_classes)
         self.max_crops = int(max_crops)
         self.scores = bool(scores)
+        self.chars = bool(chars)
+        self.column_geometry = column_geometry
         if lexicon is not None and not isinstance(lexicon, Lexicon):
             lexicon = Lexicon(lexicon, charset)
         self.lexicon = lexicon
@@ -106,17 +121,64 @@ class TextReader(object):
                                          for j in range(k)]
         return out['ids'][:, 0], out['lengths'][:, 0], extras
 
+    def _align(self, pred, ids, lengths, found):
+        """One chunk's FINAL strings aligned to its posterior (`ctc_forced_align`): (begin, end, sym_lp) as numpy [M, S] and the
+        number of columns T.  The final ids are the decoded ones (greedy, or the beam's first hypothesis), or `Lexicon.ids` of the
+        word where one was taken; a lexicon word is aligned to the posterior over the folded alphabet (`Lexicon._folded`), the
+        rows that kept their raw string to the posterior as it is: two calls per chunk at most, each with length -1 (unalignable,
+        no work) for the other call's rows.  Only the three arrays cross to the host."""
+        blank, unknown = getattr(self.charset, 'blank', 0), getattr(self.charset, 'unknown', 1)
+        if isinstance(pred, (tuple, list)):
+            pred = pred[0]
+        if pred.dim() == 4:
+            pred = pred.select(2, 0)
+        dev = pred.device
+        # (a string of more symbols than mr_ctc_align takes keeps its length and is unalignable)
+        targets = ids[:, :_DEFINES["MR_CTC_ALIGN_MAX_SYMBOLS"]].to(device=dev, dtype=torch.int32)
+        lens = lengths.to(device=dev, dtype=torch.int32)
+        took = fold = None
+        if found is not None:
+            took = found['index'] >= 0
+            if self.lexicon_rule == 'nearest' and self.lexicon_max_distance is not None:
+                took = took & (found['distance'] <= self.lexicon_max_distance)
+            words, word_lens = self.lexicon.ids(torch.where(took, found['index'], torch.full_like(found['index'], -1)))
+            S = max(targets.shape[1], words.shape[1])
+            targets = torch.nn.functional.pad(targets, (0, S - targets.shape[1]), value=blank)
+            words = torch.nn.functional.pad(words, (0, S - words.shape[1]), value=blank)
+            targets = torch.where(took[:, None], words, targets)
+            lens = torch.where(took, word_lens, lens)
+            fold = self.lexicon._tensors(dev)[2]
+        if fold is None:                                        # one posterior for every row
+            out = ctc_forced_align(pred, targets, lens, blank=blank, unknown=unknown)
+        else:
+            none = torch.full_like(lens, -1)
+            raw = ctc_forced_align(pred, targets, torch.where(took, none, lens), blank=blank, unknown=unknown)
+            folded = ctc_forced_align(self.lexicon._folded(pred, fold, False), targets, torch.where(took, lens, none),
+                                      blank=blank, unknown=unknown)
+            out = {k: torch.where(took[:, None], folded[k], raw[k]) for k in ('begin', 'end', 'sym_lp')}
+        return out['begin'].cpu().numpy(), out['end'].cpu().numpy(), out['sym_lp'].cpu().numpy(), int(pred.shape[2])
+
+    def _spans(self, symbols, begin, end, sym_lp, T):
+        """What `read` makes one crop's 'chars' of: [(character, first column, one past the last, summed log-probability)] and T,
+        or None when the string could not be aligned (the slots of its symbols are then empty)."""
+        n = int((begin >= 0).sum())
+        if n != len(symbols):
+            return None
+        return [(ch, int(begin[k]), int(end[k]), float(sym_lp[k])) for k, ch in enumerate(symbols)], T
+
     def recognize(self, crops):
         """crops: f32 [M, 3, H, W] on the device -> M strings (with a lexicon: the nearest words, see `read`)."""
         texts = self._recognize(crops)[0]
         return texts if self.lexicon is None else [t[0] for t in texts]
 
     def _recognize(self, crops):
-        """(texts, extras).  texts: M strings; with a lexicon M (text, raw text, distance) triples, the text the nearest lexicon
+        """(texts, extras, spans).  texts: M strings; with a lexicon M (text, raw text, distance) triples, the text the nearest lexicon
         word where its distance is within `lexicon_max_distance`; with the likelihood rule (text, raw text, distance, score), the
         text the most probable word among those within `lexicon_max_distance` of the greedy string.  extras: None, or with
-        decode='beam' M dicts of the keys the beam adds to an item."""
+        decode='beam' M dicts of the keys the beam adds to an item.  spans: None, or with chars=True per crop what `_spans` returns
+        for the crop's final text."""
         texts = []
+        spans = [] if self.chars else None
         extras = [] if self.decode == 'beam' else None
         likelihood = self.lexicon is not None and self.lexicon_rule == 'likelihood'
         for lo in range(0, crops.shape[0], self.max_crops):
@@ -136,22 +198,47 @@ class TextReader(object):
                     beyond = torch.arange(rows.shape[1], device=rows.device)[None, :] >= lengths.to(rows.device)[:, None]
                     rows = rows.masked_fill(beyond, getattr(self.charset, 'blank', 0))
                 found = self.lexicon.nearest(rows)
+            aligned = self._align(pred, ids, lengths, found) if self.chars else None
             ids = ids.cpu().numpy()
             lengths = np.full(len(ids), ids.shape[1]) if lengths is None else lengths.cpu().numpy()
             raw = [self.charset.label_to_string(row[:int(k)]) for row, k in zip(ids, lengths)]
+            first = len(texts)
             if found is None:
                 texts.extend(raw)
-                continue
-            if likelihood:
+            elif likelihood:
                 index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
                 for text, i, d, score in zip(raw, index, distance, found['score'].cpu().tolist()):
                     texts.append((self.lexicon.words[i] if i >= 0 else text, text, d, score))
-                continue
-            index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
-            for text, i, d in zip(raw, index, distance):
-                near = i >= 0 and (self.lexicon_max_distance is None or d <= self.lexicon_max_distance)
-                texts.append((self.lexicon.words[i] if near else text, text, d))
-        return texts, extras
+            else:
+                index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
+                for text, i, d in zip(raw, index, distance):
+                    near = i >= 0 and (self.lexicon_max_distance is None or d <= self.lexicon_max_distance)
+                    texts.append((self.lexicon.words[i] if near else text, text, d))
+            if aligned is not None:
+                begin, end, sym_lp, T = aligned
+                for m, (row, k, text) in enumerate(zip(ids, lengths, texts[first:])):
+                    if found is None or text[0] == text[1]:     # the raw string (or a word that spells the same): its own ids
+                        symbols = [self.charset.label_to_string(row[j:j + 1]) for j in range(int(k))]
+                    else:                                       # a lexicon word: its own characters
+                        symbols = list(text[0])
+                    spans.append(self._spans(symbols, begin[m], end[m], sym_lp[m], T))
+        return texts, extras, spans
+
+    def _chars(self, plan, spans):
+        """One item's 'chars' from its crop's plan and aligned spans: the canvas rectangle of each character's columns, clamped to
+        the valid canvas, carried to the photo by `CropPlan.canvas_to_photo`."""
+        if spans is None:
+            return None
+        spans, T = spans
+        H, W = plan.canvas
+        stride, offset = self.column_geometry if self.column_geometry is not None else (float(W) / T, 0.0)
+        chars = []
+        for ch, begin, end, lp in spans:
+            u0 = min(max(offset + begin * stride, 0.0), float(plan.dst_w))
+            u1 = min(max(offset + end * stride, 0.0), float(plan.dst_w))
+            quad = plan.canvas_to_photo([[u0, 0.0], [u1, 0.0], [u1, float(H)], [u0, float(H)]])
+            chars.append({'char': ch, 'quad': quad.tolist(), 'score': math.exp(lp / (end - begin))})
+        return chars
 
     def read(self, images):
         """images: a list of uint8 HWC numpy arrays.  Returns, per image, a list of {'quad': [[x, y] * 4], 'text': str} in the
@@ -168,7 +255,17 @@ class TextReader(object):
         with a lexicon and the `nearest` rule as 'raw_text' and as what the nearest word is searched for -- and every item also
         has 'text_score', a float: its log-probability under the posterior (a lower bound: pruned alignments are missing); with
         `nbest > 1` also 'alternatives', the list of (text, score) of all hypotheses returned, the first one included, in
-        descending order.  A crop whose beam died (no string has a non-zero probability) gets '', -inf and []."""
+        descending order.  A crop whose beam died (no string has a non-zero probability) gets '', -inf and [].  With `chars=True`
+        (`decode='ctc'` or `'beam'`) every item also has 'chars', one {'char', 'quad', 'score'} per character of 'text': the final
+        string -- the greedy ids, the beam's first hypothesis, or the lexicon word where one was taken -- is aligned to the crop's
+        posterior by `ctc_forced_align` (a lexicon word to the posterior over the folded alphabet), 'score' is the geometric mean
+        probability of the character over the columns of its span, exp(sym_lp / (end - begin)), and 'quad' the photo quadrilateral
+        [[x, y] * 4] (TL, TR, BR, BL of the canvas rectangle) of the canvas columns U in [offset + begin * stride, offset + end *
+        stride], clamped to the valid canvas, over the whole height, carried to the photo by `CropPlan.canvas_to_photo` -- a
+        vertical crop gives boxes stacked along the photo's vertical axis.  `column_geometry` is (stride, offset) in canvas pixels;
+        None means (W / T, 0): the posterior's columns partition the canvas evenly.  A model whose columns are not spread evenly
+        (the CRNN's 33 columns over 128 pixels) should pass its own.  A text that cannot be aligned (a lexicon word of more
+        symbols than columns, or one reachable only through zero probabilities) gets 'chars': None."""
         images = list(images)
         results = [[] for _ in images]
         if not images:
@@ -186,7 +283,7 @@ class TextReader(object):
         if layout.M == 0:
             return results
         crops = self.cropper.upload(staged, layout)
-        texts, extras = self._recognize(crops['image'])
+        texts, extras, spans = self._recognize(crops['image'])
         host = staged.numpy()
         index = host[layout.index_off:layout.index_off + 4 * layout.M].view(np.int32)
         quads = host[layout.quad_off:layout.quad_off + 64 * layout.M].view(np.float64).reshape(layout.M, 4, 2)
@@ -200,6 +297,8 @@ class TextReader(object):
                     results[i][-1]['lexicon_score'] = text[3]
             if extras is not None:
                 results[i][-1].update(extras[m])
+            if spans is not None:
+                results[i][-1]['chars'] = self._chars(layout.plans[m], spans[m])
         if self.scores:                                                        # ... and so are their scores
             dropped = set(layout.dropped)
             for i, found in enumerate(results):
