@@ -273,6 +273,22 @@ def _grad_internal(g, dtype):
     return to_internal(g, dtype)
 
 
+def _logical(y, C):
+    """NHWC buffer [N,H,W,Cp] -> logical NCHW view of its first C channels (what Conv2dFn returns for a padded K)."""
+    return (y if y.shape[3] == C else y[..., :C]).permute(0, 3, 1, 2)
+
+
+def _grad_padded(g, dtype, Cp):
+    """incoming gradient (logical NCHW, C <= Cp channels) -> NHWC contiguous [N,H,W,Cp] of the compute dtype; a logical count
+    that is no multiple of the vector is re-packed with zero pad channels, as to_internal packed the forward input."""
+    if g.shape[1] == Cp:
+        return _grad_internal(g, dtype)
+    gi = to_internal(g, dtype)
+    if gi.shape[3] != Cp:
+        raise RuntimeError("gradient with %d channels for an operand padded to %d" % (g.shape[1], Cp))
+    return gi
+
+
 def mark_zero_padded(t):
     """Tag an NHWC gradient buffer whose channels beyond the logical count are zero (written that way by the producing
     kernel).  A consumer that works on channel-padded operands -- Conv2dFn.backward with Kp != K -- recognises a logical
@@ -1570,15 +1586,16 @@ class AdaptiveAvgPoolFn(Function):
         call("mr_adaptive_avgpool_fwd", dtype_code(dtype), ptr(xi), ptr(y), N, H, W, C, OH, OW)
         ctx.geom = (N, H, W, C, OH, OW)
         ctx.dtype = dtype
-        return y.permute(0, 3, 1, 2)
+        ctx.logical = x.shape[1]
+        return _logical(y, ctx.logical)
 
     @staticmethod
     def backward(ctx, gy):
         N, H, W, C, OH, OW = ctx.geom
-        g = _grad_internal(gy, ctx.dtype)
+        g = _grad_padded(gy, ctx.dtype, C)
         dx = torch.empty((N, H, W, C), dtype=ctx.dtype, device=g.device)
         call("mr_adaptive_avgpool_bwd", dtype_code(ctx.dtype), ptr(g), ptr(dx), N, H, W, C, OH, OW)
-        return dx.permute(0, 3, 1, 2), None
+        return _logical(dx, ctx.logical), None
 
 
 def adaptive_avg_pool2d(x, output_size):
@@ -1646,15 +1663,16 @@ class BilinearFn(Function):
         call("mr_bilinear_fwd", dtype_code(dtype), ptr(xi), ptr(y), N, H, W, C, OH, OW, C, 0, 0)
         ctx.geom = (N, H, W, C, OH, OW)
         ctx.dtype = dtype
-        return y.permute(0, 3, 1, 2)
+        ctx.logical = x.shape[1]
+        return _logical(y, ctx.logical)
 
     @staticmethod
     def backward(ctx, gy):
         N, H, W, C, OH, OW = ctx.geom
-        g = _grad_internal(gy, ctx.dtype)
+        g = _grad_padded(gy, ctx.dtype, C)
         dx = torch.empty((N, H, W, C), dtype=ctx.dtype, device=g.device)
         call("mr_bilinear_bwd", dtype_code(ctx.dtype), ptr(g), ptr(dx), N, H, W, C, OH, OW, C, 0)
-        return dx.permute(0, 3, 1, 2), None
+        return _logical(dx, ctx.logical), None
 
 
 def interpolate_bilinear(x, size):
@@ -1705,8 +1723,8 @@ class BilinearCatFn(Function):
 
 
 def cat_bilinear(base, branches):
-    """cat([base] + [interpolate_bilinear(b, base.shape[2:]) for b in branches], 1); channel counts must be multiples of one
-    16-byte vector (falls back to the separate ops otherwise)."""
+    """cat([base] + [interpolate_bilinear(b, base.shape[2:]) for b in branches], 1); one buffer and no per-branch copy when
+    every channel count is a multiple of one 16-byte vector, the separate ops otherwise."""
     v = vec_of(get_compute_dtype())
     if base.shape[1] % v or any(b.shape[1] % v for b in branches):
         return cat_channels([base] + [interpolate_bilinear(b, base.shape[2:]) for b in branches])
@@ -1724,22 +1742,23 @@ class UpsampleAddFn(Function):
         xi, yi = to_internal(x, dtype), to_internal(y, dtype)
         N, H, W, C = xi.shape
         _, OH, OW, C2 = yi.shape
-        if C != C2:
+        if C != C2 or x.shape[1] != y.shape[1]:
             raise RuntimeError("upsample_add: channel mismatch")
         out = torch.empty_like(yi)
         call("mr_copy_channels", dt, ptr(yi), C, 0, ptr(out), C, 0, N * OH * OW, C)
         call("mr_bilinear_fwd", dt, ptr(xi), ptr(out), N, H, W, C, OH, OW, C, 0, 1)
         ctx.geom = (N, H, W, C, OH, OW)
         ctx.dtype = dtype
-        return out.permute(0, 3, 1, 2)
+        ctx.logical = x.shape[1]
+        return _logical(out, ctx.logical)
 
     @staticmethod
     def backward(ctx, g_out):
         N, H, W, C, OH, OW = ctx.geom
-        g = _grad_internal(g_out, ctx.dtype)
+        g = _grad_padded(g_out, ctx.dtype, C)
         dx = torch.empty((N, H, W, C), dtype=ctx.dtype, device=g.device)
         call("mr_bilinear_bwd", dtype_code(ctx.dtype), ptr(g), ptr(dx), N, H, W, C, OH, OW, C, 0)
-        return dx.permute(0, 3, 1, 2), g_out
+        return _logical(dx, ctx.logical), g_out
 
 
 def upsample_add(x, y):
@@ -1748,8 +1767,9 @@ def upsample_add(x, y):
 
 class NearestUpFn(Function):
     """nn.Upsample(scale_factor=s, mode='nearest')(x) (+ y): the DB head's top-down path and its x2 / x4 / x8 output
-    branches (decoders/seg_detector.py:22-43,121-128).  With `into` = (buffer NHWC, channel offset) the result is written
-    straight into a channel slice of a concatenation buffer (torch.cat((p5, p4, p3, p2), 1), seg_detector.py:130)."""
+    branches (decoders/seg_detector.py:22-43,121-128).  `add` (optional) has the output's shape and receives the upstream
+    gradient unchanged.  (mr_nearest_up_fwd / _bwd can also address a channel slice of a wider buffer -- ldy, coff; this
+    function always writes a buffer of its own.)"""
 
     @staticmethod
     def forward(ctx, x, scale, add):
@@ -1759,20 +1779,23 @@ class NearestUpFn(Function):
         xi = to_internal(x, dtype)
         N, H, W, C = xi.shape
         ai = to_internal(add, dtype) if add is not None else None
+        if ai is not None and (tuple(ai.shape) != (N, H * scale, W * scale, C) or add.shape[1] != x.shape[1]):
+            raise RuntimeError("upsample_nearest: `add` must have the output's shape")
         out = torch.empty((N, H * scale, W * scale, C), dtype=dtype, device=xi.device)
         call("mr_nearest_up_fwd", dt, ptr(xi), ptr(ai), ptr(out), N, H, W, C, int(scale), C, 0)
         ctx.geom = (N, H, W, C, int(scale))
         ctx.dtype = dtype
         ctx.has_add = add is not None
-        return out.permute(0, 3, 1, 2)
+        ctx.logical = x.shape[1]
+        return _logical(out, ctx.logical)
 
     @staticmethod
     def backward(ctx, g_out):
         N, H, W, C, s = ctx.geom
-        g = _grad_internal(g_out, ctx.dtype)
+        g = _grad_padded(g_out, ctx.dtype, C)
         dx = torch.empty((N, H, W, C), dtype=ctx.dtype, device=g.device)
         call("mr_nearest_up_bwd", dtype_code(ctx.dtype), ptr(g), ptr(dx), N, H, W, C, s, C, 0)
-        return dx.permute(0, 3, 1, 2), None, (g_out if ctx.has_add else None)
+        return _logical(dx, ctx.logical), None, (g_out if ctx.has_add else None)
 
 
 def upsample_nearest(x, scale, add=None):
@@ -1814,6 +1837,12 @@ class CatChannelsFn(Function):
 
 
 def cat_channels(tensors):
+    """torch.cat(tensors, 1) in the compute dtype.  The vector copy needs every part to be a multiple of one 16-byte vector (a
+    padded part would leave zero channels inside the result); other channel counts go through torch.cat itself."""
+    dtype = get_compute_dtype()
+    v = vec_of(dtype)
+    if any(t.shape[1] % v for t in tensors):
+        return torch.cat([t.to(dtype) for t in tensors], 1)
     return CatChannelsFn.apply(*tensors)
 
 
@@ -1825,20 +1854,30 @@ class ScaleChannelsFn(Function):
         dtype = get_compute_dtype()
         xi = to_internal(x, dtype)
         N, H, W, C = xi.shape
+        if tuple(scale.shape) != (N, x.shape[1]):
+            raise RuntimeError("scale must be [N, C] = %s, got %s" % ((N, x.shape[1]), tuple(scale.shape)))
+        scale = scale.detach().to(torch.float32)
+        if C != x.shape[1]:         # the kernel indexes scale[n * C + c] with the padded C
+            padded = torch.zeros((N, C), dtype=torch.float32, device=scale.device)
+            padded[:, :x.shape[1]] = scale
+            scale = padded
+        scale = scale.contiguous()
         y = torch.empty_like(xi)
         call("mr_scale_channels", dtype_code(dtype), ptr(xi), ptr(scale), ptr(y), N, H * W, C)
         ctx.save_for_backward(scale)
         ctx.dtype = dtype
-        return y.permute(0, 3, 1, 2)
+        ctx.logical = x.shape[1]
+        return _logical(y, ctx.logical)
 
     @staticmethod
     def backward(ctx, gy):
         (scale,) = ctx.saved_tensors
-        g = _grad_internal(gy, ctx.dtype)
-        N, H, W, C = g.shape
+        N, C = scale.shape
+        g = _grad_padded(gy, ctx.dtype, C)
+        _, H, W, _ = g.shape
         dx = torch.empty_like(g)
         call("mr_scale_channels", dtype_code(ctx.dtype), ptr(g), ptr(scale), ptr(dx), N, H * W, C)
-        return dx.permute(0, 3, 1, 2), None
+        return _logical(dx, ctx.logical), None
 
 
 def dropout2d(x, p, training):

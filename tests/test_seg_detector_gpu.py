@@ -221,3 +221,101 @@ def test_db_head_tail_equals_the_torch_expression(dtype):
     tol = 2e-6 if dtype == torch.float32 else 1e-2
     for i, (a, r) in enumerate(zip(got, want)):
         assert _rel(a, r) < (5e-6 if i < 3 else tol), i
+
+
+def _head_tail_both_ways(xb, xt, w, k=50.0):
+    """(HIP results, float64 torch results) of F.db_head_tail and the gradients of sum_i (out_i * w_i).sum(); w_i = None leaves
+    that output without an upstream gradient (the nullable gb / gt / gtb of mr_db_head_tail_bwd)."""
+    from megreader_amd.nn import functional as F
+
+    def total(outs):
+        return sum((o * wi).sum() for o, wi in zip(outs, w) if wi is not None)
+    xb, xt = xb.to(DEV).requires_grad_(True), xt.to(DEV).requires_grad_(True)
+    outs = F.db_head_tail(xb, xt, k)
+    total(outs).backward()
+    got = tuple(o.detach() for o in outs) + (xb.grad.clone(), xt.grad.clone())
+    xb2 = xb.detach().clone().requires_grad_(True)
+    xt2 = xt.detach().clone().requires_grad_(True)
+    b2, t2 = torch.sigmoid(xb2.double()), torch.sigmoid(xt2.double())
+    tb2 = torch.reciprocal(1 + torch.exp(-k * (b2 - t2)))
+    total((b2, t2, tb2)).backward()
+    grads = [x.grad if x.grad is not None else torch.zeros_like(x, dtype=torch.float64) for x in (xb2, xt2)]   # not reached: 0
+    return got, (b2.detach(), t2.detach(), tb2.detach(), grads[0], grads[1])
+
+
+def _head_tail_bounds(dtype):          # as test_db_head_tail_equals_the_torch_expression: outputs (f32), input gradients (dtype)
+    return 5e-6, (2e-6 if dtype == torch.float32 else 1e-2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("n", [1, 257, 4096 * 256 + 3])
+def test_db_head_tail_sizes(dtype, n):
+    """One element, one element past a workgroup, and three elements past the 4096-workgroup cap of the grid, where the kernels
+    stride; the last elements are compared on their own as well.  With one element the max norm is that element's own relative
+    error, and the float32 bar follows from the arithmetic instead: binary and thresh are rounded to float32 (2^-25 each below 1),
+    the step function multiplies the error of their difference by k = 50, and the product chain adds a few roundings --
+    (k + 8) 2^-24 = 3.5e-6 of the gradient."""
+    g = torch.Generator().manual_seed(n)
+    xb = (torch.randn(1, 1, 1, n, generator=g) * 3).to(dtype)
+    xt = (torch.randn(1, 1, 1, n, generator=g) * 3).to(dtype)
+    w = [torch.randn(1, 1, 1, n, generator=g).to(DEV) for _ in range(3)]
+    got, want = _head_tail_both_ways(xb, xt, w)
+    t_out, t_grad = _head_tail_bounds(dtype)
+    if n == 1:
+        t_grad = max(t_grad, (50.0 + 8) * 2.0 ** -24)
+    for i, (a, r) in enumerate(zip(got, want)):
+        assert a.shape == r.shape and bool(torch.isfinite(a).all()), i
+        assert _rel(a, r) < (t_out if i < 3 else t_grad), i
+        tail = slice(max(0, n - 3), n)
+        assert float((a[..., tail].double() - r[..., tail]).abs().max()) <= (t_out if i < 3 else t_grad) * float(r.abs().max()), i
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_db_head_tail_saturated_logits(dtype):
+    """Logits of +-120: exp(120) overflows float32 and exp(-120) underflows it, so the sigmoids are exactly 0 and 1 -- the float64
+    values rounded to float32 -- every output stays finite, and no gradient passes a saturated sigmoid."""
+    g = torch.Generator().manual_seed(9)
+    shape = (2, 1, 9, 31)
+    xs = []
+    for _ in range(2):
+        x = torch.randn(shape, generator=g) * 3
+        kind = torch.randint(0, 4, shape, generator=g)          # half of the elements saturate, either way
+        x[kind == 0] = 120.0
+        x[kind == 1] = -120.0
+        xs.append(x.to(dtype))
+    w = [torch.randn(shape, generator=g).to(DEV) for _ in range(3)]
+    got, want = _head_tail_both_ways(xs[0], xs[1], w)
+    t_out, t_grad = _head_tail_bounds(dtype)
+    for a in got:
+        assert bool(torch.isfinite(a).all())
+    sat = [(x.float().abs() == 120.0).to(DEV) for x in xs]
+    for i in (0, 1):
+        assert torch.equal(got[i][sat[i]], want[i].float()[sat[i]])     # the float64 sigmoid rounded once
+        assert set(got[i][sat[i]].unique().tolist()) == {0.0, 1.0}
+        assert not got[3 + i][sat[i]].any()                     # b (1 - b) = 0
+        assert _rel(got[i], want[i]) < t_out and _rel(got[3 + i], want[3 + i]) < t_grad
+    # thresh_binary: where both sigmoids saturate, binary - thresh is exactly -1, 0 or 1 and the map spans 1 / (1 + exp(+-50)):
+    # those element by element on their own scale (one expf and one divide), the whole map in the max norm
+    both = sat[0] & sat[1]
+    assert int(both.sum()) > 50
+    assert float(((got[2].double() - want[2]).abs() / want[2])[both].max()) < t_out
+    assert _rel(got[2], want[2]) < t_out
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_db_head_tail_single_upstream_gradient(dtype, which):
+    """Only one of binary / thresh / thresh_binary feeds the loss: the other two upstream gradients arrive as None."""
+    g = torch.Generator().manual_seed(4 + which)
+    shape = (2, 1, 7, 37)
+    xb = (torch.randn(shape, generator=g) * 3).to(dtype)
+    xt = (torch.randn(shape, generator=g) * 3).to(dtype)
+    w = [torch.randn(shape, generator=g).to(DEV) if i == which else None for i in range(3)]
+    got, want = _head_tail_both_ways(xb, xt, w)
+    _, t_grad = _head_tail_bounds(dtype)
+    if which == 0:
+        assert not got[4].any() and not want[4].any()           # thresh does not reach binary
+    if which == 1:
+        assert not got[3].any() and not want[3].any()
+    for i in (3, 4):
+        assert _rel(got[i], want[i]) < t_grad, i
