@@ -814,6 +814,60 @@ int mr_resize_normalize(const unsigned char* src, const void* desc, int N, int H
 int mr_encode_labels(const int* codepoints, const long long* offsets, int N, int max_size, const int* table_cp,
                      const int* table_id, int ntab, int unknown, int* label, int* length, hipStream_t stream);
 
+/* ---- Baseline JPEG decode (csrc/jpeg.hip, csrc/jpeg_plan.h): the "decode" in front of the input pipeline.  A batch of encoded
+ * files goes to the device as bytes; the host only reads their marker segments (mr_jpeg_plan: one call per batch, no allocation,
+ * no GPU call) and the device does the entropy decode, dequantisation, inverse DCT, chroma upsampling and colour conversion.
+ * The pixels are bit-identical to the default decode of libjpeg / libjpeg-turbo (slow-integer IDCT, triangle upsampling,
+ * 16-bit fixed-point YCbCr -> RGB), which is what PIL and cv2.imdecode return.
+ * Supported on the device: SOF0 (baseline, 8-bit, Huffman), 1 or 3 components in one interleaved scan, luma sampling 1x1, 2x1
+ * or 2x2 with chroma 1x1, 8-bit quantisation tables, YCbCr (JFIF, Adobe transform 1, or unmarked) or grayscale.  Everything else
+ * -- progressive, arithmetic, 12-bit, 4 components, Adobe transform 0, multi-scan, other sampling, bytes that do not start with
+ * SOI -- is MR_JPEG_UNSUPPORTED (decode it on the host); a file that starts as a JPEG and breaks the syntax is MR_JPEG_CORRUPT.
+ *
+ * mr_jpeg_plan fills images[n] and the work items: an image without a restart interval is one item, an image with one is one item
+ * per interval (the host finds the RSTn markers with a byte scan).  One wavefront decodes one item, so restart markers are the
+ * only parallelism inside one image.  totals[4] = {items needed, bytes of the blob buffer, of the workspace, of the output}: the
+ * caller copies blob i to blob_off of ONE buffer (offsets are 16-byte aligned, all blobs are laid out whatever their status) and
+ * allocates the other two.  When totals[0] > max_items the item list is incomplete: call again with room for totals[0].
+ * On MR_JPEG_OK every offset of the plan lies inside its buffer. */
+#define MR_JPEG_OK 0
+#define MR_JPEG_UNSUPPORTED 1
+#define MR_JPEG_CORRUPT 2
+typedef struct mr_jpeg_image {
+  int status, h, w, ncomp;
+  int hs, vs;                     /* luma sampling factors (chroma is 1x1; a grayscale image reports 1x1) */
+  int mcu_w, mcu_h;               /* MCUs per row, MCU rows */
+  int restart;                    /* restart interval in MCUs, 0: none */
+  int first_item, n_items;        /* this image's work items */
+  int reserved0;
+  long long blob_off, blob_len;   /* the blob inside the blob buffer */
+  long long scan_off, scan_len;   /* the entropy-coded segment inside the blob */
+  long long plane_off[3];         /* uint8 component planes inside the workspace, padded to whole MCUs */
+  int plane_pitch[3], plane_rows[3];
+  long long out_off;              /* first output byte: uint8 [h][w][3], pitch exactly w * 3 */
+  int comp_tq[3], comp_td[3], comp_ta[3];   /* per component: quantisation table 0..3, DC table 0..1, AC table 0..1 */
+  int reserved1;
+  int quant[64];                  /* 4 tables x 64 BYTES in memory order, coefficients in zigzag order */
+  int huff_maxcode[64];           /* [DC0, DC1, AC0, AC1][code length - 1]: the largest code of that length, -1: none */
+  int huff_valoff[64];            /* same index: (index of the first symbol of that length) - (its code) */
+  int huff_sym[256];              /* 4 tables x 256 BYTES in memory order: the symbols by increasing code */
+} mr_jpeg_image;
+typedef struct mr_jpeg_item {
+  int image, mcu0, nmcu, reserved;   /* MCUs mcu0 .. mcu0 + nmcu - 1 of that image, DC predictors starting at 0 */
+  long long off, len;                /* their stuffed bytes inside the blob; no marker inside */
+} mr_jpeg_item;
+int mr_sizeof_jpeg_image(void);
+int mr_sizeof_jpeg_item(void);
+int mr_jpeg_plan(int n, const void* const* blobs, const long long* lens, mr_jpeg_image* images, mr_jpeg_item* items,
+                 long long max_items, long long* totals);
+/* blobs_dev: the blob buffer; plan_dev: the n_images mr_jpeg_image followed by the n_items mr_jpeg_item, as mr_jpeg_plan wrote
+ * them (16-byte aligned); workspace, out: totals[2] and totals[3] bytes; status: i32 [n_images], written by the call (the plan's
+ * status, raised to MR_JPEG_CORRUPT when an item meets an invalid code or runs out of bytes before its last MCU -- such an image's
+ * pixels are unspecified, every other image is unaffected).  rgb: 0 writes B, G, R per pixel (cv2's order), 1 writes R, G, B.
+ * Only bytes [out_off, out_off + h*w*3) of OK images are written.  Three launches on `stream`, no host synchronisation. */
+int mr_jpeg_decode(const void* blobs_dev, const void* plan_dev, int n_images, int n_items, void* workspace, void* out,
+                   int* status, int rgb, hipStream_t stream);
+
 /* ---- DB detector augmentation (csrc/image_sample.hip): the image half of data/processes/augment_data.py
  * (`AugmentDetectionData`: Fliplr, Affine rotate, Resize), data/processes/random_crop_data.py (`RandomCropData`) and
  * data/processes/normalize_image.py in ONE bilinear pass.  The host composes the chain into one affine map per image

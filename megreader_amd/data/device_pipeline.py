@@ -13,6 +13,11 @@ Here the host only hands over the DECODED uint8 pixels (4x fewer bytes than the 
 `process()` = one pinned staging copy (async, side stream) + mr_resize_normalize + mr_encode_labels.
 Resize arithmetic follows cv2's float32 INTER_LINEAR path (csrc/image_sample.hip); cv2 itself is not available in the build
 image, so that one piece is checked against the numpy restatement in oracle/pipeline.py ("parity unpinned").
+
+`EncodedDevicePipeline` takes the step in front as well: it is handed the ENCODED files (what the reference's LMDB and msgpack
+stores hold), the host reads only their JPEG headers, and the device decodes them (data/jpeg_decode.py, csrc/jpeg.hip) into the
+buffer the resize kernel reads -- 5-10x fewer bytes over PCIe again, and no PIL call per sample.  Formats the device does not
+decode (PNG, progressive JPEG, ...) still take the host path inside the same batch.
 """
 import ctypes
 
@@ -21,7 +26,7 @@ import torch
 
 from .._lib import STRUCTS, call, load, ptr
 from ..charsets import EnglishCharset
-from .staging import Sections, Staging, check_images, upload
+from .staging import Sections, Staging, align16, check_images, upload
 
 RGB_MEAN = (122.67891434, 116.66876762, 104.00698793)   # data/processes/normalize_image.py:9 (applied to BGR as is)
 
@@ -104,24 +109,34 @@ class DevicePipeline(object):
         self.unknown = getattr(self.charset, "unknown", 1)
         self._staging = Staging()
 
+    def _describe(self, shapes):
+        """The `ImgDesc` table of images of the given (h, w); the offsets are the caller's to fill."""
+        H, W = self.image_size
+        descs = (ImgDesc * len(shapes))()
+        for d, shape in zip(descs, shapes):
+            d.h, d.w, d.pitch = shape[0], shape[1], shape[1] * 3
+            d.dst_w = W if self.mode == 'resize' else target_width('pad', self.image_size, shape)
+            # cv2: inv_scale = (double)dsize / ssize; scale = 1. / inv_scale
+            d.scale_x = 1.0 / (float(d.dst_w) / float(shape[1]))
+            d.scale_y = 1.0 / (float(H) / float(shape[0]))
+        return descs
+
+    @staticmethod
+    def _text(texts):
+        """The two text sections: the UTF-32 codepoints of all strings back to back, and their int64 [n + 1] offsets."""
+        cp = [np.frombuffer(t.encode('utf-32-le'), dtype=np.int32) for t in texts]
+        offs = np.zeros(len(texts) + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([len(c) for c in cp])
+        return [np.concatenate(cp + [np.zeros(0, dtype=np.int32)]), offs]
+
     def pack(self, images, texts, slot=0):
         """Host side: lay the decoded uint8 HWC images, their descriptors and the UTF-32 text out in ONE pinned
         staging buffer (per prefetch slot).  Returns (pinned uint8 tensor, layout tuple); the layout's last element is the
         `ImgDesc` array that was staged (`photos` reads it)."""
         n = len(images)
-        H, W = self.image_size
         check_images(images)
-        descs = (ImgDesc * n)()
-        for d, im in zip(descs, images):
-            d.h, d.w, d.pitch = im.shape[0], im.shape[1], im.shape[1] * 3
-            d.dst_w = W if self.mode == 'resize' else target_width('pad', self.image_size, im.shape)
-            # cv2: inv_scale = (double)dsize / ssize; scale = 1. / inv_scale
-            d.scale_x = 1.0 / (float(d.dst_w) / float(im.shape[1]))
-            d.scale_y = 1.0 / (float(H) / float(im.shape[0]))
-        cp = [np.frombuffer(t.encode('utf-32-le'), dtype=np.int32) for t in texts]
-        offs = np.zeros(n + 1, dtype=np.int64)
-        offs[1:] = np.cumsum([len(c) for c in cp])
-        lay = Sections(list(images) + [descs, np.concatenate(cp + [np.zeros(0, dtype=np.int32)]), offs])
+        descs = self._describe([im.shape for im in images])
+        lay = Sections(list(images) + [descs] + self._text(texts))
         for d, off in zip(descs, lay.offsets):
             d.offset = off
         staged, _ = self._staging.stage(slot, lay)
@@ -129,9 +144,12 @@ class DevicePipeline(object):
 
     def upload(self, staged, layout):
         """One async H2D copy of the staging buffer, then the two kernels, on the CURRENT stream."""
+        return self._kernels(upload(staged, self.device), layout)
+
+    def _kernels(self, dbuf, layout):
+        """mr_resize_normalize and mr_encode_labels over the uploaded buffer."""
         n, desc_off, text_off, offs_off = layout[:4]
         H, W = self.image_size
-        dbuf = upload(staged, self.device)
         image = torch.empty((n, 3, H, W), dtype=torch.float32, device=self.device)
         call("mr_resize_normalize", ptr(dbuf), dbuf.data_ptr() + desc_off, n, H, W, RGB_MEAN[0], RGB_MEAN[1],
              RGB_MEAN[2], ptr(image))
@@ -150,6 +168,54 @@ class DevicePipeline(object):
     def process(self, images, texts):
         staged, layout = self.pack(images, texts)
         return self.upload(staged, layout)
+
+
+class EncodedDevicePipeline(DevicePipeline):
+    """`DevicePipeline` fed with ENCODED image files: `pack(blobs, texts, slot=0)` / `upload` / `photos` / `process` have the
+    same shape, so `Prefetcher` drives it unchanged.  The host reads only the JPEG headers (data/jpeg_decode.py: one C call per
+    batch); the encoded bytes cross PCIe and the device decodes them (csrc/jpeg.hip) into the buffer that `mr_resize_normalize`
+    reads.  What the device does not decode (PNG, progressive JPEG, ...; `JpegDecoder.plan`) is decoded on the host as before and
+    staged as raw pixels beside the blobs.  The batch also carries 'jpeg_status', int32 [n] on the device: MR_JPEG_CORRUPT where
+    an image's stream turned out to be damaged (nothing synchronises to look at it here).  Pixels are BGR, as the mean is."""
+
+    def __init__(self, image_size=(32, 128), mode='resize', charset=None, max_size=32, device=None, host_above=None):
+        super().__init__(image_size, mode, charset, max_size, device)
+        from .jpeg_decode import HOST_ABOVE, JpegDecoder
+        self.decoder = JpegDecoder(self.device, 'BGR', HOST_ABOVE if host_above is None else host_above)
+
+    def pack(self, blobs, texts, slot=0):
+        """Host side: ONE staging buffer [blobs | plan | host-decoded pixels | descriptors | text].  The device buffer of
+        `upload` is [staged bytes | workspace | decoded pixels]; the `ImgDesc` offsets point into its decoded region for the
+        images the device decodes and at the staged pixels for the others.  Raises ValueError for blobs whose headers are
+        corrupt."""
+        plan = self.decoder.plan(blobs)
+        if plan.corrupt():
+            raise ValueError("corrupt JPEG data at batch indices %s" % plan.corrupt())
+        n = plan.n
+        host = sorted(plan.host)
+        descs = self._describe([plan.shape(i) for i in range(n)])
+        lay = Sections(plan.sections() + [plan.host[i] for i in host] + [descs] + self._text(texts), pad_end=True)
+        workspace_off = lay.total
+        out_off = workspace_off + align16(plan.workspace_bytes)
+        at = dict(zip(host, lay.offsets[3:]))
+        for i, d in enumerate(descs):
+            d.offset = at[i] if i in at else out_off + plan.images[i].out_off
+        staged, views = self._staging.stage(slot, lay)
+        plan.fill_blobs(views[0])
+        jpeg = (plan, lay.offsets[0], lay.offsets[1], workspace_off, out_off, out_off + plan.out_bytes)
+        return staged, (n,) + tuple(lay.offsets[3 + len(host):]) + (descs, jpeg)
+
+    def upload(self, staged, layout):
+        """One device buffer, one async H2D copy of the staged part, then mr_jpeg_decode and the two kernels of
+        `DevicePipeline`, on the CURRENT stream."""
+        from .jpeg_decode import launch
+        plan, blob_off, plan_off, workspace_off, out_off, total = layout[5]
+        dbuf = torch.empty((total,), dtype=torch.uint8, device=self.device)
+        dbuf[:staged.numel()].copy_(staged, non_blocking=True)
+        status = launch(plan, dbuf, blob_off, plan_off, workspace_off, out_off, False)
+        batch = self._kernels(dbuf, layout)
+        batch['jpeg_status'] = status
+        return batch
 
 
 class Prefetcher(object):

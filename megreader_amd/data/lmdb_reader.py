@@ -401,12 +401,17 @@ class LMDBImageStore(object):
         assert maybe_image is not None, 'image %s not found at %s' % (data_id, path)
         return maybe_image
 
-    def default_unpack(self, data_id, meta):
+    def default_unpack(self, data_id, meta, decode=True):
+        """decode=False: meta['image_bytes'] = the stored file as it is (for `EncodedDevicePipeline`, which decodes on the
+        GPU); PIL is not touched."""
+        data = self.search_image(data_id, meta['db_path'])
+        if not decode:
+            meta['image_bytes'] = bytes(data)
+            return meta
         import io
 
         import numpy as np
         from PIL import Image
-        data = self.search_image(data_id, meta['db_path'])
         rgb = np.array(Image.open(io.BytesIO(data)).convert('RGB'))
         meta['image'] = np.ascontiguousarray(rgb[:, :, ::-1])
         return meta

@@ -14,23 +14,28 @@ import io
 
 import msgpack
 import numpy as np
-from PIL import Image
 
 
 class UnpackMsgpackData(object):
-    """`convert(data: bytes) -> dict` with the reference's key / value rules; `mode` 'BGR' (default) or 'RGB'."""
+    """`convert(data: bytes) -> dict` with the reference's key / value rules; `mode` 'BGR' (default) or 'RGB'.
+    decode_images=False leaves the value under b'img' as the stored `bytes` (for `EncodedDevicePipeline`, which decodes on the
+    GPU) and does not touch PIL."""
 
-    def __init__(self, mode='BGR'):
+    def __init__(self, mode='BGR', decode_images=True):
         if mode not in ('BGR', 'RGB'):
             raise ValueError("mode must be 'BGR' or 'RGB'")
         self.mode = mode
+        self.decode_images = decode_images
 
     def convert_obj(self, obj):
         if isinstance(obj, dict):
             out = {}
             for key, value in obj.items():
                 nkey = key.decode() if isinstance(key, bytes) else key
-                if nkey == 'img':
+                if nkey == 'img' and not self.decode_images:
+                    out[nkey] = value
+                elif nkey == 'img':
+                    from PIL import Image
                     img = np.array(Image.open(io.BytesIO(value)).convert('RGB'))      # uint8 [H, W, 3]
                     out[nkey] = np.ascontiguousarray(img[:, :, ::-1]) if self.mode == 'BGR' else img
                 else:
@@ -56,9 +61,18 @@ class UnpackMsgpackData(object):
         return meta
 
 
-def records_to_batch(records, pipeline, text_key='gt', mode='BGR'):
+def records_to_batch(records, pipeline, text_key='gt', mode='BGR', decode='host'):
     """Decode a list of msgpack records and hand them to a `DevicePipeline`: returns what `pipeline.process` returns
-    ({'image': f32 [N,3,H,W] on the GPU, 'label', 'length'})."""
-    unpack = UnpackMsgpackData(mode=mode)
+    ({'image': f32 [N,3,H,W] on the GPU, 'label', 'length'}).  decode='device': the images stay encoded on the host and
+    `pipeline` must be an `EncodedDevicePipeline` (BGR only: the pipeline's mean is)."""
+    if decode not in ('host', 'device'):
+        raise ValueError("decode must be 'host' or 'device'")
+    if decode == 'device':
+        from .device_pipeline import EncodedDevicePipeline
+        if not isinstance(pipeline, EncodedDevicePipeline):
+            raise TypeError("records_to_batch(decode='device') needs an EncodedDevicePipeline")
+        if mode != 'BGR':
+            raise ValueError("records_to_batch(decode='device') decodes to BGR")
+    unpack = UnpackMsgpackData(mode=mode, decode_images=decode == 'host')
     items = [unpack.convert(r) for r in records]
     return pipeline.process([it['img'] for it in items], [it.get(text_key, '') for it in items])
