@@ -29,8 +29,6 @@
 
 namespace mr {
 
-#define CTCA_NEG_INF (-__builtin_inff())
-
 enum { CTCA_LDS_WORDS = 4096 };   // back-pointer words (16 KiB) a row may keep in LDS
 
 // register slots of a lane for a string of K symbols (K + 1 pairs of positions), and 32-bit back-pointer words per row
@@ -40,26 +38,15 @@ __host__ __device__ inline long long ctca_row_words(int T, int K) {
   return (long long)((T + cpw - 1) / cpw) * 64;
 }
 
-// lane l <- lane l - 1 (DPP wave_shr:1, no LDS); lane 0 keeps `first`
-__device__ __forceinline__ float ctca_from_lane_below(float v, float first, int lane) {
-  const int got = __builtin_amdgcn_update_dpp(__float_as_int(CTCA_NEG_INF), __float_as_int(v), 0x138, 0xf, 0xf, false);
-  return lane == 0 ? first : __int_as_float(got);
-}
-
-template <typename PT>
-__device__ __forceinline__ float ctca_lp(const PT* p, long long off, bool log_probs) {
-  return ctc_lp(to_f32(p[off]), log_probs);
-}
-
 // A row that is unalignable or has no alignment of non-zero probability
 __device__ __forceinline__ void ctca_fill_dead(int T, int S, float* score, int* pos, int* begin, int* end, float* sym_lp,
                                                int* peak) {
   const int lane = threadIdx.x;
   for (int t = lane; t < T; t += 64) pos[t] = -1;
   for (int i = lane; i < S; i += 64) {
-    begin[i] = -1; end[i] = -1; peak[i] = -1; sym_lp[i] = CTCA_NEG_INF;
+    begin[i] = -1; end[i] = -1; peak[i] = -1; sym_lp[i] = CTC_NEG_INF;
   }
-  if (lane == 0) *score = CTCA_NEG_INF;
+  if (lane == 0) *score = CTC_NEG_INF;
 }
 
 // The row's recursion, back-trace and outputs with NS slots per lane (K < 64 * NS); every pointer is the row's own.  The target
@@ -82,7 +69,7 @@ __device__ bool ctca_row(const PT* row, long long sc, long long st, int T, bool 
   }
   float B[NS], Y[NS];
 #pragma unroll
-  for (int j = 0; j < NS; ++j) B[j] = Y[j] = CTCA_NEG_INF;
+  for (int j = 0; j < NS; ++j) B[j] = Y[j] = CTC_NEG_INF;
   unsigned word = 0u;
   // the values of AHEAD columns: the symbols' per slot, the blank's one column per lane
   float v[NS][AHEAD], lb;
@@ -116,15 +103,15 @@ __device__ bool ctca_row(const PT* row, long long sc, long long st, int T, bool 
         if (u == 0 && t0 == 0) {
           if (lane == 0) {
             B[0] = lpb;
-            Y[0] = live[0] ? v[0][u] : CTCA_NEG_INF;
+            Y[0] = live[0] ? v[0][u] : CTC_NEG_INF;
           }
         } else {
           float Yb[NS];   // Y_{i-1} of the column before, for every slot, before any is overwritten
 #pragma unroll
           for (int j = 0; j < NS; ++j) {
-            float first = CTCA_NEG_INF;
+            float first = CTC_NEG_INF;
             if (j > 0) first = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Y[j > 0 ? j - 1 : 0]), 63));
-            Yb[j] = ctca_from_lane_below(Y[j], first, lane);
+            Yb[j] = ctc_from_lane_below(Y[j], first, lane);
           }
           unsigned codes = 0u;
 #pragma unroll
@@ -138,7 +125,7 @@ __device__ bool ctca_row(const PT* row, long long sc, long long st, int T, bool 
             if (B[j] > my) { my = B[j]; cy = 1u; }
             if (hop[j] && Yb[j] > my) { my = Yb[j]; cy = 2u; }
             B[j] = lpb + mb;
-            Y[j] = live[j] ? v[j][u] + my : CTCA_NEG_INF;
+            Y[j] = live[j] ? v[j][u] + my : CTC_NEG_INF;
             codes |= (cy | (cb << 2)) << (4 * j);
           }
           word |= codes << (BITS * (u & (CPW - 1)));
@@ -174,11 +161,11 @@ __device__ bool ctca_row(const PT* row, long long sc, long long st, int T, bool 
     if (K >= 1 && ((K - 1) >> 6) == j) ysel = Y[j];
   }
   const float dB = __shfl(bsel, K & 63, 64);
-  const float dY = K >= 1 ? __shfl(ysel, (K - 1) & 63, 64) : CTCA_NEG_INF;
+  const float dY = K >= 1 ? __shfl(ysel, (K - 1) & 63, 64) : CTC_NEG_INF;
   // (the same on every lane; readfirstlane tells the compiler so, and the walk below stays in scalar registers)
   int s = __builtin_amdgcn_readfirstlane(K == 0 ? 0 : (dB >= dY ? 2 * K : 2 * K - 1));
   const float best = (K == 0 || dB >= dY) ? dB : dY;
-  if (!(best > CTCA_NEG_INF)) return false;
+  if (!(best > CTC_NEG_INF)) return false;
 
   // back-trace: one path, walked by the scalar unit; the lanes watch it for what is theirs
   int bg[NS], en[NS];
@@ -217,10 +204,10 @@ __device__ bool ctca_row(const PT* row, long long sc, long long st, int T, bool 
   for (int j = 0; j < NS; ++j) {
     const int i = lane + 64 * j;
     if (i < K) {
-      float acc = CTCA_NEG_INF, top = CTCA_NEG_INF;
+      float acc = CTC_NEG_INF, top = CTC_NEG_INF;
       int pk = -1;
       for (int t = bg[j]; t < en[j]; ++t) {
-        const float lp = ctca_lp(ps[j], (long long)t * st, log_probs);
+        const float lp = ctc_lp_at(ps[j], st, t, log_probs);
         if (t == bg[j]) {
           acc = lp; top = lp; pk = t;
         } else {
@@ -232,7 +219,7 @@ __device__ bool ctca_row(const PT* row, long long sc, long long st, int T, bool 
     }
   }
   for (int i = K + lane; i < S; i += 64) {
-    begin[i] = -1; end[i] = -1; peak[i] = -1; sym_lp[i] = CTCA_NEG_INF;
+    begin[i] = -1; end[i] = -1; peak[i] = -1; sym_lp[i] = CTC_NEG_INF;
   }
   if (lane == 0) *score = best;
   return true;
@@ -304,29 +291,18 @@ int mr_ctc_align(int dtype, const void* pred, long long sn, long long sc, long l
   MR_CHECK_ARG(N >= 0, "mr_ctc_align: N=%d rows", N);
   MR_CHECK_ARG(S >= 0 && S <= MR_CTC_ALIGN_MAX_SYMBOLS, "mr_ctc_align: S=%d symbols per row (0..MR_CTC_ALIGN_MAX_SYMBOLS=%d)", S,
                MR_CTC_ALIGN_MAX_SYMBOLS);
-  MR_CHECK_ARG(T >= 1 && T <= MR_SEQ_MEASURE_MAX, "mr_ctc_align: T=%d columns (1..MR_SEQ_MEASURE_MAX=%d)", T, MR_SEQ_MEASURE_MAX);
-  MR_CHECK_ARG(C >= 2, "mr_ctc_align: C=%d classes (blank and one symbol are 2)", C);
-  MR_CHECK_ARG(blank >= 0 && blank < C, "mr_ctc_align: blank=%d is not a class of C=%d", blank, C);
-  if (dtype != MR_DTYPE_F32 && dtype != MR_DTYPE_BF16) {
-    mr::set_error("mr_ctc_align: bad dtype %d (0 = float32, 1 = bfloat16)", dtype);
-    return MR_ERR_DTYPE;
-  }
+  MR_CTC_TRY(ctc_check_columns("mr_ctc_align", T, MR_SEQ_MEASURE_MAX));
+  MR_CTC_TRY(ctc_check_classes("mr_ctc_align", C, blank));
+  MR_CTC_TRY(ctc_check_dtype("mr_ctc_align", dtype));
   if (N == 0) return MR_OK;
-  const long long need = ctca_ws_bytes(N, T, S);
-  MR_CHECK_ARG(need > 0, "mr_ctc_align: N=%d T=%d S=%d need a workspace above 2 GiB: split the batch", N, T, S);
-  MR_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 7) == 0,
-               "mr_ctc_align: workspace %p of %lld bytes; mr_ctc_align_ws_bytes asks for %lld, 8-byte aligned", ws, ws_bytes, need);
+  MR_CTC_TRY(ctc_check_workspace("mr_ctc_align", "mr_ctc_align_ws_bytes", ws, ws_bytes, ctca_ws_bytes(N, T, S)));
   MR_CHECK_ARG(pred && target_len && score && pos && (S == 0 || (targets && begin && end && sym_lp && peak)),
                "mr_ctc_align: null pointer");
   const long long row_words = ctca_row_words(T, S);
-  if (dtype == MR_DTYPE_F32)
-    hipLaunchKernelGGL(ctc_align_kernel<float>, dim3((unsigned)N), dim3(64), 0, stream, (const float*)pred, sn, sc, st, C, T,
-                       log_probs, blank, unknown, targets, S, target_len, score, pos, begin, end, sym_lp, peak, (unsigned*)ws,
-                       row_words);
-  else
-    hipLaunchKernelGGL(ctc_align_kernel<bf16_t>, dim3((unsigned)N), dim3(64), 0, stream, (const bf16_t*)pred, sn, sc, st, C, T,
-                       log_probs, blank, unknown, targets, S, target_len, score, pos, begin, end, sym_lp, peak, (unsigned*)ws,
-                       row_words);
+  MR_CTC_DISPATCH(dtype, PT,
+                  hipLaunchKernelGGL(ctc_align_kernel<PT>, dim3((unsigned)N), dim3(64), 0, stream, (const PT*)pred, sn, sc, st, C,
+                                     T, log_probs, blank, unknown, targets, S, target_len, score, pos, begin, end, sym_lp, peak,
+                                     (unsigned*)ws, row_words));
   MR_CHECK_LAUNCH();
   return MR_OK;
 }

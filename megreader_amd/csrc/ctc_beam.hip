@@ -27,47 +27,11 @@
 
 namespace mr {
 
-typedef unsigned long long u64;
-
 enum {
   CTCB_STAGE_MAX = 8192,   // classes up to which the column kernel keeps the column's logs in LDS (32 KiB)
   CTCB_AHEAD = 8,          // loads a lane of the column kernel issues before it takes the first log
 };
-
-#define CTCB_NEG_INF (-__builtin_inff())
-
-// as lex_lse2 (lexicon.hip): shifted by the greater term, -inf when both are (the select drops the NaN of -inf - -inf)
-__device__ __forceinline__ float ctcb_lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  const float r = m + __logf(__expf(a - m) + __expf(b - m));
-  return m == CTCB_NEG_INF ? m : r;
-}
-
-// lp[t, c] as the header defines it: the value itself, or the f32 nearest to the f64 log of the probability
-template <typename PT>
-__device__ __forceinline__ float ctcb_lp(const PT* col, long long sc, int c, bool log_probs) {
-  return ctc_lp(to_f32(col[(long long)c * sc]), log_probs);
-}
-
-__device__ __forceinline__ unsigned ctcb_ordered(float x) {
-  const unsigned u = __float_as_uint(x == 0.f ? 0.f : x);   // (-0 and +0 are one value)
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ctcb_unordered(unsigned u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-// greater key = greater value, then lower index; 0 = "no candidate" (-inf never makes a key)
-__device__ __forceinline__ u64 ctcb_key(float v, unsigned index) {
-  return v > CTCB_NEG_INF ? ((u64)ctcb_ordered(v) << 32) | (u64)(0xffffffffu - index) : 0ull;
-}
-__device__ __forceinline__ u64 ctcb_wave_max(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
+constexpr bool CTCB_MERGE_ZEROS = true;   // ctc_key: -0 and +0 are one value in every key of this file (ctc_posterior.h says why)
 
 template <typename PT>
 __global__ __launch_bounds__(64) void ctc_beam_columns_kernel(const PT* pred, long long sn, long long sc, long long st, int C,
@@ -94,21 +58,21 @@ __global__ __launch_bounds__(64) void ctc_beam_columns_kernel(const PT* pred, lo
       if (c < C) {
         const float lp = ctc_lp(v[u], log_probs != 0);
         if (staged) ctcb_col[c] = lp;
-        const u64 k = (c != blank && c != unknown) ? ctcb_key(lp, (unsigned)c) : 0ull;
+        const u64 k = (c != blank && c != unknown) ? ctc_key(lp, (unsigned)c, CTCB_MERGE_ZEROS) : 0ull;
         mine = k > mine ? k : mine;
       }
     }
   }
   u64 got = 0ull;
   for (int j = 0; j < Kc; ++j) {
-    const u64 w = ctcb_wave_max(mine);
+    const u64 w = ctc_wave_max(mine);
     if (w == 0ull) break;   // (wave-uniform) fewer eligible classes than Kc
     if (lane == j) got = w;
     if (mine == w) {        // keys are distinct: one lane.  Its next best below w
       u64 m = 0ull;
       for (int c = lane; c < C; c += 64) {
-        const float lp = staged ? ctcb_col[c] : ctcb_lp(col, sc, c, log_probs);
-        const u64 k = (c != blank && c != unknown) ? ctcb_key(lp, (unsigned)c) : 0ull;
+        const float lp = staged ? ctcb_col[c] : ctc_lp_at(col, sc, c, log_probs != 0);
+        const u64 k = (c != blank && c != unknown) ? ctc_key(lp, (unsigned)c, CTCB_MERGE_ZEROS) : 0ull;
         if (k < w && k > m) m = k;
       }
       mine = m;
@@ -118,7 +82,7 @@ __global__ __launch_bounds__(64) void ctc_beam_columns_kernel(const PT* pred, lo
   if (lane < Kc) {
     const int c = (int)(0xffffffffu - (unsigned)(got & 0xffffffffull));
     // the value as it was read, not the one rebuilt from the key (which made -0 a +0)
-    const float lp = got ? (staged ? ctcb_col[c] : ctcb_lp(col, sc, c, log_probs)) : CTCB_NEG_INF;
+    const float lp = got ? (staged ? ctcb_col[c] : ctc_lp_at(col, sc, c, log_probs != 0)) : CTC_NEG_INF;
     sym_id[column * Kc + lane] = got ? c : -1;
     sym_lp[column * Kc + lane] = lp;
   }
@@ -156,15 +120,15 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const PT* pred, long long 
   u64* tab = tables + (long long)n * slots;
   for (unsigned i = lane; i < slots; i += 64) tab[i] = 0ull;
   // beam entry `lane`: the start state is the empty prefix alone
-  float pb = lane == 0 ? 0.f : CTCB_NEG_INF, pnb = CTCB_NEG_INF, tot = pb;
+  float pb = lane == 0 ? 0.f : CTC_NEG_INF, pnb = CTC_NEG_INF, tot = pb;
   int last = -1, len = 0, node = 0, par = -1, nb = 1;
   __syncthreads();   // the zeroed table has landed before the first compare-and-swap
   for (int t = 0; t < T; ++t) {
     const PT* col = pred + (long long)n * sn + (long long)t * st;
     const long long list = ((long long)n * T + t) * Kc;
     const int cid = lane < Kc ? sym_id[list + lane] : -1;
-    const float clp = lane < Kc ? sym_lp[list + lane] : CTCB_NEG_INF;
-    const float lpb = ctcb_lp(col, sc, blank, log_probs);
+    const float clp = lane < Kc ? sym_lp[list + lane] : CTC_NEG_INF;
+    const float lpb = ctc_lp_at(col, sc, blank, log_probs != 0);
     const int kc = __popcll(__ballot(cid >= 0));   // the eligible ones come first
     b_pb[lane] = pb; b_pnb[lane] = pnb; b_tot[lane] = tot;
     b_last[lane] = last; b_len[lane] = len; b_node[lane] = node; b_par[lane] = par;
@@ -175,32 +139,32 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const PT* pred, long long 
     int merged = -1;
     if (lane < nb) {
       const float npb = tot + lpb;
-      float npnb = CTCB_NEG_INF;
+      float npnb = CTC_NEG_INF;
       if (len > 0) {
         int jl = -1;
         for (int j = 0; j < kc; ++j)
           if (c_id[j] == last) jl = j;
-        npnb = pnb + (jl >= 0 ? c_lp[jl] : ctcb_lp(col, sc, last, log_probs));   // the same bits either way
+        npnb = pnb + (jl >= 0 ? c_lp[jl] : ctc_lp_at(col, sc, last, log_probs != 0));   // the same bits either way
         if (jl >= 0) {
           int p = -1;
           for (int i = 0; i < nb; ++i)
             if (b_node[i] == par) p = i;
           if (p >= 0) {
             const float from = (b_len[p] > 0 && b_last[p] == last) ? b_pb[p] : b_tot[p];
-            npnb = ctcb_lse2(npnb, from + c_lp[jl]);
+            npnb = ctc_lse2(npnb, from + c_lp[jl]);
             merged = p * kc + jl;
           }
         }
       }
       s_pb[lane] = npb; s_pnb[lane] = npnb;
-      key = ctcb_key(ctcb_lse2(npb, npnb), (unsigned)lane);
+      key = ctc_key(ctc_lse2(npb, npnb), (unsigned)lane, CTCB_MERGE_ZEROS);
     }
     keys[lane] = key;
     const int ne = nb * kc;
     for (int e = lane; e < ne; e += 64) {
       const int p = e / kc, j = e - p * kc;
       const float from = (b_len[p] > 0 && b_last[p] == c_id[j]) ? b_pb[p] : b_tot[p];
-      keys[64 + e] = ctcb_key(from + c_lp[j], (unsigned)(64 + e));
+      keys[64 + e] = ctc_key(from + c_lp[j], (unsigned)(64 + e), CTCB_MERGE_ZEROS);
     }
     __syncthreads();
     if (merged >= 0) keys[64 + merged] = 0ull;
@@ -211,7 +175,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const PT* pred, long long 
     u64 got = 0ull;
     int kept = 0;
     for (int r = 0; r < B; ++r) {
-      const u64 w = ctcb_wave_max(mine);
+      const u64 w = ctc_wave_max(mine);
       if (w == 0ull) break;   // (wave-uniform) nothing finite is left
       if (lane == r) got = w;
       ++kept;
@@ -227,16 +191,16 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const PT* pred, long long 
     nb = kept;
     if (lane < nb) {
       const int idx = (int)(0xffffffffu - (unsigned)(got & 0xffffffffull));
-      tot = ctcb_unordered((unsigned)(got >> 32));
+      tot = ctc_unordered((unsigned)(got >> 32));
       if (idx < 64) {
         pb = s_pb[idx]; pnb = s_pnb[idx]; last = b_last[idx]; len = b_len[idx]; node = b_node[idx]; par = b_par[idx];
       } else {
         const int e = idx - 64, p = e / kc, j = e - p * kc;
-        pb = CTCB_NEG_INF; pnb = tot; last = c_id[j]; len = b_len[p] + 1; par = b_node[p];
+        pb = CTC_NEG_INF; pnb = tot; last = c_id[j]; len = b_len[p] + 1; par = b_node[p];
         node = ctcb_find_or_create(tab, slots, par, last);
       }
     } else {
-      pb = pnb = tot = CTCB_NEG_INF; last = -1; len = 0; node = 0; par = -1;
+      pb = pnb = tot = CTC_NEG_INF; last = -1; len = 0; node = 0; par = -1;
     }
     __syncthreads();   // every read of the old beam is done before the next column overwrites it
   }
@@ -245,7 +209,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const PT* pred, long long 
   b_len[lane] = have ? len : 0;
   if (lane < K) {
     lengths[(long long)n * K + lane] = have ? len : 0;
-    scores[(long long)n * K + lane] = have ? tot : CTCB_NEG_INF;
+    scores[(long long)n * K + lane] = have ? tot : CTC_NEG_INF;
   }
   if (lane == 0) count[n] = min(nb, K);
   __syncthreads();
@@ -288,26 +252,17 @@ int mr_ctc_beam_search(int dtype, const void* pred, long long sn, long long sc, 
                        int blank, int unknown, int beam, int nbest, int top_classes, int* ids, int* lengths, float* scores,
                        int* count, void* ws, long long ws_bytes, hipStream_t stream) {
   MR_CHECK_ARG(N >= 0, "mr_ctc_beam_search: N=%d rows", N);
-  MR_CHECK_ARG(T >= 1 && T <= MR_SEQ_MEASURE_MAX, "mr_ctc_beam_search: T=%d columns (1..MR_SEQ_MEASURE_MAX=%d)", T,
-               MR_SEQ_MEASURE_MAX);
-  MR_CHECK_ARG(C >= 2, "mr_ctc_beam_search: C=%d classes (blank and one symbol are 2)", C);
-  MR_CHECK_ARG(blank >= 0 && blank < C, "mr_ctc_beam_search: blank=%d is not a class of C=%d", blank, C);
+  MR_CTC_TRY(ctc_check_columns("mr_ctc_beam_search", T, MR_SEQ_MEASURE_MAX));
+  MR_CTC_TRY(ctc_check_classes("mr_ctc_beam_search", C, blank));
   MR_CHECK_ARG(beam >= 1 && beam <= MR_CTC_BEAM_MAX, "mr_ctc_beam_search: beam=%d (1..MR_CTC_BEAM_MAX=%d)", beam,
                MR_CTC_BEAM_MAX);
   MR_CHECK_ARG(nbest >= 1 && nbest <= beam, "mr_ctc_beam_search: nbest=%d (1..beam=%d)", nbest, beam);
   MR_CHECK_ARG(top_classes >= 1 && top_classes <= MR_CTC_BEAM_TOP_MAX,
                "mr_ctc_beam_search: top_classes=%d (1..MR_CTC_BEAM_TOP_MAX=%d)", top_classes, MR_CTC_BEAM_TOP_MAX);
-  if (dtype != MR_DTYPE_F32 && dtype != MR_DTYPE_BF16) {
-    mr::set_error("mr_ctc_beam_search: bad dtype %d (0 = float32, 1 = bfloat16)", dtype);
-    return MR_ERR_DTYPE;
-  }
+  MR_CTC_TRY(ctc_check_dtype("mr_ctc_beam_search", dtype));
   if (N == 0) return MR_OK;
-  const long long need = ctcb_ws_bytes(N, T, beam, top_classes);
-  MR_CHECK_ARG(need > 0, "mr_ctc_beam_search: N=%d T=%d beam=%d top_classes=%d need a workspace above 2 GiB: split the batch", N,
-               T, beam, top_classes);
-  MR_CHECK_ARG(ws && ws_bytes >= need && ((uintptr_t)ws & 7) == 0,
-               "mr_ctc_beam_search: workspace %p of %lld bytes; mr_ctc_beam_ws_bytes asks for %lld, 8-byte aligned", ws, ws_bytes,
-               need);
+  MR_CTC_TRY(ctc_check_workspace("mr_ctc_beam_search", "mr_ctc_beam_ws_bytes", ws, ws_bytes,
+                                 ctcb_ws_bytes(N, T, beam, top_classes)));
   MR_CHECK_ARG(pred && ids && lengths && scores && count, "mr_ctc_beam_search: null pointer");
   MR_CHECK_ARG((long long)N * T <= INT_MAX, "mr_ctc_beam_search: N=%d rows x T=%d columns exceed the grid", N, T);
   const long long cells = (long long)N * T * top_classes;
@@ -318,17 +273,12 @@ int mr_ctc_beam_search(int dtype, const void* pred, long long sn, long long sc, 
   const int staged = C <= CTCB_STAGE_MAX;
   const size_t lds = staged ? (size_t)C * sizeof(float) : 0;
   const int Kc = top_classes;
-  if (dtype == MR_DTYPE_F32) {
-    hipLaunchKernelGGL(ctc_beam_columns_kernel<float>, dim3((unsigned)(N * T)), dim3(64), lds, stream, (const float*)pred, sn, sc,
-                       st, C, T, log_probs, blank, unknown, Kc, staged, sym_id, sym_lp);
-    hipLaunchKernelGGL(ctc_beam_kernel<float>, dim3(N), dim3(64), 0, stream, (const float*)pred, sn, sc, st, C, T, log_probs, blank,
-                       beam, nbest, Kc, sym_id, sym_lp, tables, slots, ids, lengths, scores, count);
-  } else {
-    hipLaunchKernelGGL(ctc_beam_columns_kernel<bf16_t>, dim3((unsigned)(N * T)), dim3(64), lds, stream, (const bf16_t*)pred, sn,
-                       sc, st, C, T, log_probs, blank, unknown, Kc, staged, sym_id, sym_lp);
-    hipLaunchKernelGGL(ctc_beam_kernel<bf16_t>, dim3(N), dim3(64), 0, stream, (const bf16_t*)pred, sn, sc, st, C, T, log_probs,
-                       blank, beam, nbest, Kc, sym_id, sym_lp, tables, slots, ids, lengths, scores, count);
-  }
+  MR_CTC_DISPATCH(dtype, PT,
+                  hipLaunchKernelGGL(ctc_beam_columns_kernel<PT>, dim3((unsigned)(N * T)), dim3(64), lds, stream, (const PT*)pred,
+                                     sn, sc, st, C, T, log_probs, blank, unknown, Kc, staged, sym_id, sym_lp);
+                  hipLaunchKernelGGL(ctc_beam_kernel<PT>, dim3(N), dim3(64), 0, stream, (const PT*)pred, sn, sc, st, C, T,
+                                     log_probs, blank, beam, nbest, Kc, sym_id, sym_lp, tables, slots, ids, lengths, scores,
+                                     count));
   MR_CHECK_LAUNCH();
   return MR_OK;
 }

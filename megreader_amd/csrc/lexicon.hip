@@ -35,8 +35,6 @@
 
 namespace mr {
 
-typedef unsigned long long u64;
-
 enum {
   LEX_BLOCK = 256,        // threads per workgroup: 4 waves share one Peq table
   LEX_STAGE_MAX = 8192,   // f32 entries (32 KiB of LDS) up to which mr_lexicon_transcribe stages a row's log-probabilities
@@ -218,27 +216,6 @@ __global__ __launch_bounds__(256) void lexicon_nearest_kernel(const int* preds, 
 
 // ---- mr_lexicon_transcribe ----
 
-#define LEX_NEG_INF (-__builtin_inff())
-
-// log(exp(a) + exp(b) [+ exp(c)]) shifted by the maximum; every term -inf gives -inf (the select drops the NaN of -inf - -inf).
-// The hardware exp2 / log2: their error (a few 1e-7 absolute per step) is far below the rounding of alpha at its magnitude.
-__device__ __forceinline__ float lex_lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  const float r = m + __logf(__expf(a - m) + __expf(b - m));
-  return m == LEX_NEG_INF ? m : r;
-}
-__device__ __forceinline__ float lex_lse3(float a, float b, float c) {
-  const float m = fmaxf(fmaxf(a, b), c);
-  const float r = m + __logf(__expf(a - m) + __expf(b - m) + __expf(c - m));
-  return m == LEX_NEG_INF ? m : r;
-}
-
-// lane i <- lane i - 1 (DPP wave_shr:1, no LDS); the first lane of a word's group (gl == 0) <- -inf
-__device__ __forceinline__ float lex_from_lane_below(float v, int gl) {
-  const int got = __builtin_amdgcn_update_dpp(__float_as_int(LEX_NEG_INF), __float_as_int(v), 0x138, 0xf, 0xf, false);
-  return gl == 0 ? LEX_NEG_INF : __int_as_float(got);
-}
-
 // score(n, l) by W = 64 or 16 lanes: row = pred + n*sn, the word's K symbols at sym -- per lane, the same for the W lanes of a
 // group; K < 0: the group has no word.  With W = 16 the wave scores four words of at most 15 symbols side by side (positions
 // 0..2K on lanes 0..K of the group); the lanes do the same arithmetic either way, so a score does not depend on W.  A pure
@@ -258,7 +235,7 @@ __device__ float lex_ctc_score(const PT* row, long long sc, long long st, int T,
   const bool bad = gl < K && (c == unknown || (unsigned)c >= (unsigned)C);
   const u64 group = W == 64 ? ~0ull : ((1ull << (W & 63)) - 1ull) << g0;
   const bool dead = K < 0 || (__ballot(bad) & group) != 0ull || K + __popcll(__ballot(twin) & group) > T;
-  if (__ballot(!dead) == 0ull) return LEX_NEG_INF;
+  if (__ballot(!dead) == 0ull) return CTC_NEG_INF;
   const bool live = gl < K && !dead;
   const bool hop = live && gl >= 1 && c != below;              // the s - 2 term: from the symbol before, over the blank
   const PT* ps = row + (long long)(live ? c : blank) * sc;     // (idle lanes read the blank's values and drop them)
@@ -266,7 +243,7 @@ __device__ float lex_ctc_score(const PT* row, long long sc, long long st, int T,
   const float* ls = lpt ? lpt + (live ? c : blank) * (T | 1) : nullptr;
   const float* lb_row = lpt ? lpt + blank * (T | 1) : nullptr;
   // the state before column 0: all mass "before the first blank"
-  float B = gl == 0 ? 0.f : LEX_NEG_INF, Y = LEX_NEG_INF, E = LEX_NEG_INF;
+  float B = gl == 0 ? 0.f : CTC_NEG_INF, Y = CTC_NEG_INF, E = CTC_NEG_INF;
   for (int t0 = 0; t0 < T; t0 += LEX_AHEAD) {
     const int nt = min((int)LEX_AHEAD, T - t0);
     float v[LEX_AHEAD], lb;
@@ -298,13 +275,13 @@ __device__ float lex_ctc_score(const PT* row, long long sc, long long st, int T,
     for (int j = 0; j < LEX_AHEAD; ++j) {
       if (j < nt) {   // (wave-uniform)
         const float lpb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lb), j));
-        const float lps = live ? v[j] : LEX_NEG_INF;
-        const float Yb = lex_from_lane_below(Y, gl);
+        const float lps = live ? v[j] : CTC_NEG_INF;
+        const float Yb = ctc_from_lane_below(Y, CTC_NEG_INF, gl);   // the first lane of a word's group takes -inf
         if constexpr (W == 64) {
-          if (K == MR_LEXICON_MAX_WORD) E = lpb + lex_lse2(E, Y);   // (K is wave-uniform here)
+          if (K == MR_LEXICON_MAX_WORD) E = lpb + ctc_lse2(E, Y);   // (K is wave-uniform here)
         }
-        const float nB = lpb + lex_lse2(B, Yb);
-        Y = lps + lex_lse3(Y, B, hop ? Yb : LEX_NEG_INF);
+        const float nB = lpb + ctc_lse2(B, Yb);
+        Y = lps + ctc_lse3(Y, B, hop ? Yb : CTC_NEG_INF);
         B = nB;
       }
     }
@@ -320,23 +297,14 @@ __device__ float lex_ctc_score(const PT* row, long long sc, long long st, int T,
   } else {
     tail = __shfl(B, g0 + min(Kc, W - 1), 64);
   }
-  const float score = Kc == 0 ? first : lex_lse2(tail, last);
-  return dead ? LEX_NEG_INF : score;
+  const float score = Kc == 0 ? first : ctc_lse2(tail, last);
+  return dead ? CTC_NEG_INF : score;
 }
 
-// order-preserving u32 of an f32 and back
-__device__ __forceinline__ unsigned lex_ordered(float x) {
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float lex_unordered(unsigned u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-// One scored candidate: its cell of the table, and the lane's best key (ordered score bits << 32 | ~index).
+// One scored candidate: its cell of the table, and the lane's best key (the score's bits as they are: ctc_posterior.h)
 __device__ __forceinline__ void lex_post(int w, float score, float* table, u64& best) {
   if (table) table[w] = score;
-  if (score > LEX_NEG_INF) best = max(best, ((u64)lex_ordered(score) << 32) | (u64)(0xffffffffu - (unsigned)w));
+  best = max(best, ctc_key(score, (unsigned)w, false));
 }
 
 // Up to four words of one row by one wave: the 16 lanes of group q hold word w at lex_sym + o, K symbols (K < 0: none).  Four at
@@ -410,8 +378,7 @@ __global__ __launch_bounds__(256) void lexicon_transcribe_kernel(const PT* pred,
     const int pitch = T | 1;
     for (int i = tid; i < C * T; i += LEX_BLOCK) {
       const int c = i / T, t = i - c * T;
-      const float v = to_f32(row[(long long)c * sc + (long long)t * st]);
-      lpt[c * pitch + t] = log_probs ? v : ctc_log_prob(v);
+      lpt[c * pitch + t] = ctc_lp(to_f32(row[(long long)c * sc + (long long)t * st]), log_probs != 0);
     }
   }
   int nd;
@@ -464,12 +431,8 @@ __global__ __launch_bounds__(256) void lexicon_transcribe_kernel(const PT* pred,
     }
     if (lane == 0 && count) atomicAdd(n_cand + n, count);
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const u64 other = __shfl_xor(best, d, 64);
-    best = other > best ? other : best;
-  }
-  if (lane == 0 && best != 0ull) atomicMax(keys + n, best);
+  const u64 top = ctc_wave_max(best);
+  if (lane == 0 && top != 0ull) atomicMax(keys + n, top);
 }
 
 // One thread per row: the winner out of the key, and its edit distance to the row.  The word (<= 64 symbols) is the pattern, the
@@ -483,13 +446,13 @@ __global__ __launch_bounds__(256) void lexicon_transcribe_unpack_kernel(const u6
   const u64 k = keys[i];
   if (k == 0ull) {
     best_index[i] = -1;
-    best_score[i] = LEX_NEG_INF;
+    best_score[i] = CTC_NEG_INF;
     best_dist[i] = -1;
     return;
   }
   const int w = (int)(0xffffffffu - (unsigned)(k & 0xffffffffull));
   best_index[i] = w;
-  best_score[i] = lex_unordered((unsigned)(k >> 32));
+  best_score[i] = ctc_unordered((unsigned)(k >> 32));
   const int o0 = lex_off[w];
   const int len = min(max(lex_off[w + 1] - o0, 0), MR_LEXICON_MAX_WORD);
   const int* sym = lex_sym + o0;
@@ -544,21 +507,20 @@ static u64* lexicon_keys(const char* who, int N, hipStream_t stream) {
   return buf[dev];
 }
 
-template <bool DENSE, typename PT>
-static int launch_transcribe(const void* pred, long long sn, long long sc, long long st, int T, int log_probs, const int* preds,
-                             int S, int N, int blank, int unknown, const int* fold, const int* lex_sym, const int* lex_off, int L,
-                             const int* span, int C, int max_distance, int chunks, int stage, size_t lds, size_t lds_max, u64* keys,
-                             int* pred_len, int* n_cand, float* all_scores, hipStream_t stream) {
-  const int rc = ensure_dynamic_lds(lexicon_transcribe_kernel<DENSE, PT>, lds_max);
+template <typename PT>
+static int launch_transcribe(bool dense, const PT* pred, long long sn, long long sc, long long st, int T, int log_probs,
+                             const int* preds, int S, int N, int blank, int unknown, const int* fold, const int* lex_sym,
+                             const int* lex_off, int L, const int* span, int C, int max_distance, int chunks, int stage, size_t lds,
+                             size_t lds_max, u64* keys, int* pred_len, int* n_cand, float* all_scores, hipStream_t stream) {
+  const auto kernel = dense ? lexicon_transcribe_kernel<true, PT> : lexicon_transcribe_kernel<false, PT>;
+  const int rc = ensure_dynamic_lds(kernel, lds_max);
   if (rc != MR_OK) return rc;
   // 16-byte loads of 16 columns of one class: f32, columns contiguous, and every (n, c) row 16-byte aligned
   const int vec = sizeof(PT) == 4 && st == 1 && sn % 4 == 0 && sc % 4 == 0 && (uintptr_t)pred % 16 == 0;
-  hipLaunchKernelGGL((lexicon_transcribe_kernel<DENSE, PT>), dim3(N * chunks), dim3(LEX_BLOCK), lds, stream, (const PT*)pred, sn,
-                     sc, st, T, log_probs, vec, stage, preds, S, N, blank, unknown, fold, lex_sym, lex_off, L, span, C, max_distance,
-                     chunks, keys, pred_len, n_cand, all_scores);
+  hipLaunchKernelGGL(kernel, dim3(N * chunks), dim3(LEX_BLOCK), lds, stream, pred, sn, sc, st, T, log_probs, vec, stage, preds, S, N,
+                     blank, unknown, fold, lex_sym, lex_off, L, span, C, max_distance, chunks, keys, pred_len, n_cand, all_scores);
   return MR_OK;
 }
-
 
 }  // namespace mr
 
@@ -607,15 +569,11 @@ int mr_lexicon_transcribe(int dtype, const void* pred, long long sn, long long s
                           float* best_score, int* best_dist, int* pred_len, int* n_cand, float* all_scores,
                           hipStream_t stream) {
   MR_CHECK_ARG(N >= 0 && S >= 0 && L >= 0, "mr_lexicon_transcribe: bad shape N=%d S=%d L=%d", N, S, L);
-  MR_CHECK_ARG(T >= 1, "mr_lexicon_transcribe: T=%d columns", T);
+  MR_CTC_TRY(ctc_check_columns("mr_lexicon_transcribe", T, 0));
   MR_CHECK_ARG(S <= MR_SEQ_MEASURE_MAX, "mr_lexicon_transcribe: S=%d exceeds MR_SEQ_MEASURE_MAX=%d ids per row", S,
                MR_SEQ_MEASURE_MAX);
-  MR_CHECK_ARG(C >= 2, "mr_lexicon_transcribe: C=%d classes (blank and unknown alone are 2)", C);
-  MR_CHECK_ARG(blank >= 0 && blank < C, "mr_lexicon_transcribe: blank=%d is not a class of C=%d", blank, C);
-  if (dtype != MR_DTYPE_F32 && dtype != MR_DTYPE_BF16) {
-    mr::set_error("mr_lexicon_transcribe: bad dtype %d (0 = float32, 1 = bfloat16)", dtype);
-    return MR_ERR_DTYPE;
-  }
+  MR_CTC_TRY(ctc_check_classes("mr_lexicon_transcribe", C, blank));
+  MR_CTC_TRY(ctc_check_dtype("mr_lexicon_transcribe", dtype));
   if (N == 0) return MR_OK;
   MR_CHECK_ARG(pred && best_index && best_score && best_dist && pred_len && n_cand && (S == 0 || preds) &&
                    (L == 0 || (lex_sym && lex_off)),
@@ -638,17 +596,12 @@ int mr_lexicon_transcribe(int dtype, const void* pred, long long sn, long long s
   if (all_scores && L > 0) {
     const long long count = (long long)N * L;
     hipLaunchKernelGGL(lexicon_fill_kernel, dim3((unsigned)min(cdivll(count, 256), 65536ll)), dim3(256), 0, stream, all_scores,
-                       count, LEX_NEG_INF);
+                       count, CTC_NEG_INF);
   }
   int rc;
-#define MR_LEX_GO(DENSE, PT)                                                                                                    \
-  launch_transcribe<DENSE, PT>(pred, sn, sc, st, T, log_probs, preds, S, N, blank, unknown, fold, lex_sym, lex_off, L, span, C, \
-                               max_distance, chunks, stage, lds, lds_max, keys, pred_len, n_cand, all_scores, stream)
-  if (dtype == MR_DTYPE_F32)
-    rc = dense ? MR_LEX_GO(true, float) : MR_LEX_GO(false, float);
-  else
-    rc = dense ? MR_LEX_GO(true, bf16_t) : MR_LEX_GO(false, bf16_t);
-#undef MR_LEX_GO
+  MR_CTC_DISPATCH(dtype, PT, rc = launch_transcribe(dense, (const PT*)pred, sn, sc, st, T, log_probs, preds, S, N, blank, unknown,
+                                                    fold, lex_sym, lex_off, L, span, C, max_distance, chunks, stage, lds, lds_max,
+                                                    keys, pred_len, n_cand, all_scores, stream));
   if (rc != MR_OK) return rc;
   hipLaunchKernelGGL(lexicon_transcribe_unpack_kernel, dim3(cdiv(N, 256)), dim3(256), 0, stream, keys, N, preds, S, blank, unknown,
                      fold, lex_sym, lex_off, C, best_index, best_score, best_dist);

@@ -9,22 +9,41 @@ from .._lib import _DEFINES, call, load, ptr, require_cuda
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float64: 2}
 
 
-def ctc_greedy_decode(pred, blank=0, unknown=1):
-    """pred: [N, C, 1, T] or [N, C, T] class scores on the GPU (f32 / bf16 / f64, any strides).
-    Returns (ids i32 [N, T] blank padded, lengths i32 [N])."""
-    require_cuda(pred)
-    if pred.dim() == 4:
-        if pred.shape[2] != 1:
-            raise RuntimeError("ctc_greedy_decode expects [N, C, 1, T]")
-        pred = pred.select(2, 0)           # CTCRepresenter: pred.select(1, 0) after the arg-max over C
-    if pred.dtype not in _DT:
-        raise TypeError("ctc_greedy_decode: unsupported dtype %s" % pred.dtype)
+def _posterior(pred, who, native=(torch.float32, torch.bfloat16), blank=None, t_max=None, error=RuntimeError):
+    """What every reader of a CTC posterior does first.  pred: [N, C, 1, T] or [N, C, T], any strides, else `error`; with `blank`
+    / `t_max` also the ValueErrors for a blank that is no class (or C < 2) and for T outside 1..t_max.  A dtype that `who`'s
+    entry point does not read (`native`) goes through f32 -- after the checks, so that no error comes behind a launch.
+    Returns (the [N, C, T] view, (N, C, T), its element strides (sn, sc, st), the library's dtype code)."""
+    if pred.dim() == 4 and pred.shape[2] == 1:
+        pred = pred.select(2, 0)               # CTCRepresenter: pred.select(1, 0) after the arg-max over C
+    if pred.dim() != 3:
+        raise error("%s expects [N, C, 1, T] or [N, C, T], got %s" % (who, tuple(pred.shape)))
     N, C, T = pred.shape
+    if blank is not None and (C < 2 or not 0 <= blank < C):
+        raise ValueError("%s: blank=%d is not one of C=%d classes (C >= 2)" % (who, blank, C))
+    if t_max is not None and not 1 <= T <= t_max:
+        raise ValueError("%s: T=%d columns, 1..%d are taken" % (who, T, t_max))
+    if pred.dtype not in native:
+        pred = pred.float()
+    return pred, (N, C, T), pred.stride(), _DT[pred.dtype]
+
+
+def _workspace(nbytes, who, sizes, device):
+    """The 8-byte aligned workspace of `nbytes`, the answer of the entry point's *_ws_bytes (0: more than it can address)."""
+    if nbytes <= 0:
+        raise ValueError("%s: %s need a workspace above 2 GiB; split the batch" % (who, sizes))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def ctc_greedy_decode(pred, blank=0, unknown=1):
+    """pred: [N, C, 1, T] or [N, C, T] class scores on the GPU (any strides; f32 / bf16 / f64 are read as they are, other types
+    go through f32).  Returns (ids i32 [N, T] blank padded, lengths i32 [N])."""
+    require_cuda(pred)
+    pred, (N, C, T), (sn, sc, st), code = _posterior(pred, "ctc_greedy_decode", native=tuple(_DT))
     out = torch.empty((N, T), dtype=torch.int32, device=pred.device)
     lengths = torch.empty((N,), dtype=torch.int32, device=pred.device)
-    sn, sc, st = pred.stride()
-    call("mr_ctc_greedy_decode", _DT[pred.dtype], ptr(pred), sn, sc, st, N, C, T, int(blank), int(unknown), ptr(out),
-         ptr(lengths))
+    with torch.cuda.device(pred.device):
+        call("mr_ctc_greedy_decode", code, ptr(pred), sn, sc, st, N, C, T, int(blank), int(unknown), ptr(out), ptr(lengths))
     return out, lengths
 
 
@@ -38,29 +57,16 @@ def ctc_beam_search_decode(pred, beam=8, nbest=1, top_classes=16, blank=0, unkno
     (descending; a lower bound of log p(string | pred), exact when nothing was pruned), count i32 [N] (hypotheses returned; slots
     past it: length 0, score -inf).  One call, no host work that depends on device data (capturable in a graph after one call
     outside); the workspace is a fresh tensor per call."""
-    if pred.dim() == 4:
-        if pred.shape[2] != 1:
-            raise RuntimeError("ctc_beam_search_decode expects [N, C, 1, T]")
-        pred = pred.select(2, 0)
-    if pred.dim() != 3:
-        raise RuntimeError("ctc_beam_search_decode expects [N, C, 1, T] or [N, C, T], got %d dimensions" % pred.dim())
-    N, C, T = pred.shape
-    defines = _DEFINES
+    who = "ctc_beam_search_decode"
     beam, nbest, top_classes, blank = int(beam), int(nbest), int(top_classes), int(blank)
-    if not 1 <= beam <= defines["MR_CTC_BEAM_MAX"]:
-        raise ValueError("ctc_beam_search_decode: beam must be in 1..%d, got %d" % (defines["MR_CTC_BEAM_MAX"], beam))
+    if not 1 <= beam <= _DEFINES["MR_CTC_BEAM_MAX"]:
+        raise ValueError("%s: beam must be in 1..%d, got %d" % (who, _DEFINES["MR_CTC_BEAM_MAX"], beam))
     if not 1 <= nbest <= beam:
-        raise ValueError("ctc_beam_search_decode: nbest must be in 1..beam=%d, got %d" % (beam, nbest))
-    if not 1 <= top_classes <= defines["MR_CTC_BEAM_TOP_MAX"]:
-        raise ValueError("ctc_beam_search_decode: top_classes must be in 1..%d, got %d"
-                         % (defines["MR_CTC_BEAM_TOP_MAX"], top_classes))
-    if C < 2 or not 0 <= blank < C:
-        raise ValueError("ctc_beam_search_decode: blank=%d is not one of C=%d classes (C >= 2)" % (blank, C))
-    if not 1 <= T <= defines["MR_SEQ_MEASURE_MAX"]:
-        raise ValueError("ctc_beam_search_decode: T=%d columns, 1..%d are taken" % (T, defines["MR_SEQ_MEASURE_MAX"]))
+        raise ValueError("%s: nbest must be in 1..beam=%d, got %d" % (who, beam, nbest))
+    if not 1 <= top_classes <= _DEFINES["MR_CTC_BEAM_TOP_MAX"]:
+        raise ValueError("%s: top_classes must be in 1..%d, got %d" % (who, _DEFINES["MR_CTC_BEAM_TOP_MAX"], top_classes))
+    pred, (N, C, T), (sn, sc, st), code = _posterior(pred, who, blank=blank, t_max=_DEFINES["MR_SEQ_MEASURE_MAX"])
     require_cuda(pred)
-    if pred.dtype not in (torch.float32, torch.bfloat16):
-        pred = pred.float()
     dev = pred.device
     ids = torch.empty((N, nbest, T), dtype=torch.int32, device=dev)
     lengths = torch.empty((N, nbest), dtype=torch.int32, device=dev)
@@ -69,14 +75,11 @@ def ctc_beam_search_decode(pred, beam=8, nbest=1, top_classes=16, blank=0, unkno
     out = {'ids': ids, 'lengths': lengths, 'scores': scores, 'count': count}
     if N == 0:
         return out
-    nbytes = load().mr_ctc_beam_ws_bytes(N, T, beam, top_classes)
-    if nbytes <= 0:
-        raise ValueError("ctc_beam_search_decode: N=%d T=%d beam=%d top_classes=%d need a workspace above 2 GiB; split the batch"
-                         % (N, T, beam, top_classes))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    sn, sc, st = pred.stride()
-    call("mr_ctc_beam_search", 0 if pred.dtype == torch.float32 else 1, ptr(pred), sn, sc, st, N, C, T, int(bool(log_probs)),
-         blank, int(unknown), beam, nbest, top_classes, ptr(ids), ptr(lengths), ptr(scores), ptr(count), ptr(ws), ws.numel() * 8)
+    ws = _workspace(load().mr_ctc_beam_ws_bytes(N, T, beam, top_classes), who,
+                    "N=%d T=%d beam=%d top_classes=%d" % (N, T, beam, top_classes), dev)
+    with torch.cuda.device(dev):
+        call("mr_ctc_beam_search", code, ptr(pred), sn, sc, st, N, C, T, int(bool(log_probs)), blank, int(unknown), beam, nbest,
+             top_classes, ptr(ids), ptr(lengths), ptr(scores), ptr(count), ptr(ws), ws.numel() * 8)
     return out
 
 
@@ -92,32 +95,20 @@ def ctc_forced_align(pred, targets, target_lengths, blank=0, unknown=1, log_prob
     -inf, -1.  A row that cannot be aligned (a symbol that is blank, `unknown` or no class, a length outside [0, S], more symbols
     than columns) or only through zero probabilities: score -inf, pos -1, every slot as one past the string.  One call, no host
     work that depends on device data (capturable in a graph); the workspace is a fresh tensor per call."""
-    if pred.dim() == 4:
-        if pred.shape[2] != 1:
-            raise RuntimeError("ctc_forced_align expects [N, C, 1, T]")
-        pred = pred.select(2, 0)
-    if pred.dim() != 3:
-        raise RuntimeError("ctc_forced_align expects [N, C, 1, T] or [N, C, T], got %d dimensions" % pred.dim())
-    N, C, T = pred.shape
-    defines = _DEFINES
+    who = "ctc_forced_align"
     blank = int(blank)
+    pred, (N, C, T), (sn, sc, st), code = _posterior(pred, who, blank=blank, t_max=_DEFINES["MR_SEQ_MEASURE_MAX"])
     if targets.dim() != 2 or targets.shape[0] != N:
-        raise ValueError("ctc_forced_align: targets must be [N=%d, S], got %s" % (N, tuple(targets.shape)))
+        raise ValueError("%s: targets must be [N=%d, S], got %s" % (who, N, tuple(targets.shape)))
     if tuple(target_lengths.shape) != (N,):
-        raise ValueError("ctc_forced_align: target_lengths must be [N=%d], got %s" % (N, tuple(target_lengths.shape)))
+        raise ValueError("%s: target_lengths must be [N=%d], got %s" % (who, N, tuple(target_lengths.shape)))
     S = targets.shape[1]
-    if S > defines["MR_CTC_ALIGN_MAX_SYMBOLS"]:
-        raise ValueError("ctc_forced_align: S=%d symbols per row, 0..%d are taken" % (S, defines["MR_CTC_ALIGN_MAX_SYMBOLS"]))
-    if C < 2 or not 0 <= blank < C:
-        raise ValueError("ctc_forced_align: blank=%d is not one of C=%d classes (C >= 2)" % (blank, C))
-    if not 1 <= T <= defines["MR_SEQ_MEASURE_MAX"]:
-        raise ValueError("ctc_forced_align: T=%d columns, 1..%d are taken" % (T, defines["MR_SEQ_MEASURE_MAX"]))
+    if S > _DEFINES["MR_CTC_ALIGN_MAX_SYMBOLS"]:
+        raise ValueError("%s: S=%d symbols per row, 0..%d are taken" % (who, S, _DEFINES["MR_CTC_ALIGN_MAX_SYMBOLS"]))
     require_cuda(pred, targets, target_lengths)
     if targets.device != pred.device or target_lengths.device != pred.device:
-        raise ValueError("ctc_forced_align: pred is on %s, targets on %s, target_lengths on %s"
-                         % (pred.device, targets.device, target_lengths.device))
-    if pred.dtype not in (torch.float32, torch.bfloat16):
-        pred = pred.float()
+        raise ValueError("%s: pred is on %s, targets on %s, target_lengths on %s"
+                         % (who, pred.device, targets.device, target_lengths.device))
     targets = targets.to(torch.int32).contiguous()
     target_lengths = target_lengths.to(torch.int32).contiguous()
     dev = pred.device
@@ -129,15 +120,11 @@ def ctc_forced_align(pred, targets, target_lengths, blank=0, unknown=1, log_prob
            'peak': torch.empty((N, S), dtype=torch.int32, device=dev)}
     if N == 0:
         return out
-    nbytes = load().mr_ctc_align_ws_bytes(N, T, S)
-    if nbytes <= 0:
-        raise ValueError("ctc_forced_align: N=%d T=%d S=%d need a workspace above 2 GiB; split the batch" % (N, T, S))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    sn, sc, st = pred.stride()
+    ws = _workspace(load().mr_ctc_align_ws_bytes(N, T, S), who, "N=%d T=%d S=%d" % (N, T, S), dev)
     with torch.cuda.device(dev):
-        call("mr_ctc_align", 0 if pred.dtype == torch.float32 else 1, ptr(pred), sn, sc, st, N, C, T, int(bool(log_probs)),
-             blank, int(unknown), ptr(targets), S, ptr(target_lengths), ptr(out['score']), ptr(out['pos']), ptr(out['begin']),
-             ptr(out['end']), ptr(out['sym_lp']), ptr(out['peak']), ptr(ws), ws.numel() * 8)
+        call("mr_ctc_align", code, ptr(pred), sn, sc, st, N, C, T, int(bool(log_probs)), blank, int(unknown), ptr(targets), S,
+             ptr(target_lengths), ptr(out['score']), ptr(out['pos']), ptr(out['begin']), ptr(out['end']), ptr(out['sym_lp']),
+             ptr(out['peak']), ptr(ws), ws.numel() * 8)
     return out
 
 

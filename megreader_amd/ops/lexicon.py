@@ -21,7 +21,7 @@ import torch
 
 from .._lib import _DEFINES, call, ptr, require_cuda
 from ..charsets import DefaultCharset, upper_fold_table
-from .decode import ctc_greedy_decode
+from .decode import _DT, _posterior, ctc_greedy_decode
 
 MAX_WORD = _DEFINES["MR_LEXICON_MAX_WORD"]
 
@@ -132,20 +132,12 @@ class Lexicon(object):
         elsewhere.  With a case-folding charset the likelihood is taken over the folded alphabet.  Greedy decode, (fold) and one
         call of mr_lexicon_transcribe; no host work that depends on device data (capturable in a graph after one call outside)."""
         require_cuda(pred)
-        if pred.dim() == 4:
-            if pred.shape[2] != 1:
-                raise ValueError("pred must be [N, C, 1, T] or [N, C, T], got %s" % (tuple(pred.shape),))
-            pred = pred.select(2, 0)
-        if pred.dim() != 3:
-            raise ValueError("pred must be [N, C, 1, T] or [N, C, T], got %s" % (tuple(pred.shape),))
-        N, C, T = pred.shape
+        pred, (N, C, T), _, _ = _posterior(pred, "Lexicon.transcribe", error=ValueError)
         if C != self.classes:
             raise ValueError("pred has %d classes, the lexicon's charset %d" % (C, self.classes))
         dev = pred.device
         if self.device is not None and self.device.index is not None and self.device != dev:
             raise ValueError("pred is on %s, the lexicon was made for %s" % (dev, self.device))
-        if pred.dtype not in (torch.float32, torch.bfloat16):
-            pred = pred.float()
         sym, off, fold = self._tensors(dev)
         if spans is not None:
             spans = spans.to(device=dev, dtype=torch.int32).contiguous()
@@ -168,7 +160,7 @@ class Lexicon(object):
             if fold is not None:
                 pred = self._folded(pred, fold, log_probs)
             sn, sc, st = pred.stride()
-            call("mr_lexicon_transcribe", 0 if pred.dtype == torch.float32 else 1, ptr(pred), sn, sc, st, T, int(bool(log_probs)),
+            call("mr_lexicon_transcribe", _DT[pred.dtype], ptr(pred), sn, sc, st, T, int(bool(log_probs)),
                  ptr(ids), T, N, int(self.blank), int(self.unknown), ptr(fold), ptr(sym), ptr(off), L, ptr(spans), C,
                  -1 if max_distance is None else int(max_distance), ptr(out['index']), ptr(out['score']), ptr(out['distance']),
                  ptr(out['length']), ptr(out['candidates']), ptr(out.get('scores')) if all_scores and L else 0)

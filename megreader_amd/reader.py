@@ -61,6 +61,7 @@ class TextReader(object):
         self.detector = detector
         self.recognizer = recognizer
         self.charset = charset
+        self.blank, self.unknown = getattr(charset, 'blank', 0), getattr(charset, 'unknown', 1)
         self.representer = representer if representer is not None else SegDetectorRepresenter(resize=True)
         self.decode = decode
         self.beam_width, self.nbest, self.beam_top_classes = int(beam_width), int(nbest), int(beam_top_classes)
@@ -82,15 +83,16 @@ class TextReader(object):
         batch = self.det_pipeline.upload(staged, layout)
         return batch, self.det_pipeline.photos(batch, layout)
 
-    def _ids(self, pred):
-        """(ids [M, S], lengths [M] or None) of one chunk's prediction."""
+    def _decode(self, pred, post):
+        """The decode step of one chunk (pred: the recogniser's output, post: its CTC posterior): (ids [M, S] and lengths [M] or
+        None, on the device; None or, with decode='beam', per crop the dict of the keys the beam adds to an item)."""
+        if self.decode == 'beam':
+            return self._beam(post)
         if callable(self.decode):
-            return self.decode(pred)
+            return tuple(self.decode(pred)) + (None,)
         if self.decode == 'ids':
-            return pred, None
-        if isinstance(pred, (tuple, list)):
-            pred = pred[0]
-        return ctc_greedy_decode(pred, blank=getattr(self.charset, 'blank', 0), unknown=getattr(self.charset, 'unknown', 1))
+            return pred, None, None
+        return ctc_greedy_decode(post, blank=self.blank, unknown=self.unknown) + (None,)
 
     @staticmethod
     def _eval(module, x):
@@ -108,10 +110,8 @@ class TextReader(object):
     def _beam(self, pred):
         """One chunk by prefix beam search: (top-1 ids [M, T] and lengths [M] on the device, per crop {'text_score'} and, with
         nbest > 1, {'alternatives'}).  The ids, lengths and scores of the hypotheses are all that crosses to the host."""
-        if isinstance(pred, (tuple, list)):
-            pred = pred[0]
         out = ctc_beam_search_decode(pred, beam=self.beam_width, nbest=self.nbest, top_classes=self.beam_top_classes,
-                                     blank=getattr(self.charset, 'blank', 0), unknown=getattr(self.charset, 'unknown', 1))
+                                     blank=self.blank, unknown=self.unknown)
         scores, count = out['scores'].cpu().tolist(), out['count'].cpu().tolist()
         extras = [{'text_score': float(row[0]) if k > 0 else float('-inf')} for row, k in zip(scores, count)]
         if self.nbest > 1:
@@ -127,9 +127,6 @@ class TextReader(object):
         word where one was taken; a lexicon word is aligned to the posterior over the folded alphabet (`Lexicon._folded`), the
         rows that kept their raw string to the posterior as it is: two calls per chunk at most, each with length -1 (unalignable,
         no work) for the other call's rows.  Only the three arrays cross to the host."""
-        blank, unknown = getattr(self.charset, 'blank', 0), getattr(self.charset, 'unknown', 1)
-        if isinstance(pred, (tuple, list)):
-            pred = pred[0]
         if pred.dim() == 4:
             pred = pred.select(2, 0)
         dev = pred.device
@@ -138,23 +135,21 @@ class TextReader(object):
         lens = lengths.to(device=dev, dtype=torch.int32)
         took = fold = None
         if found is not None:
-            took = found['index'] >= 0
-            if self.lexicon_rule == 'nearest' and self.lexicon_max_distance is not None:
-                took = took & (found['distance'] <= self.lexicon_max_distance)
+            took = self._takes_word(found['index'], found['distance'])
             words, word_lens = self.lexicon.ids(torch.where(took, found['index'], torch.full_like(found['index'], -1)))
             S = max(targets.shape[1], words.shape[1])
-            targets = torch.nn.functional.pad(targets, (0, S - targets.shape[1]), value=blank)
-            words = torch.nn.functional.pad(words, (0, S - words.shape[1]), value=blank)
+            targets = torch.nn.functional.pad(targets, (0, S - targets.shape[1]), value=self.blank)
+            words = torch.nn.functional.pad(words, (0, S - words.shape[1]), value=self.blank)
             targets = torch.where(took[:, None], words, targets)
             lens = torch.where(took, word_lens, lens)
             fold = self.lexicon._tensors(dev)[2]
         if fold is None:                                        # one posterior for every row
-            out = ctc_forced_align(pred, targets, lens, blank=blank, unknown=unknown)
+            out = ctc_forced_align(pred, targets, lens, blank=self.blank, unknown=self.unknown)
         else:
             none = torch.full_like(lens, -1)
-            raw = ctc_forced_align(pred, targets, torch.where(took, none, lens), blank=blank, unknown=unknown)
+            raw = ctc_forced_align(pred, targets, torch.where(took, none, lens), blank=self.blank, unknown=self.unknown)
             folded = ctc_forced_align(self.lexicon._folded(pred, fold, False), targets, torch.where(took, lens, none),
-                                      blank=blank, unknown=unknown)
+                                      blank=self.blank, unknown=self.unknown)
             out = {k: torch.where(took[:, None], folded[k], raw[k]) for k in ('begin', 'end', 'sym_lp')}
         return out['begin'].cpu().numpy(), out['end'].cpu().numpy(), out['sym_lp'].cpu().numpy(), int(pred.shape[2])
 
@@ -168,61 +163,69 @@ class TextReader(object):
 
     def recognize(self, crops):
         """crops: f32 [M, 3, H, W] on the device -> M strings (with a lexicon: the nearest words, see `read`)."""
-        texts = self._recognize(crops)[0]
-        return texts if self.lexicon is None else [t[0] for t in texts]
+        return [rec['text'] for rec in self._recognize(crops)]
+
+    def _takes_word(self, index, distance):
+        """Whether the lexicon word `index` at edit distance `distance` replaces the raw string: the one statement of the rule, on
+        device tensors (`_align`) and on the host's integers (`_to_host`) alike."""
+        took = index >= 0
+        if self.lexicon_rule == 'nearest' and self.lexicon_max_distance is not None:
+            took = took & (distance <= self.lexicon_max_distance)
+        return took
+
+    def _lexicon(self, pred, ids, lengths):
+        """The lexicon step of one chunk, on the device: None, or what `Lexicon.transcribe` finds in the posterior (likelihood
+        rule) or `Lexicon.nearest` for the decoded ids, before they are copied."""
+        if self.lexicon is None:
+            return None
+        if self.lexicon_rule == 'likelihood':
+            return self.lexicon.transcribe(pred, max_distance=self.lexicon_max_distance)
+        rows = ids.to(torch.int32)
+        if lengths is not None:
+            beyond = torch.arange(rows.shape[1], device=rows.device)[None, :] >= lengths.to(rows.device)[:, None]
+            rows = rows.masked_fill(beyond, self.blank)
+        return self.lexicon.nearest(rows)
+
+    def _to_host(self, ids, lengths, extras, found, aligned):
+        """One chunk's records (`_recognize`): copies the ids, lengths and what the lexicon found; `aligned` is on the host."""
+        ids = ids.cpu().numpy()
+        lengths = np.full(len(ids), ids.shape[1]) if lengths is None else lengths.cpu().numpy()
+        records = [{'text': self.charset.label_to_string(row[:int(k)]), 'word': False} for row, k in zip(ids, lengths)]
+        for rec, extra in zip(records, extras or ()):
+            rec['extras'] = extra
+        if found is not None:
+            index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
+            for rec, i, d in zip(records, index, distance):
+                rec.update(raw_text=rec['text'], lexicon_distance=d, word=bool(self._takes_word(i, d)))
+                if rec['word']:
+                    rec['text'] = self.lexicon.words[i]
+            if self.lexicon_rule == 'likelihood':
+                for rec, score in zip(records, found['score'].cpu().tolist()):
+                    rec['lexicon_score'] = score
+        if aligned is not None:
+            begin, end, sym_lp, T = aligned
+            for m, (rec, row, k) in enumerate(zip(records, ids, lengths)):
+                own = [self.charset.label_to_string(row[j:j + 1]) for j in range(int(k))]      # the raw string: its own ids
+                rec['spans'] = self._spans(list(rec['text']) if rec['word'] else own, begin[m], end[m], sym_lp[m], T)
+        return records
 
     def _recognize(self, crops):
-        """(texts, extras, spans).  texts: M strings; with a lexicon M (text, raw text, distance) triples, the text the nearest lexicon
-        word where its distance is within `lexicon_max_distance`; with the likelihood rule (text, raw text, distance, score), the
-        text the most probable word among those within `lexicon_max_distance` of the greedy string.  extras: None, or with
-        decode='beam' M dicts of the keys the beam adds to an item.  spans: None, or with chars=True per crop what `_spans` returns
-        for the crop's final text."""
-        texts = []
-        spans = [] if self.chars else None
-        extras = [] if self.decode == 'beam' else None
-        likelihood = self.lexicon is not None and self.lexicon_rule == 'likelihood'
+        """One record (a dict) per crop, of the fields its mode produces and no others:
+          'text', 'word'      the final string, and whether it is a lexicon word that was taken for the decoded one;
+          'raw_text', 'lexicon_distance'   with a lexicon: the decoded string, and the distance of the word found (taken or not);
+          'lexicon_score'     with the likelihood rule: log p(word | posterior);
+          'extras'            with decode='beam': the dict of the keys the beam adds to an item;
+          'spans'             with chars=True: what `_spans` returns for the final text (None: it could not be aligned).
+        Per chunk of `max_crops`: decode, lexicon and align on the device, then one step that copies to the host."""
+        records = []
         for lo in range(0, crops.shape[0], self.max_crops):
             pred = self._eval(self.recognizer, crops[lo:lo + self.max_crops])
-            if extras is None:
-                ids, lengths = self._ids(pred)
-            else:
-                ids, lengths, more = self._beam(pred)
-                extras.extend(more)
-            found = None
-            if likelihood:                                      # on the device posterior
-                found = self.lexicon.transcribe(pred[0] if isinstance(pred, (tuple, list)) else pred,
-                                                max_distance=self.lexicon_max_distance)
-            elif self.lexicon is not None:                      # on the device ids, before they are copied
-                rows = ids.to(torch.int32)
-                if lengths is not None:
-                    beyond = torch.arange(rows.shape[1], device=rows.device)[None, :] >= lengths.to(rows.device)[:, None]
-                    rows = rows.masked_fill(beyond, getattr(self.charset, 'blank', 0))
-                found = self.lexicon.nearest(rows)
-            aligned = self._align(pred, ids, lengths, found) if self.chars else None
-            ids = ids.cpu().numpy()
-            lengths = np.full(len(ids), ids.shape[1]) if lengths is None else lengths.cpu().numpy()
-            raw = [self.charset.label_to_string(row[:int(k)]) for row, k in zip(ids, lengths)]
-            first = len(texts)
-            if found is None:
-                texts.extend(raw)
-            elif likelihood:
-                index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
-                for text, i, d, score in zip(raw, index, distance, found['score'].cpu().tolist()):
-                    texts.append((self.lexicon.words[i] if i >= 0 else text, text, d, score))
-            else:
-                index, distance = torch.stack([found['index'], found['distance']]).cpu().tolist()
-                for text, i, d in zip(raw, index, distance):
-                    near = i >= 0 and (self.lexicon_max_distance is None or d <= self.lexicon_max_distance)
-                    texts.append((self.lexicon.words[i] if near else text, text, d))
-            if aligned is not None:
-                begin, end, sym_lp, T = aligned
-                for m, (row, k, text) in enumerate(zip(ids, lengths, texts[first:])):
-                    if found is None or text[0] == text[1]:     # the raw string (or a word that spells the same): its own ids
-                        symbols = [self.charset.label_to_string(row[j:j + 1]) for j in range(int(k))]
-                    else:                                       # a lexicon word: its own characters
-                        symbols = list(text[0])
-                    spans.append(self._spans(symbols, begin[m], end[m], sym_lp[m], T))
-        return texts, extras, spans
+            post = pred[0] if isinstance(pred, (tuple, list)) else pred     # (of a CTC recogniser)
+            ids, lengths, extras = self._decode(pred, post)
+            found = self._lexicon(post, ids, lengths)
+            aligned = self._align(post, ids, lengths, found) if self.chars else None
+            records.extend(self._to_host(ids, lengths, extras, found, aligned))
+        return records
 
     def _chars(self, plan, spans):
         """One item's 'chars' from its crop's plan and aligned spans: the canvas rectangle of each character's columns, clamped to
@@ -283,22 +286,18 @@ class TextReader(object):
         if layout.M == 0:
             return results
         crops = self.cropper.upload(staged, layout)
-        texts, extras, spans = self._recognize(crops['image'])
+        records = self._recognize(crops['image'])
         host = staged.numpy()
         index = host[layout.index_off:layout.index_off + 4 * layout.M].view(np.int32)
         quads = host[layout.quad_off:layout.quad_off + 64 * layout.M].view(np.float64).reshape(layout.M, 4, 2)
         # (boxes with a zero side were dropped by the cropper)
-        for m, (i, quad, text) in enumerate(zip(index.tolist(), quads.tolist(), texts)):
-            if self.lexicon is None:
-                results[i].append({'quad': quad, 'text': text})
-            else:
-                results[i].append({'quad': quad, 'text': text[0], 'raw_text': text[1], 'lexicon_distance': text[2]})
-                if len(text) > 3:
-                    results[i][-1]['lexicon_score'] = text[3]
-            if extras is not None:
-                results[i][-1].update(extras[m])
-            if spans is not None:
-                results[i][-1]['chars'] = self._chars(layout.plans[m], spans[m])
+        for i, quad, plan, rec in zip(index.tolist(), quads.tolist(), layout.plans, records):
+            item = {'quad': quad, 'text': rec['text']}
+            item.update((key, rec[key]) for key in ('raw_text', 'lexicon_distance', 'lexicon_score') if key in rec)
+            item.update(rec.get('extras', ()))
+            if 'spans' in rec:
+                item['chars'] = self._chars(plan, rec['spans'])
+            results[i].append(item)
         if self.scores:                                                        # ... and so are their scores
             dropped = set(layout.dropped)
             for i, found in enumerate(results):

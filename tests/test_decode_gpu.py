@@ -440,3 +440,49 @@ def test_decode_2d_signed_scores_and_masks():
     assert np.array_equal(ids.cpu().numpy(), want)
     assert ln.cpu().tolist() == [int((r != 0).sum()) for r in want]
     assert len(set(want.reshape(-1).tolist())) >= 5
+
+
+def test_posterior_layouts_and_dtypes_read_alike_by_the_four_wrappers():
+    """One posterior (N=3, C=5, T=7) through ctc_greedy_decode, ctc_beam_search_decode, ctc_forced_align and Lexicon.transcribe as
+    [N, C, T], [N, C, 1, T], a transposed view (st != 1) and f64 / f16 copies: the same bits out every time.  Every value is a
+    multiple of 1/64, exact in f16, so a copy holds the same numbers and a column's greatest value stays 22/64 clear of the next."""
+    from megreader_amd.charsets import Charset
+    from megreader_amd.ops.decode import ctc_beam_search_decode, ctc_forced_align
+    from megreader_amd.ops.lexicon import Lexicon
+    N, C, T = 3, 5, 7
+    rng = np.random.RandomState(11)
+    y = np.stack([np.stack([rng.permutation([34, 12, 9, 6, 3]) for _ in range(T)], axis=1) for _ in range(N)]).astype(np.float32) / 64
+    pred = torch.from_numpy(y)                                                   # [N, C, T]
+    assert pred.shape == (N, C, T) and torch.equal(pred.sum(dim=1), torch.ones(N, T))
+    assert torch.equal(pred.half().float(), pred) and torch.equal(pred.double().float(), pred)
+    top2 = pred.topk(2, dim=1).values
+    assert float((top2[:, 0] - top2[:, 1]).min()) == 22 / 64
+    pred = pred.to(DEV)
+    transposed = pred.permute(0, 2, 1).contiguous().permute(0, 2, 1)             # [N, C, T] over an [N, T, C] base
+    assert transposed.stride() == (T * C, 1, C) and not transposed.is_contiguous()
+    forms = {'[N, C, T]': pred, '[N, C, 1, T]': pred.unsqueeze(2), 'transposed': transposed, 'f64': pred.double(),
+             'f16': pred.half()}
+    lexicon = Lexicon(["AB", "CAB", "B", "ACCA"], Charset("ABC"))
+    assert len(lexicon.charset) == C
+    targets = torch.tensor([[2, 3, 0], [4, 2, 3], [3, 0, 0]], dtype=torch.int32, device=DEV)
+    lengths = torch.tensor([2, 3, 1], dtype=torch.int32, device=DEV)
+    wrappers = {
+        'greedy': lambda p: dict(zip(('ids', 'lengths'), ctc_greedy_decode(p))),
+        'beam': lambda p: ctc_beam_search_decode(p, beam=4, nbest=2, top_classes=3),
+        'align': lambda p: ctc_forced_align(p, targets, lengths),
+        'transcribe': lambda p: lexicon.transcribe(p, all_scores=True),
+    }
+    errors = {'greedy': RuntimeError, 'beam': RuntimeError, 'align': RuntimeError, 'transcribe': ValueError}
+    for name, run in wrappers.items():
+        want = run(forms['[N, C, T]'])
+        for form, p in forms.items():
+            got = run(p)
+            assert got.keys() == want.keys()
+            for key in want:
+                assert got[key].dtype == want[key].dtype and torch.equal(got[key], want[key]), (name, form, key)
+        with pytest.raises(errors[name]):
+            run(torch.full((N, C, 2, T), 0.2, device=DEV))
+    # and they read something: the greedy path is the column maxima, the beam has two strings per row, every row aligns
+    ids, _ = ctc_greedy_decode(pred)
+    assert ids.shape == (N, T) and int(wrappers['beam'](pred)['count'].min()) == 2
+    assert torch.isfinite(wrappers['align'](pred)['score']).all() and int(wrappers['transcribe'](pred)['index'].min()) >= 0

@@ -141,3 +141,125 @@ def test_real_recogniser_reads_what_the_steps_by_hand_read():
     ids, lengths = ctc_greedy_decode(pred)
     by_hand = [charset.label_to_string(row[:int(k)]) for row, k in zip(ids.cpu().numpy(), lengths.cpu().numpy())]
     assert [item['text'] for found in results for item in found] == by_hand
+
+
+class SoftSpell(SpellByBrightness):
+    """The stub's spelling with a quarter of every column's mass spread over all classes: no probability is 0 or 1, so the scores
+    of the beam, of the lexicon and of the characters are numbers that can differ."""
+
+    def forward(self, crops):
+        hard = super().forward(crops)
+        return hard * 0.75 + 0.25 / hard.shape[1]
+
+
+def item_keys(decode, rule, chars, scores):
+    """An item's keys in the order `TextReader.read` documents."""
+    return (['quad', 'text'] + (['raw_text', 'lexicon_distance'] if rule else []) + (['lexicon_score'] if rule == 'likelihood' else [])
+            + (['text_score', 'alternatives'] if decode == 'beam' else []) + (['chars'] if chars else []) + (['score'] if scores else []))
+
+
+def test_items_of_every_mode_are_what_the_ops_give_by_hand():
+    from megreader_amd.data.quad_crop import plan_crop
+    from megreader_amd.ops.decode import ctc_beam_search_decode, ctc_forced_align
+    from megreader_amd.ops.lexicon import Lexicon
+    charset = EnglishCharset()
+    blank, unknown = charset.blank, charset.unknown
+    words, delta, rec_size = ["AB12", "HELL0", "TEXTS"], 1, (32, 128)       # AB12 is there, HELLO and TEXT are one edit away, X9 far
+    lexicon = Lexicon(words, charset)
+    pictures = photos()
+    shapes = [p.shape for p in pictures for _ in range(2)][:4]
+
+    def string(row, k):
+        return charset.label_to_string(row[:int(k)])
+
+    # the same crops, the posterior and every op, once, by hand
+    plain = TextReader(detector, SoftSpell(charset), charset, det_size=DET_SIZE).read(pictures)
+    quads = [[item['quad'] for item in found] for found in plain]
+    crops = QuadCropper(image_size=rec_size).crop(pictures, quads)
+    assert crops['index'].cpu().tolist() == [0, 0, 1, 1]
+    post = SoftSpell(charset)(crops['image'])
+    T = post.shape[3]
+    decoded = {}
+    ids, lengths = ctc_greedy_decode(post, blank=blank, unknown=unknown)
+    decoded['ctc'] = (ids, lengths, [string(r, k) for r, k in zip(ids.cpu().numpy(), lengths.cpu().numpy())], None)
+    beam = ctc_beam_search_decode(post, beam=8, nbest=2, top_classes=16, blank=blank, unknown=unknown)
+    b_ids, b_len, b_scores, b_count = (beam[k].cpu().numpy() for k in ('ids', 'lengths', 'scores', 'count'))
+    extras = [{'text_score': float(s[0]) if n > 0 else float('-inf'),
+               'alternatives': [(string(r[j], k[j]), float(s[j])) for j in range(int(n))]}
+              for r, k, s, n in zip(b_ids, b_len, b_scores, b_count)]
+    decoded['beam'] = (beam['ids'][:, 0], beam['lengths'][:, 0], [string(r[0], k[0]) for r, k in zip(b_ids, b_len)], extras)
+    assert sorted(decoded['ctc'][2]) == sorted(LEVELS.values()) and decoded['beam'][2] == decoded['ctc'][2]
+    assert all(len(e['alternatives']) == 2 and e['alternatives'][0][1] > e['alternatives'][1][1] > -math.inf for e in extras)
+
+    def by_hand(decode, rule, chars):
+        ids, lengths, raw, extras = decoded[decode]
+        rows = ids.to(torch.int32).masked_fill(torch.arange(ids.shape[1], device=ids.device)[None, :] >= lengths[:, None], blank)
+        final = [r[:int(k)].tolist() for r, k in zip(rows.cpu().numpy(), lengths.cpu().numpy())]
+        items = [{'text': t} for t in raw]
+        took = [False] * len(raw)
+        if rule:
+            found = lexicon.nearest(rows) if rule == 'nearest' else lexicon.transcribe(post, max_distance=delta)
+            index, distance = found['index'].cpu().tolist(), found['distance'].cpu().tolist()
+            took = [i >= 0 and (rule == 'likelihood' or d <= delta) for i, d in zip(index, distance)]
+            for m, item in enumerate(items):
+                item.update(raw_text=raw[m], lexicon_distance=distance[m])
+                if took[m]:
+                    item['text'] = words[index[m]]
+                    final[m] = lexicon.sym[lexicon.off[index[m]]:lexicon.off[index[m] + 1]].tolist()
+                if rule == 'likelihood':
+                    item['lexicon_score'] = found['score'].cpu().tolist()[m]
+        if extras is not None:
+            for item, extra in zip(items, extras):
+                item.update(extra)
+        if chars:
+            S = max(len(f) for f in final)
+            targets = torch.tensor([f + [blank] * (S - len(f)) for f in final], dtype=torch.int32, device="cuda")
+            lens = torch.tensor([len(f) for f in final], dtype=torch.int32, device="cuda")
+            out = {k: v.cpu().numpy() for k, v in ctc_forced_align(post, targets, lens, blank=blank, unknown=unknown).items()}
+            if lexicon.fold is not None:                        # a lexicon word is aligned to the folded posterior
+                fold = torch.tensor(lexicon.fold, dtype=torch.int32, device="cuda")
+                folded = ctc_forced_align(lexicon._folded(post.select(2, 0), fold, False), targets, lens, blank=blank, unknown=unknown)
+                out = {k: np.where(np.asarray(took).reshape((-1,) + (1,) * (v.ndim - 1)), folded[k].cpu().numpy(), v)
+                       for k, v in out.items()}
+            for m, item in enumerate(items):
+                assert math.isfinite(float(out['score'][m]))
+                plan = plan_crop(shapes[m], np.asarray(plain_flat[m]['quad'], dtype=np.float64), rec_size, 'resize', 'min_area_rect')
+                item['chars'] = []
+                for k, ch in enumerate(item['text']):
+                    b, e = int(out['begin'][m][k]), int(out['end'][m][k])
+                    u0, u1 = (min(max(v * (rec_size[1] / float(T)), 0.0), float(plan.dst_w)) for v in (b, e))
+                    quad = plan.canvas_to_photo([[u0, 0.0], [u1, 0.0], [u1, float(rec_size[0])], [u0, float(rec_size[0])]])
+                    item['chars'].append({'char': ch, 'quad': quad.tolist(), 'score': math.exp(float(out['sym_lp'][m][k]) / (e - b))})
+        return items
+
+    plain_flat = [item for found in plain for item in found]
+    seen = set()
+    for decode, rule in (('ctc', None), ('ctc', 'nearest'), ('ctc', 'likelihood'), ('beam', None), ('beam', 'nearest')):
+        for chars in (False, True):
+            want = by_hand(decode, rule, chars)
+            for scores in (False, True):
+                recognizer = SoftSpell(charset)
+                kw = dict(lexicon=lexicon, lexicon_rule=rule, lexicon_max_distance=delta) if rule else {}
+                reader = TextReader(detector, recognizer, charset, det_size=DET_SIZE, rec_size=rec_size, decode=decode, nbest=2,
+                                    max_crops=3, chars=chars, scores=scores, **kw)
+                results = reader.read(pictures)
+                assert recognizer.batches == [3, 1] and [len(found) for found in results] == [2, 2, 0]
+                got = [item for found in results for item in found]
+                for item, ref, base in zip(got, want, plain_flat):
+                    mode = (decode, rule, chars, scores)
+                    assert list(item) == item_keys(decode, rule, chars, scores), mode
+                    assert item['quad'] == base['quad']
+                    if scores:
+                        assert isinstance(item.pop('score'), float)
+                    quads_got = [ch.pop('quad') for ch in item.get('chars', [])]
+                    quads_ref = [ch.pop('quad') for ch in [dict(c) for c in ref.get('chars', [])]]
+                    assert len(quads_got) == len(quads_ref) and np.allclose(np.asarray(quads_got).reshape(-1, 4, 2),
+                                                                            np.asarray(quads_ref).reshape(-1, 4, 2), atol=1e-9), mode
+                    ref = dict(ref, quad=base['quad'])
+                    if chars:
+                        ref['chars'] = [{k: v for k, v in ch.items() if k != 'quad'} for ch in ref['chars']]
+                    assert item == ref, (mode, item, ref)                   # strings, ints and floats (-inf included) bit for bit
+                    seen.add((item['text'], item.get('raw_text'), item.get('lexicon_distance')))
+    # the lexicon did all three things: confirmed a string, replaced one, and left one alone (nearest: too far; likelihood: nothing)
+    assert {("AB12", "AB12", 0), ("HELL0", "HELLO", 1), ("TEXTS", "TEXT", 1), ("X9", "X9", -1)} <= seen
+    assert any(t == "X9" and d is not None and d > delta for t, _, d in seen)
