@@ -22,7 +22,7 @@ from torch.nn.modules.utils import _pair
 from .... import get_compute_dtype
 from ...._lib import call, dcn_backward_workspace, dcn_workspace, dtype_code, load, ptr, vec_of
 from ....nn import prep
-from ....nn.functional import (ZeroArena, _grad_internal, grad_sink, mark_zero_padded, notify_grad_ready, to_internal)
+from ....nn.functional import GradDest, ZeroArena, _grad_internal, mark_zero_padded, to_internal
 
 
 def _dcn_forward(ctx, input, off, msk, weight, bias, stride, padding, dilation, groups, deformable_groups):
@@ -76,7 +76,7 @@ def _dcn_forward(ctx, input, off, msk, weight, bias, stride, padding, dilation, 
 def _dcn_backward(ctx, grad_output, want_dx, want_dw, want_db, scratch_ok=False):
     """Shared backward: (grad_input NCHW view | None, grad_offset f32 NCHW, grad_mask f32 NCHW, grad_weight | None,
     grad_bias | None).  Parameter gradients go straight into the fused optimizers' gradient sinks when those exist
-    (nn/functional.py grad_sink: no temporary, no `grad += tmp` launch) -- the returned gradient is then None."""
+    (nn/grads.py GradDest: no temporary, no `grad += tmp` launch) -- the returned gradient is then None."""
     xi, off, msk, w_t, col_saved = ctx.saved_tensors
     N, H, W, C, Co, kh, kw, stride, padding, dilation, Ho, Wo, off_bs, msk_bs = ctx.geom
     dtype = ctx.dtype
@@ -86,8 +86,8 @@ def _dcn_backward(ctx, grad_output, want_dx, want_dw, want_db, scratch_ok=False)
     g = _grad_internal(grad_output, dtype)
     col, ws_flags = dcn_backward_workspace(dtype, N, H, W, C, Co, kh, kw, Ho, Wo, dev)   # CSR of the scatter / column matrix
     weight, bias = ctx.params
-    w_sink = grad_sink(weight, (Co, kh, kw, C)) if want_dw else None
-    b_sink = grad_sink(bias, (Co,)) if want_db else None
+    w = GradDest(weight, want_dw, (Co, kh, kw, C))
+    b = GradDest(bias, want_db, (Co,))
     # the input gradient straight in the compute dtype where the fused kernel runs un-split (every layer of the detector at
     # batch 2): no zero fill in front of it, no conversion pass behind it
     direct = bool(want_dx and load().mr_dcn2_dx_direct(dt, N, H, W, C, Co, kh, kw))
@@ -95,7 +95,7 @@ def _dcn_backward(ctx, grad_output, want_dx, want_dw, want_db, scratch_ok=False)
     # were 52 fill launches per DB step) -- or none: scratch_ok (the packed node consumes the offset / mask gradients before
     # it returns) takes them from the pre-zeroed arena that zero_grad() clears with the gradient buffers
     sizes = [off.numel(), msk.numel(), N * H * W * C if (want_dx and not direct) else 0,
-             Co * K if (want_dw and w_sink is None) else 0, Co if (want_db and b_sink is None) else 0]
+             Co * K if (w.want and not w.sunk) else 0, Co if (b.want and not b.sunk) else 0]
     offs = [0]
     for n_ in sizes:
         offs.append(offs[-1] + (n_ + 63) // 64 * 64)
@@ -110,11 +110,9 @@ def _dcn_backward(ctx, grad_output, want_dx, want_dw, want_db, scratch_ok=False)
     grad_mask = zbuf[offs[1]:offs[1] + sizes[1]].view(msk.shape)
     dx32 = zbuf[offs[2]:offs[2] + sizes[2]].view(N, H, W, C) if (want_dx and not direct) else None
     dxi = torch.empty((N, H, W, C), dtype=dtype, device=dev) if direct else None
-    gw = gb = None
-    if want_dw:
-        gw = w_sink if w_sink is not None else zbuf[offs[3]:offs[3] + sizes[3]].view(Co, kh, kw, C)
-    if want_db:
-        gb = b_sink if b_sink is not None else zbuf[offs[4]:offs[4] + sizes[4]]
+    # (fallbacks are cut from zbuf, which is an arena slice only when no parameter gradient needs one: `not any(sizes[2:])`)
+    gw = w.into(lambda: zbuf[offs[3]:offs[3] + sizes[3]].view(Co, kh, kw, C))
+    gb = b.into(lambda: zbuf[offs[4]:offs[4] + sizes[4]])
     call("mr_dcn2_bwd3", dt, ptr(g), ptr(xi), ptr(w_t), ptr(off), off_bs, ptr(msk), msk_bs, ptr(col), ptr(dx32), ptr(dxi),
          ws_flags, ptr(grad_offset), ptr(grad_mask), ptr(gw), ptr(gb), ptr(col_saved), N, H, W, C, Co, kh, kw, stride, padding,
          dilation, Ho, Wo)
@@ -128,18 +126,9 @@ def _dcn_backward(ctx, grad_output, want_dx, want_dw, want_db, scratch_ok=False)
             dxi = torch.empty((N, H, W, C), dtype=dtype, device=dev)
             call("mr_cast", 0, ptr(dx32), dt, ptr(dxi), dx32.numel())
         grad_input = dxi.permute(0, 3, 1, 2)
-    grad_weight = grad_bias = None
-    if want_dw:
-        if w_sink is not None:
-            notify_grad_ready(weight)
-        else:
-            grad_weight = gw.permute(0, 3, 1, 2)
-    if want_db:
-        if b_sink is not None:
-            notify_grad_ready(bias)
-        else:
-            grad_bias = gb
-    return grad_input, grad_offset, grad_mask, grad_weight, grad_bias
+    w.notify()
+    b.notify()
+    return grad_input, grad_offset, grad_mask, w.grad(lambda t: t.permute(0, 3, 1, 2)), b.grad()
 
 
 class ModulatedDeformConvFunction(Function):

@@ -17,231 +17,14 @@ from torch.autograd import Function
 from .. import get_compute_dtype
 from . import prep
 from .._lib import call, dtype_code, load, ptr, require_cuda, vec_of
+from .grads import (GradDest, ZeroArena, _TnDefer, _wgrad, accumulate_multi, discard_deferred_wgrads,  # noqa: F401
+                    flush_deferred_wgrads, grad_sink, notify_grad_ready, zero_segments)
 
 _ESIZE = {torch.float32: 4, torch.bfloat16: 2}
 
 
 def _ceil_to(x, m):
     return (x + m - 1) // m * m
-
-
-def grad_sink(param, physical_shape=None):
-    """Gradient sink protocol.  megreader_amd.optim attaches to every parameter it owns a persistent f32 view of its
-    flat gradient buffer (`param._mr_grad_sink`, also installed as `param.grad`).  Backward kernels that accumulate
-    (`+=`) anyway -- the split-P wgrad GEMMs and column sums -- write straight into that view and the autograd
-    Function returns None for the parameter: no temporary gradient, no zero-fill, no `grad += tmp` kernel.
-    Returns the sink tensor if it exists and its memory is dense in the layout the kernel writes
-    (`physical_shape`: e.g. KRSC for a channels_last OIHW conv weight), else None (normal autograd path)."""
-    sink = getattr(param, "_mr_grad_sink", None)
-    if sink is None or sink.dtype != torch.float32 or not sink.is_cuda:
-        return None
-    # only while the sink IS param.grad: after `model.zero_grad()` (grad=None) or a user-assigned .grad the normal
-    # autograd accumulation path must run, otherwise stale sums would survive in the flat buffer
-    if param.grad is None or param.grad.data_ptr() != sink.data_ptr():
-        return None
-    if physical_shape == "strided":   # the kernel takes explicit strides
-        return sink
-    if physical_shape is not None:
-        if len(physical_shape) == 4:
-            phys = sink.permute(0, 2, 3, 1)
-            if tuple(phys.shape) != tuple(physical_shape) or not phys.is_contiguous():
-                return None
-        elif tuple(sink.shape) != tuple(physical_shape) or not sink.is_contiguous():
-            return None
-    elif not sink.is_contiguous():
-        return None
-    return sink
-
-
-def notify_grad_ready(param):
-    """Tell data-parallel wrappers that `param`'s gradient was accumulated through its sink (the autograd
-    post-accumulate hook does not fire when a Function returns None)."""
-    for hook in getattr(param, "_mr_grad_ready_hooks", ()):
-        hook(param)
-
-
-class ZeroArena(object):
-    """Pre-zeroed f64 scratch for the per-channel reduction buffers of BatchNorm (mr_bn_scratch_doubles(C) per call,
-    forward and backward).  Each call used to zero its own buffer with a memset (120 tiny launches per ResNet-50 step).  Slices
-    are handed out once per zeroing by a bump pointer; `reset()` -- called by the fused optimizers' `zero_grad()` --
-    re-zeroes the used prefix with ONE fill and rewinds.  When the arena is exhausted (nobody calls reset: eval
-    loops, foreign optimizers) `take` returns None and the caller falls back to its own memset."""
-    SIZE = 1 << 24  # doubles (128 MB: the offset / mask gradients of the 13 DCN layers of a detector step take ~32 MB; ResNet-50 takes ~34 doubles per BN channel per step, ~1 M; the four persistent-LSTM
-                    # exchange rings of a CRNN step 3.2 M)
-    arenas = {}
-
-    def __init__(self, device):
-        self.buf = torch.zeros((ZeroArena.SIZE,), dtype=torch.float64, device=device)
-        self.offset = 0
-
-    @staticmethod
-    def take(device, n):
-        a = ZeroArena.arenas.get(device)
-        if a is None:
-            a = ZeroArena.arenas[device] = ZeroArena(device)
-        n = (n + 31) // 32 * 32
-        if a.offset + n > ZeroArena.SIZE:
-            return None
-        out = a.buf[a.offset:a.offset + n]
-        a.offset += n
-        return out
-
-    @staticmethod
-    def reset(device):
-        a = ZeroArena.arenas.get(device)
-        if a is not None and a.offset:
-            a.buf[:a.offset].zero_()
-            a.offset = 0
-
-    @staticmethod
-    def rewind(device):
-        """(data pointer, bytes) of the used prefix -- which the CALLER zeroes (zero_tensors: one launch together with the flat
-        gradient buffers) -- and rewind; None when nothing was handed out."""
-        a = ZeroArena.arenas.get(device)
-        if a is None or not a.offset:
-            return None
-        used = a.offset
-        a.offset = 0
-        return a.buf.data_ptr(), used * 8
-
-
-def zero_segments(segments):
-    """Zero fill of (data pointer, bytes) pairs, 8 per launch (mr_zero_multi); 16-byte aligned, sizes multiples of 16."""
-    for i in range(0, len(segments), 8):
-        chunk = segments[i:i + 8]
-        n = len(chunk)
-        call("mr_zero_multi", n, (ctypes.c_void_p * n)(*[p for p, _ in chunk]), (ctypes.c_longlong * n)(*[b for _, b in chunk]))
-
-
-def accumulate_multi(pairs):
-    """dst += src for a list of (dst, src) dense f32 tensor pairs, 8 pairs per launch (mr_accumulate_multi)."""
-    for i in range(0, len(pairs), 8):
-        chunk = pairs[i:i + 8]
-        n = len(chunk)
-        dst = (ctypes.c_void_p * n)(*[d.data_ptr() for d, _ in chunk])
-        src = (ctypes.c_void_p * n)(*[s.data_ptr() for _, s in chunk])
-        cnt = (ctypes.c_longlong * n)(*[s.numel() for _, s in chunk])
-        call("mr_accumulate_multi", n, dst, src, cnt)
-
-
-class _TnDefer(object):
-    """Deferred, grouped weight-gradient launches (include/megreader_hip.h: mr_tn_defer / mr_tn_flush).  Nothing later in a
-    backward pass reads a weight gradient that goes to a gradient sink, so the small weight-gradient GEMMs (ResNet 1x1 / strided
-    layers, LSTM / Linear layers) are recorded while backward runs and launched several problems per launch: at the latest from
-    an autograd-engine callback at the end of the backward pass, earlier whenever MAX problems are waiting.  The operands of the
-    recorded problems are kept alive here until the flush; parameters are reported to data-parallel wrappers
-    (notify_grad_ready) only after the launch that completes their gradient.
-    MEGREADER_TN_DEFER=0 (or mr_tuning.tn_defer = 0): every launch immediate (A/B).
-    Every launch stays on the backward stream: forking weight-gradient launches onto side streams was measured slower in
-    every step (CHANGELOG.md, "Retired: the side-stream weight-gradient switches")."""
-    enabled = os.environ.get("MEGREADER_TN_DEFER", "1") != "0"
-    MAX = 12
-    keep = []
-    notify = []
-    queued = False
-    task = -1      # graph task (one backward() call) the end-of-backward callback is registered with
-    mark = 0
-
-    @staticmethod
-    def _task_id():
-        fn = getattr(torch._C, "_current_graph_task_id", None)
-        return fn() if fn is not None else -1
-
-    @staticmethod
-    def abort():
-        """Forget everything recorded and not yet launched: the backward pass that recorded it raised -- the autograd
-        engine skips its final callbacks then, so `queued` would stay set, the records would point at operands about to be
-        released and a later step would add stale problems into its gradients.  Called from the recording sites when a call
-        between begin() and end() raises, from begin() when it finds the state of ANOTHER graph task, and from the optimizers'
-        zero_grad() / the capture fallbacks of the graphed step."""
-        lib = load()
-        lib.mr_tn_defer(0)
-        lib.mr_tn_discard()
-        del _TnDefer.keep[:]
-        del _TnDefer.notify[:]
-        _TnDefer.queued = False
-        _TnDefer.task = -1
-
-    @staticmethod
-    def begin():
-        """Start recording for the calls that follow (until end()); False when deferral is not possible here (switched off,
-        or not inside a backward pass -- the end-of-backward flush could not be registered)."""
-        if not _TnDefer.enabled:
-            return False
-        tid = _TnDefer._task_id()
-        if _TnDefer.queued and tid != _TnDefer.task:
-            _TnDefer.abort()          # left over from a backward pass that never reached its callback
-        if not _TnDefer.queued:
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(_TnDefer.flush)
-            except RuntimeError:
-                return False
-            _TnDefer.queued = True
-            _TnDefer.task = tid
-        lib = load()
-        _TnDefer.mark = lib.mr_tn_pending()
-        lib.mr_tn_defer(1)
-        return True
-
-    @staticmethod
-    def record(launch, tensors, params):
-        """begin() was True: run `launch` (the library calls to record) and end(); a raise in between drops the recording state
-        instead of leaving mr_tn_defer(1) on for whatever this thread launches next."""
-        try:
-            launch()
-        except BaseException:
-            _TnDefer.abort()
-            raise
-        return _TnDefer.end(tensors, params)
-
-    @staticmethod
-    def end(tensors, params):
-        """Stop recording.  True when the calls since begin() were recorded (the caller must then NOT report its parameters
-        ready: the flush does); False when the library launched them at once (f32, all-taps kernel, mr_tuning.tn_defer = 0)."""
-        lib = load()
-        lib.mr_tn_defer(0)
-        n = lib.mr_tn_pending()
-        if n == _TnDefer.mark:
-            return False
-        _TnDefer.keep.extend(t for t in tensors if t is not None)
-        _TnDefer.notify.extend(params)
-        if n >= _TnDefer.MAX:
-            _TnDefer.flush(final=False)
-        return True
-
-    @staticmethod
-    def flush(final=True):
-        """Launch what is recorded and report its parameters ready; final: the end-of-backward callback of the graph task."""
-        if load().mr_tn_pending():
-            call("mr_tn_flush")
-        ready, _TnDefer.notify = _TnDefer.notify, []
-        del _TnDefer.keep[:]
-        if final:
-            _TnDefer.queued = False
-            _TnDefer.task = -1
-        for p in ready:
-            notify_grad_ready(p)
-
-
-def _wgrad(launch, may_defer, keep, params, immediate=None):
-    """The weight-gradient launch of one layer.  may_defer (every gradient it writes goes to a sink) and _TnDefer.begin()
-    succeeds: `launch` under recording, `keep` alive and `params` reported ready by the flush; True when the problems were
-    really recorded.  Otherwise `immediate` (default: `launch`) now and False: the caller reports its parameters itself."""
-    if may_defer and _TnDefer.begin():
-        return _TnDefer.record(launch, keep, params)
-    (immediate or launch)()
-    return False
-
-
-def discard_deferred_wgrads():
-    """Drop every recorded, not yet launched weight-gradient problem (a backward pass that raised; a failed capture)."""
-    _TnDefer.abort()
-
-
-def flush_deferred_wgrads():
-    """Launch every recorded weight-gradient problem now (data-parallel wrappers call this before they finalise a backward
-    pass; harmless when nothing is recorded)."""
-    _TnDefer.flush(final=False)
 
 
 def to_internal(x, dtype):
@@ -430,105 +213,101 @@ class Conv2dFn(Function):
 
     @staticmethod
     def backward(ctx, gy, g_fork=None):
-        xi, w_crsk, y = ctx.saved_tensors
-        N, H, W, Cp, C, K, Kp, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo = ctx.geom
-        dtype = ctx.dtype
-        dt = dtype_code(dtype)
-        if Kp == K:
-            g = _grad_internal(gy, dtype)
-        else:  # re-pad the gradient to the padded channel count (small head convolutions only)
-            g = _zero_padded_base(gy, (N, Ho, Wo, Kp), dtype)      # already padded by its producer (DCN offset convs)
-            if g is None:
-                g = torch.zeros((N, Ho, Wo, Kp), dtype=dtype, device=gy.device)
-                g[..., :K] = gy.permute(0, 2, 3, 1)
-        if ctx.relu:
-            gm = torch.empty_like(g)
-            call("mr_relu_bwd", dt, ptr(g), ptr(y), ptr(gm), g.numel())
-            g = gm
-        dx = dwt = db = None
-        if ctx.needs_input_grad[0]:
-            dxi = torch.empty((N, H, W, C), dtype=dtype, device=g.device)
-            ga = None
-            if g_fork is not None:     # dx = dgrad(g) + gradient of the forked alias of x, one kernel (mr_conv2d_dgrad_add)
-                ga = _grad_internal(g_fork, dtype)
-                if tuple(ga.shape) != (N, H, W, C) or not ga.is_contiguous():
-                    ga = ga.contiguous()
-            link = ctx.bnb_link
-            fused_bnb = False
-            if link is not None and link.xi is not None and link.dtype == dtype and tuple(link.xi.shape) == (N, H, W, C) and \
-                    BNB_EPILOGUE:
-                # x is the output of a training-mode BatchNorm and this convolution its only consumer: dxi IS that
-                # BatchNorm's incoming gradient, and its two per-channel reductions ride in this dgrad's epilogue
-                sums = ZeroArena.take(g.device, load().mr_bn_scratch_doubles(C))
-                if sums is not None:
-                    produced = ctypes.c_int(0)
-                    call("mr_conv2d_dgrad_bnb", dt, ptr(g), ptr(w_crsk), ptr(dxi), ptr(ga), ptr(link.xi), ptr(link.y),
-                         ptr(link.mean), ptr(link.rstd), ptr(sums), ctypes.byref(produced), N, H, W, C, C, Kp, Kp, R, S, sh,
-                         sw, ph, pw, dh, dw, Ho, Wo)
-                    fused_bnb = True
-                    if produced.value:
-                        link.sums, link.grad_ptr = sums, dxi.data_ptr()
-            if fused_bnb:
-                pass
-            elif ga is not None:
-                call("mr_conv2d_dgrad_add", dt, ptr(g), ptr(w_crsk), ptr(dxi), ptr(ga), N, H, W, C, C, Kp, Kp, R, S, sh, sw,
-                     ph, pw, dh, dw, Ho, Wo)
-            elif POINTWISE_STRIDED_DGRAD and R == 1 and S == 1 and (sh > 1 or sw > 1) and ph == 0 and pw == 0:
-                # strided 1x1 convolution (ResNet downsample branch): the dense dgrad on the sub-sampled grid, then one pass
-                # that places it at the sampled positions of dx and zeroes the rest (mr_scatter_strided)
-                dxs = torch.empty((N, Ho, Wo, C), dtype=dtype, device=g.device)
-                call("mr_conv2d_dgrad", dt, ptr(g), ptr(w_crsk), ptr(dxs), N, Ho, Wo, C, C, Kp, Kp, 1, 1, 1, 1, 0, 0, 1, 1, Ho,
-                     Wo)
-                call("mr_scatter_strided", dt, ptr(dxs), ptr(dxi), N, H, W, C, sh, sw, Ho, Wo)
-            else:
-                call("mr_conv2d_dgrad", dt, ptr(g), ptr(w_crsk), ptr(dxi), N, H, W, C, C, Kp, Kp, R, S, sh, sw, ph, pw,
-                     dh, dw, Ho, Wo)
-            dx = dxi.permute(0, 3, 1, 2)
-        elif g_fork is not None:
-            raise RuntimeError("conv2d_fork: the forked input received a gradient but the convolution input needs none")
-        weight_p, bias_p = ctx.params
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        # gradient sinks (see grad_sink): the wgrad / bias kernels accumulate directly into the flat gradient buffer
-        # (padded output channels, Kp != K: the wgrad kernel writes exactly K rows / bias entries -- the pad channels of g
-        # are zero -- so the sinks work for the 27-channel DCN offset convolutions too)
-        w_sink = grad_sink(weight_p, (K, R, S, C)) if (ctx.needs_input_grad[1] and Cp == C) else None
-        b_sink = grad_sink(bias_p, (K,)) if want_db else None
-        Kw = K if (w_sink is not None or b_sink is not None) else Kp   # rows of dw / entries of db the kernels write
-        if want_db:
-            db = b_sink if b_sink is not None else torch.zeros((Kp,), dtype=torch.float32, device=g.device)
-        if ctx.needs_input_grad[1]:
-            gw = w_sink if w_sink is not None else torch.zeros((Kp, R, S, Cp), dtype=torch.float32, device=g.device)
-            # the bias gradient (column sums of dy) rides along the wgrad pass over dy
-            # the gather's row table (8 bytes per output pixel) depends only on the layer geometry: built on first
-            # use, then passed to every later step (bf16, R*S <= 32; otherwise the call is plain mr_conv2d_wgrad)
-            tab, build = (None, 0)
-            if dtype == torch.bfloat16 and R * S <= 32:
-                # (Kw % 8: the all-taps kernel needs whole channel vectors and its table has another format than the GEMM
-                # kernel's -- two layers of one geometry that differ in that must not share a table)
-                tab, build = _wgrad_rowtab(g.device, (N, H, W, Cp, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo), Kw % 8 == 0)
-            def wgrad_launch():
-                call("mr_conv2d_wgrad_tab", dt, ptr(g), ptr(xi), ptr(gw), ptr(db) if want_db else 0, N, H, W, Cp, Cp, Kw,
-                     Kp, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo, ptr(tab), build)
-            # sunk gradients have no reader inside the backward pass: the launch may wait and share a grouped launch (_TnDefer)
-            if _wgrad(wgrad_launch, w_sink is not None and (not want_db or b_sink is not None), (g, xi, tab),
-                      [weight_p] + ([bias_p] if want_db else [])):
-                return dx, None, None, None, None, None, None, None, None, None, None
-            if w_sink is not None:
-                dwt = None
-                notify_grad_ready(weight_p)
-            else:
-                if Cp != C or Kp != K:
-                    gw = gw[:K, :, :, :C]
-                dwt = gw.permute(0, 3, 1, 2)
-        elif want_db:
-            call("mr_colsum", dt, ptr(g), ptr(db), N * Ho * Wo, Kw, Kp, 0)
-        if want_db:
-            if b_sink is not None:
-                db = None
-                notify_grad_ready(bias_p)
-            elif Kp != K:
-                db = db[:K]
-        return dx, dwt, db, None, None, None, None, None, None, None, None
+        return _conv2d_backward(ctx.saved_tensors, ctx.geom, ctx.dtype, ctx.params, ctx.has_bias, ctx.relu, ctx.bnb_link,
+                                ctx.needs_input_grad[:3], gy, g_fork) + (None,) * 8
+
+
+def _conv2d_backward(saved, geom, dtype, params, has_bias, relu, bnb_link, needs, gy, g_fork=None):
+    """(dx, dw, db) of a convolution node (Conv2dFn, ConvReluPoolFn).  saved: (xi, w_crsk, y -- read only for relu); needs: which of
+    (x, weight, bias) want a gradient; relu: apply the mask of the fused ReLU to gy first; bnb_link: see BnBwdLink."""
+    xi, w_crsk, y = saved
+    N, H, W, Cp, C, K, Kp, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo = geom
+    need_dx, need_dw, need_db = needs
+    dt = dtype_code(dtype)
+    if Kp == K:
+        g = _grad_internal(gy, dtype)
+    else:  # re-pad the gradient to the padded channel count (small head convolutions only)
+        g = _zero_padded_base(gy, (N, Ho, Wo, Kp), dtype)      # already padded by its producer (DCN offset convs)
+        if g is None:
+            g = torch.zeros((N, Ho, Wo, Kp), dtype=dtype, device=gy.device)
+            g[..., :K] = gy.permute(0, 2, 3, 1)
+    if relu:
+        gm = torch.empty_like(g)
+        call("mr_relu_bwd", dt, ptr(g), ptr(y), ptr(gm), g.numel())
+        g = gm
+    dx = None
+    if need_dx:
+        dxi = torch.empty((N, H, W, C), dtype=dtype, device=g.device)
+        ga = None
+        if g_fork is not None:     # dx = dgrad(g) + gradient of the forked alias of x, one kernel (mr_conv2d_dgrad_add)
+            ga = _grad_internal(g_fork, dtype)
+            if tuple(ga.shape) != (N, H, W, C) or not ga.is_contiguous():
+                ga = ga.contiguous()
+        link = bnb_link
+        fused_bnb = False
+        if link is not None and link.xi is not None and link.dtype == dtype and tuple(link.xi.shape) == (N, H, W, C) and \
+                BNB_EPILOGUE:
+            # x is the output of a training-mode BatchNorm and this convolution its only consumer: dxi IS that
+            # BatchNorm's incoming gradient, and its two per-channel reductions ride in this dgrad's epilogue
+            sums = ZeroArena.take(g.device, load().mr_bn_scratch_doubles(C))
+            if sums is not None:
+                produced = ctypes.c_int(0)
+                call("mr_conv2d_dgrad_bnb", dt, ptr(g), ptr(w_crsk), ptr(dxi), ptr(ga), ptr(link.xi), ptr(link.y),
+                     ptr(link.mean), ptr(link.rstd), ptr(sums), ctypes.byref(produced), N, H, W, C, C, Kp, Kp, R, S, sh,
+                     sw, ph, pw, dh, dw, Ho, Wo)
+                fused_bnb = True
+                if produced.value:
+                    link.sums, link.grad_ptr = sums, dxi.data_ptr()
+        if fused_bnb:
+            pass
+        elif ga is not None:
+            call("mr_conv2d_dgrad_add", dt, ptr(g), ptr(w_crsk), ptr(dxi), ptr(ga), N, H, W, C, C, Kp, Kp, R, S, sh, sw,
+                 ph, pw, dh, dw, Ho, Wo)
+        elif POINTWISE_STRIDED_DGRAD and R == 1 and S == 1 and (sh > 1 or sw > 1) and ph == 0 and pw == 0:
+            # strided 1x1 convolution (ResNet downsample branch): the dense dgrad on the sub-sampled grid, then one pass
+            # that places it at the sampled positions of dx and zeroes the rest (mr_scatter_strided)
+            dxs = torch.empty((N, Ho, Wo, C), dtype=dtype, device=g.device)
+            call("mr_conv2d_dgrad", dt, ptr(g), ptr(w_crsk), ptr(dxs), N, Ho, Wo, C, C, Kp, Kp, 1, 1, 1, 1, 0, 0, 1, 1, Ho,
+                 Wo)
+            call("mr_scatter_strided", dt, ptr(dxs), ptr(dxi), N, H, W, C, sh, sw, Ho, Wo)
+        else:
+            call("mr_conv2d_dgrad", dt, ptr(g), ptr(w_crsk), ptr(dxi), N, H, W, C, C, Kp, Kp, R, S, sh, sw, ph, pw,
+                 dh, dw, Ho, Wo)
+        dx = dxi.permute(0, 3, 1, 2)
+    elif g_fork is not None:
+        raise RuntimeError("conv2d_fork: the forked input received a gradient but the convolution input needs none")
+    weight_p, bias_p = params
+    # gradient sinks (see grad_sink): the wgrad / bias kernels accumulate directly into the flat gradient buffer
+    w = GradDest(weight_p, need_dw, (K, R, S, C))
+    b = GradDest(bias_p, has_bias and need_db, (K,))
+    if Cp != C:
+        w.sink = None      # no weight sink for a channel-padded input: the kernel writes rows of Cp, the parameter has C
+    # rows of dw / entries of db written = K when any sink exists, else Kp (the pad channels of g are zero, so K rows are the
+    # whole gradient: the sinks work for the 27-channel DCN offset convolutions too)
+    Kw = K if (w.sunk or b.sunk) else Kp
+    db = b.into(lambda: torch.zeros((Kp,), dtype=torch.float32, device=g.device))
+    if w.want:
+        gw = w.into(lambda: torch.zeros((Kp, R, S, Cp), dtype=torch.float32, device=g.device))
+        # the bias gradient (column sums of dy) rides along the wgrad pass over dy
+        # the gather's row table (8 bytes per output pixel) depends only on the layer geometry: built on first
+        # use, then passed to every later step (bf16, R*S <= 32; otherwise the call is plain mr_conv2d_wgrad)
+        tab, build = (None, 0)
+        if dtype == torch.bfloat16 and R * S <= 32:
+            # (Kw % 8: the all-taps kernel needs whole channel vectors and its table has another format than the GEMM
+            # kernel's -- two layers of one geometry that differ in that must not share a table)
+            tab, build = _wgrad_rowtab(g.device, (N, H, W, Cp, R, S, sh, sw, ph, pw, dh, dw, Ho, Wo), Kw % 8 == 0)
+        def wgrad_launch():
+            call("mr_conv2d_wgrad_tab", dt, ptr(g), ptr(xi), ptr(gw), ptr(db), N, H, W, Cp, Cp, Kw, Kp, R, S, sh, sw, ph, pw,
+                 dh, dw, Ho, Wo, ptr(tab), build)
+        # sunk gradients have no reader inside the backward pass: the launch may wait and share a grouped launch (_TnDefer)
+        if _wgrad(wgrad_launch, w.sunk and (not b.want or b.sunk), (g, xi, tab), [weight_p] + ([bias_p] if b.want else [])):
+            return dx, None, None
+        w.notify()
+    elif b.want:
+        call("mr_colsum", dt, ptr(g), ptr(db), N * Ho * Wo, Kw, Kp, 0)
+    b.notify()
+    return (dx, w.grad(lambda t: (t if (Cp == C and Kp == K) else t[:K, :, :, :C]).permute(0, 3, 1, 2)),
+            b.grad(lambda t: t if Kp == K else t[:K]))
 
 
 # data gradient of a strided 1x1 convolution as dense dgrad + scatter (round 4); MEGREADER_POINTWISE_STRIDED_DGRAD=0: the
@@ -861,27 +640,18 @@ class StemConvReluPoolFn(Function):
         dtype = ctx.dtype
         N, C, H, W = x.shape
         g = _grad_internal(gy, dtype)
-        want_dw = ctx.needs_input_grad[1]
-        want_db = bias_p is not None and ctx.needs_input_grad[2]
-        w_sink = grad_sink(weight_p, "strided") if want_dw else None
-        b_sink = grad_sink(bias_p, (64,)) if want_db else None
-        dw = db = None
-        if want_dw:
-            dw = w_sink if w_sink is not None else torch.zeros_like(weight_p)
-        if want_db:
-            db = b_sink if b_sink is not None else torch.zeros((64,), dtype=torch.float32, device=g.device)
+        w = GradDest(weight_p, ctx.needs_input_grad[1], "strided")      # the kernel takes the sink's own strides
+        b = GradDest(bias_p, bias_p is not None and ctx.needs_input_grad[2], (64,))
+        dw = w.into(lambda: torch.zeros_like(weight_p))
+        db = b.into(lambda: torch.zeros((64,), dtype=torch.float32, device=g.device))
         if dw is not None or db is not None:
             ws = torch.empty((load().mr_stem_bwd_workspace(C),), dtype=torch.float32, device=g.device)
             sk, sc, sr, ss = dw.stride() if dw is not None else (0, 0, 0, 0)
             call("mr_stem_bwd", dtype_code(dtype), ptr(g), ptr(code), ptr(x), ptr(ws), ptr(dw), sk, sc, sr, ss, ptr(db),
                  N, C, H, W)
-        if w_sink is not None:
-            notify_grad_ready(weight_p)
-            dw = None
-        if b_sink is not None:
-            notify_grad_ready(bias_p)
-            db = None
-        return None, dw, db
+        w.notify()
+        b.notify()
+        return None, w.grad(), b.grad()
 
 
 def stem_conv_relu_pool(x, weight, bias):
@@ -935,16 +705,9 @@ class ConvReluPoolFn(Function):
         dz = torch.empty((N, Ho, Wo, K), dtype=dtype, device=g.device)
         call("mr_maxpool_bwd", dtype_code(dtype), ptr(g), ptr(idx), ptr(y), ptr(dz), N, Ho, Wo, K, kh, kw, psh, psw, pph, ppw,
              PHo, PWo)
-
-        class _ConvCtx(object):      # what Conv2dFn.backward reads from its ctx (relu already applied by the pool's backward)
-            pass
-        c = _ConvCtx()
-        c.saved_tensors = (xi, w_crsk, None)
-        c.geom, c.dtype, c.params, c.has_bias = ctx.geom, dtype, ctx.params, ctx.has_bias
-        c.relu, c.bnb_link = False, None
-        c.needs_input_grad = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]) + (False,) * 8
-        grads = Conv2dFn.backward(c, dz.permute(0, 3, 1, 2))
-        return grads[0], grads[1], grads[2], None, None, None, None
+        # relu=False: the pool's backward applied the mask already
+        return _conv2d_backward((xi, w_crsk, None), ctx.geom, dtype, ctx.params, ctx.has_bias, False, None,
+                                ctx.needs_input_grad[:3], dz.permute(0, 3, 1, 2)) + (None,) * 4
 
 
 def conv_relu_pool_eligible(x, weight, stride, padding, dilation, pool_kernel, pool_stride, pool_padding):
@@ -1099,47 +862,38 @@ class LinearFn(Function):
                 gp[:, :Nout] = g2
         else:
             gp = g2 if (g2.dtype == dtype and g2.is_contiguous()) else g2.to(dtype).contiguous()
-        dx = dw = db = None
-        dx_fn = None
+        dx = dx_fn = None
         if ctx.needs_input_grad[0]:
             dx2 = torch.empty((M, K), dtype=dtype, device=gy.device)
             dx_fn = lambda: call("mr_gemm_nt", dt, ptr(gp), Np, ptr(w_t), Np, ptr(dx2), K, 0, 0, M, K, Np)
             dx = dx2.view(*ctx.lead, K)
         weight_p, bias_p = ctx.params
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        # sinks also when the output width is padded (38 classes in a 40-column buffer): the GEMM is then asked for
-        # NA = Nout rows of A^T B with lda = Np -- the padding columns feed output rows that are never stored
-        w_sink = grad_sink(weight_p, (Nout, K)) if ctx.needs_input_grad[1] else None
-        b_sink = grad_sink(bias_p, (Nout,)) if (want_db and (w_sink is not None or not ctx.needs_input_grad[1])) else None
-        NA = Nout if (w_sink is not None or (not ctx.needs_input_grad[1] and b_sink is not None)) else Np
-        gb = None
-        if want_db:
-            gb = b_sink if b_sink is not None else torch.zeros((Np,), dtype=torch.float32, device=gy.device)
-        if ctx.needs_input_grad[1]:
-            gw = w_sink if w_sink is not None else torch.zeros((Np, K), dtype=torch.float32, device=gy.device)
+        w = GradDest(weight_p, ctx.needs_input_grad[1], (Nout, K))
+        b = GradDest(bias_p, ctx.has_bias and ctx.needs_input_grad[2], (Nout,))
+        if w.want and not w.sunk:
+            b.sink = None      # bias sink only with a weight sink: one GEMM writes NA rows of both
+        # sinks also when the output width is padded (38 classes in a 40-column buffer): rows written = Nout when a sink takes
+        # them, else Np -- the GEMM computes NA rows of A^T B with lda = Np, the padding columns feed rows that are never stored
+        NA = Nout if (w.sunk or b.sunk) else Np
+        gb = b.into(lambda: torch.zeros((Np,), dtype=torch.float32, device=gy.device))
+        if w.want:
+            gw = w.into(lambda: torch.zeros((Np, K), dtype=torch.float32, device=gy.device))
             def lin_launch():
                 if dx_fn is not None:
                     dx_fn()
                 call("mr_gemm_tn", dt, ptr(gp), Np, ptr(x2), K, ptr(gw), K, M, NA, K, 0, ptr(gb))
             # sunk gradients: recorded for a grouped launch (_TnDefer); the flush reports the parameters ready
-            if _wgrad(lin_launch, w_sink is not None and (gb is None or b_sink is not None) and dtype == torch.bfloat16,
-                      (gp, x2), [weight_p] + ([bias_p] if want_db else [])):
+            if _wgrad(lin_launch, w.sunk and (not b.want or b.sunk) and dtype == torch.bfloat16, (gp, x2),
+                      [weight_p] + ([bias_p] if b.want else [])):
                 return dx, None, None
-            dx_fn = None
-            if w_sink is not None:
-                notify_grad_ready(weight_p)
-            else:
-                dw = gw[:Nout]
-        elif want_db:
-            call("mr_colsum", dt, ptr(gp), ptr(gb), M, NA, Np, 0)
-        if dx_fn is not None:
-            dx_fn()
-        if want_db:
-            if b_sink is not None:
-                notify_grad_ready(bias_p)
-            else:
-                db = gb[:Nout]
-        return dx, dw, db
+            w.notify()
+        else:
+            if b.want:
+                call("mr_colsum", dt, ptr(gp), ptr(gb), M, NA, Np, 0)
+            if dx_fn is not None:
+                dx_fn()
+        b.notify()
+        return dx, w.grad(lambda t: t[:Nout]), b.grad(lambda t: t[:Nout])
 
 
 def linear(x, weight, bias=None):
@@ -1208,43 +962,35 @@ class ConvTranspose2x2Fn(Function):
         dy2 = torch.empty((P, ld2), dtype=dtype, device=dev)
         call("mr_deconv2x2_s2d", dt, ptr(g), ptr(dy2), ld2, N, H, W, Cout)
         weight_p, bias_p = ctx.params
-        dx = dw = db = None
+        dx = dw = None
         if ctx.needs_input_grad[0]:
             dxi = torch.empty((N, H, W, Cin), dtype=dtype, device=dev)
             call("mr_gemm_nt", dt, ptr(dy2), ld2, ptr(w_n), ld2, ptr(dxi), Cin, 0, 0, P, Cin, ld2)
             dx = dxi.permute(0, 3, 1, 2)
-        want_db = bias_p is not None and ctx.needs_input_grad[2]
-        if want_db:
-            b_sink = grad_sink(bias_p, (Cout,))
-            gb = b_sink if b_sink is not None else torch.zeros((Cout,), dtype=torch.float32, device=dev)
+        b = GradDest(bias_p, bias_p is not None and ctx.needs_input_grad[2], (Cout,))
+        if b.want:
+            gb = b.into(lambda: torch.zeros((Cout,), dtype=torch.float32, device=dev))
             call("mr_colsum", dt, ptr(g), ptr(gb), N * 4 * H * W, Cout, Cout, 0)
-            if b_sink is not None:
-                notify_grad_ready(bias_p)
+            b.notify()
+        w = GradDest(weight_p, ctx.needs_input_grad[1])      # dense in the parameter's own (row-major) layout
+        if w.want and ld2 != K4:    # Cout = 1: the GEMM needs whole vectors of columns -- a padded scratch, folded into the gradient
+            tmp = torch.zeros((Cin, ld2), dtype=torch.float32, device=dev)
+            call("mr_gemm_tn", dt, ptr(x2), Cin, ptr(dy2), ld2, ptr(tmp), ld2, P, Cin, ld2, 0, 0)
+            if w.sunk:
+                w.sink.view(Cin, K4).add_(tmp[:, :K4])
+                w.notify()
             else:
-                db = gb
-        if ctx.needs_input_grad[1]:
-            w_sink = grad_sink(weight_p)      # dense in the parameter's own (row-major) layout
-            if ld2 != K4:     # Cout = 1: the GEMM needs whole vectors of columns -- a padded scratch, folded into the gradient
-                tmp = torch.zeros((Cin, ld2), dtype=torch.float32, device=dev)
-                call("mr_gemm_tn", dt, ptr(x2), Cin, ptr(dy2), ld2, ptr(tmp), ld2, P, Cin, ld2, 0, 0)
-                if w_sink is not None:
-                    w_sink.view(Cin, K4).add_(tmp[:, :K4])
-                    notify_grad_ready(weight_p)
-                else:
-                    dw = tmp[:, :K4].reshape(Cin, Cout, 2, 2)
-            else:
-                gw = w_sink if w_sink is not None else torch.zeros((Cin, K4), dtype=torch.float32, device=dev)
+                dw = tmp[:, :K4].reshape(Cin, Cout, 2, 2)
+        elif w.want:
+            gw = w.into(lambda: torch.zeros((Cin, K4), dtype=torch.float32, device=dev))
 
-                # dW[ci, (co, i, j)] += sum_p x[p, ci] dy2[p, (co, i, j)]: the parameter's own memory order
-                def deconv_launch():
-                    call("mr_gemm_tn", dt, ptr(x2), Cin, ptr(dy2), ld2, ptr(gw), K4, P, Cin, K4, 0, 0)
-                if _wgrad(deconv_launch, w_sink is not None and dtype == torch.bfloat16, (x2, dy2), [weight_p]):
-                    pass        # the flush reports the parameter ready
-                elif w_sink is not None:
-                    notify_grad_ready(weight_p)
-                else:
-                    dw = gw.view(Cin, Cout, 2, 2)
-        return dx, dw, db
+            # dW[ci, (co, i, j)] += sum_p x[p, ci] dy2[p, (co, i, j)]: the parameter's own memory order
+            def deconv_launch():
+                call("mr_gemm_tn", dt, ptr(x2), Cin, ptr(dy2), ld2, ptr(gw), K4, P, Cin, K4, 0, 0)
+            if not _wgrad(deconv_launch, w.sunk and dtype == torch.bfloat16, (x2, dy2), [weight_p]):
+                w.notify()      # (recorded: the flush reports the parameter ready)
+            dw = w.grad(lambda t: t.view(Cin, Cout, 2, 2))
+        return dx, dw, b.grad()
 
 
 class DBHeadTailFn(Function):
