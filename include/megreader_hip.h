@@ -149,6 +149,14 @@ int mr_set_tn_taps_workspace(void* ws, long long bytes);
  * under the current mr_tuning.tn_taps setting */
 int mr_tn_taps_would_run(int N, int H, int W, int Cin, int ldx, int Cout, int lddy, int R, int S, int sh, int sw,
                          int ph, int pw, int dh, int dw, int Ho, int Wo);
+/* host only: how mr_tn_flush launches n <= 12 recorded all-taps problems on a chip of `cus` CUs whose workspace holds `slabs`
+ * partial-tile slabs (0: atomics only).  tiles[i] = 64 x 64 x 9-tap output tiles, chunks[i] = 64-position chunks of the pixel
+ * stream of problem i; out: launch[i] (launch index, numbered by first problem), splits[i] workgroups per tile, cps[i] chunks
+ * per workgroup, *cost = the modelled cost in chunk-times: sum over the launches of ceil(sum tiles * splits / (2 * cus)) *
+ * (largest cps + 12).  Every partition is tried for n <= 8, greedy merging in recording order above.  Returns the number of
+ * launches, < 0 on bad arguments. */
+int mr_tn_taps_plan(int cus, int slabs, int n, const int* tiles, const int* chunks, int* launch, int* splits, int* cps,
+                    double* cost);
 /* tile (BM*1000+BN) the NT kernels pick for an M x N problem; host-only query used for profiling labels */
 int mr_nt_tile_code(int M, int N);
 /* same, including the big-tile policy (returns 256256 for the 8-wave 256x256 kernel); cg = channels of the gathered
@@ -168,9 +176,12 @@ int mr_gemm_tn2(int dtype, const void* A, long long lda, const void* B, long lon
  * ResNet at batch 32 (backbones/resnet.py:113-181), the LSTM / Linear layers of the CRNN head (decoders/crnn.py:8-24) -- are GEMMs
  * of 16..64 output tiles: alone, each has to cut its pixel loop into 8..32 splits to fill the chip.  Nothing later in the backward
  * pass reads them, so they can wait and run side by side.  mr_tn_defer(1): on the calling host thread, bf16 launches that would
- * take the 128x128 TN GEMM kernel (mr_gemm_tn; mr_conv2d_wgrad_tab off the all-taps kernel) are RECORDED (operand pointers and
- * geometry) instead of launched; mr_tn_defer(0) stops recording.  mr_tn_flush launches everything recorded, up to 12 problems per
- * launch, each with 1 / n-th of the splits.  The caller keeps every operand alive and unmodified until the flush, flushes on the
+ * take the 128x128 TN GEMM kernel (mr_gemm_tn, mr_conv2d_wgrad_tab) are RECORDED (operand pointers and geometry) instead of
+ * launched; mr_tn_defer(0) stops recording.  mr_tn_flush launches everything recorded, up to 12 problems per launch, each with
+ * 1 / n-th of the splits.  The 3x3 layers that mr_conv2d_wgrad_tab gives to the all-taps kernel are recorded too (their stream
+ * table is still built at once): every workgroup of that kernel pays a fixed price -- prologue and a 147 KB partial tile --
+ * whatever it reduced, so the flush packs up to 8 of them into one launch with fewer splits each (mr_tn_taps_plan); under
+ * mr_tuning.tn_taps_fin / tn_taps_w8 / tn_splits they are launched one by one.  The caller keeps every operand alive and unmodified until the flush, flushes on the
  * stream the operands were produced on, and must not read an output (or zero it) before the flush.  mr_tn_defer returns the
  * previous setting, mr_tn_pending the number of recorded problems (both host only).  mr_tuning.tn_defer = 0 makes mr_tn_defer a
  * no-op (A/B). */
@@ -238,7 +249,8 @@ int mr_conv2d_wgrad(int dtype, const void* dy, const void* x, float* dw_krsc, fl
  * ({element offset of the pixel's window in x, validity bit per tap}); build != 0 fills it first, build == 0 trusts
  * it (a layer's geometry is constant: build once, reuse every step).  bf16 and R*S <= 32; otherwise, or with
  * rowtab == NULL, identical to mr_conv2d_wgrad.  build bit 1: the launch may run concurrently with other weight-gradient
- * launches (another stream): the shared split-reduction workspace (mr_set_tn_taps_workspace) is not used, f32 atomics only. */
+ * launches (another stream): the shared split-reduction workspace (mr_set_tn_taps_workspace) is not used, f32 atomics only.
+ * Inside mr_tn_defer(1) the launch is recorded for mr_tn_flush (both kernels; not with build bit 1); the table is built at once. */
 int mr_conv2d_wgrad_tab(int dtype, const void* dy, const void* x, float* dw_krsc, float* dbias, int N, int H, int W,
                         int Cin, int ldx, int Cout, int lddy, int R, int S, int sh, int sw, int ph, int pw, int dh,
                         int dw, int Ho, int Wo, void* rowtab, int build, hipStream_t stream);

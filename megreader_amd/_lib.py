@@ -256,8 +256,9 @@ _TN_WS_CALLS = frozenset(("mr_gemm_tn", "mr_gemm_tn2", "mr_conv2d_wgrad", "mr_co
 
 def ensure_tn_workspace(device=None):
     """Register (once per device) the workspace of the weight-gradient kernels' in-launch split reduction
-    (mr_set_tn_taps_workspace): 16 KB of tickets + one 147456-byte slab per workgroup of a full launch (2 per CU).
-    Launches that use it must be stream-ordered with each other."""
+    (mr_set_tn_taps_workspace): 16 KB of tickets + one 147456-byte slab per workgroup of a full launch (2 per CU; the grouped
+    all-taps launches of mr_tn_flush are planned to fit the same slabs).  Launches that use it must be stream-ordered with each
+    other."""
     if device is None:
         idx = torch.cuda.current_device()
     else:

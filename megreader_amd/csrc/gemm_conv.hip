@@ -452,7 +452,8 @@ static int launch_tn_big(TnArgs a, const ConvGeom& g, int total_steps, hipStream
 // While deferral is on for the calling host thread, bf16 launches of the 128x128 TN GEMM kernel (dense: BMODE 0, conv with a row
 // table: BMODE 2) are RECORDED instead of launched; mr_tn_flush launches everything recorded so far, up to TN_GROUP_MAX problems
 // per launch.  The split of every problem is chosen for the GROUP: one p-step count L per workgroup for all problems, so that
-// the workgroups of the launch finish together and the chip is filled by problems, not by splits.
+// the workgroups of the launch finish together and the chip is filled by problems, not by splits.  All-taps problems
+// (mr_conv2d_wgrad_tab, tn_taps.hip) are recorded on a queue of their own; launch_tn_taps_group plans and launches them.
 #define g_tn_defer MR_TUNE(tn_defer)   // 1 (default): mr_tn_defer(1) records; 0: it is ignored (every launch immediate)
 struct TnRecord { TnArgs a; ConvGeom g; };
 // Recording is switched per host THREAD (the bracket mr_tn_defer(1) ... mr_tn_defer(0) is one autograd node's), the QUEUE is per
@@ -461,7 +462,12 @@ struct TnRecord { TnArgs a; ConvGeom g; };
 // that thread saw nothing pending, skipped the launch and still released the operands.
 struct TnDeferState { bool on = false; };
 static thread_local TnDeferState g_tn_defer_state;
-struct TnQueue { std::vector<TnRecord> q[2]; };   // [0]: BMODE 0, [1]: BMODE 2
+struct TnQueue {
+  std::vector<TnRecord> q[2];       // [0]: BMODE 0, [1]: BMODE 2
+  std::vector<TapsProblem> taps;    // all-taps kernel (tn_taps.hip): planned and launched by launch_tn_taps_group
+  size_t size() const { return q[0].size() + q[1].size() + taps.size(); }
+  void clear() { q[0].clear(); q[1].clear(); taps.clear(); }
+};
 static std::mutex g_tn_queue_mutex;
 static TnQueue g_tn_queue[MR_MAX_DEVICES];
 static TnQueue* tn_queue_of_current_device() {     // (call with g_tn_queue_mutex held); null: no device to queue for
@@ -527,8 +533,11 @@ static int tn_flush(hipStream_t stream, bool beside) {
     if (TnQueue* dq = tn_queue_of_current_device()) {
       mine.q[0].swap(dq->q[0]);
       mine.q[1].swap(dq->q[1]);
+      mine.taps.swap(dq->taps);
     }
   }
+  for (size_t i = 0; i < mine.taps.size() && rc == MR_OK; i += TAPS_PLAN_MAX)
+    rc = launch_tn_taps_group(&mine.taps[i], (int)std::min<size_t>(TAPS_PLAN_MAX, mine.taps.size() - i), beside, stream);
   for (int m = 0; m < 2 && rc == MR_OK; ++m) {
     std::vector<TnRecord>& q = mine.q[m];
     size_t i = 0;
@@ -753,6 +762,20 @@ int mr_tn_taps_would_run(int Nimg, int H, int W, int Cin, int ldx, int Cout, int
                         (long long)Nimg * Ho * Wo * 8)) ? 1 : 0;
 }
 
+// host only: the launch plan of mr_tn_flush for n recorded all-taps problems (taps_plan, tn_taps.h)
+int mr_tn_taps_plan(int cus, int slabs, int n, const int* tiles, const int* chunks, int* launch, int* splits, int* cps,
+                    double* cost) {
+  const double c = tiles && chunks && launch && splits && cps ? taps_plan(cus, slabs, n, tiles, chunks, launch, splits, cps) : -1.0;
+  if (c < 0.0) {
+    set_error("mr_tn_taps_plan: need 1 <= n <= %d, cus > 0, tiles > 0, chunks > 0 and non-null arrays", TAPS_PLAN_MAX);
+    return -1;
+  }
+  if (cost) *cost = c;
+  int launches = 0;
+  for (int i = 0; i < n; ++i) launches = std::max(launches, launch[i] + 1);
+  return launches;
+}
+
 // Which NT tile (BM*1000 + BN) a problem of M rows x N columns is dispatched to (profiling / bench labels).
 int mr_nt_tile_code(int M, int N) {
   const TileChoice t = nt_tile(M, N);
@@ -799,7 +822,7 @@ int mr_gemm_nt(int dtype, const void* A, long long lda, const void* B, int ldb, 
 }
 
 // Deferred weight-gradient launches.  mr_tn_defer(1): from now on, on the calling host thread, the bf16 weight-gradient GEMMs that
-// would run on the 128x128 TN kernel (mr_gemm_tn; mr_conv2d_wgrad_tab off the all-taps kernel) are recorded instead of launched;
+// would run on the 128x128 TN kernel (mr_gemm_tn, mr_conv2d_wgrad_tab) or on the all-taps kernel are recorded instead of launched;
 // mr_tn_defer(0) stops recording (what is recorded stays).  mr_tn_flush(stream) launches everything recorded, several problems
 // per launch.  The CALLER keeps every operand alive and unmodified until the flush and must not read an output before it.
 // Returns the previous setting.  Host only.
@@ -811,7 +834,7 @@ int mr_tn_defer(int on) {
 int mr_tn_pending(void) {
   std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
   const TnQueue* dq = tn_queue_of_current_device();
-  return dq ? (int)(dq->q[0].size() + dq->q[1].size()) : 0;
+  return dq ? (int)dq->size() : 0;
 }
 // Drops the current device's recorded problems WITHOUT launching them (a backward pass that raised: its records point at operands
 // the caller is about to release) and switches recording off for the calling thread; returns how many were dropped.  Host only.
@@ -820,9 +843,8 @@ int mr_tn_discard(void) {
   std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
   TnQueue* dq = tn_queue_of_current_device();
   if (!dq) return 0;
-  const int n = (int)(dq->q[0].size() + dq->q[1].size());
-  dq->q[0].clear();
-  dq->q[1].clear();
+  const int n = (int)dq->size();
+  dq->clear();
   return n;
 }
 int mr_tn_flush(hipStream_t stream) { return tn_flush(stream, false); }
@@ -1066,6 +1088,17 @@ int mr_conv2d_wgrad_tab(int dtype, const void* dy, const void* x, float* dw_krsc
     TapsProblem tp;
     tp.dy = dy; tp.x = x; tp.dw = dw_krsc; tp.dbias = dbias; tp.tab = (int*)rowtab; tp.build = build; tp.beside = beside;
     tp.N = Nimg; tp.H = H; tp.W = W; tp.Cin = Cin; tp.ldx = ldx; tp.Cout = Cout; tp.lddy = lddy; tp.dil = dh;
+    // inside a recording bracket the problem waits for the flush (the conditions of launch_tn); its table is built now
+    if (g_tn_defer_state.on && g_tn_defer && g_tn_splits == 0 && !beside) {
+      std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
+      if (TnQueue* dq = tn_queue_of_current_device()) {
+        if (build)
+          if (const int rc = taps_build_table(tp, stream)) return rc;
+        tp.build = 0;
+        dq->taps.push_back(tp);
+        return MR_OK;
+      }
+    }
     return launch_tn_taps(tp, g_tn_splits, stream);
   }
   TnArgs a;

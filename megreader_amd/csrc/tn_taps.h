@@ -29,4 +29,20 @@ int taps_set_abl(int mask);   // timing-only ablations (wrong results), see tn_t
 #endif
 int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream);
 
+// ---- recorded problems (mr_tn_defer / mr_tn_flush): several problems per launch, so that the workgroup slots of the chip are
+// filled by problems, not by splits, and the fixed price of a workgroup is paid once per slot instead of once per layer.
+constexpr int TAPS_PLAN_MAX = 12;   // problems per plan (= TN_GROUP_MAX)
+int taps_build_table(const TapsProblem& p, hipStream_t stream);   // what p.build != 0 does, for a problem that is recorded
+// Launches p[0..n) (tables built, n <= TAPS_PLAN_MAX) as taps_plan partitions them; a problem alone in its launch goes through
+// launch_tn_taps.  p[i].build / p[i].beside are ignored: `beside` is the flush's.
+int launch_tn_taps_group(const TapsProblem* p, int n, bool beside, hipStream_t stream);
+// Host only.  Partitions n problems (tiles[i] output tiles of 64 Cout x 64 Cin x 9 taps, chunks[i] 64-position chunks to
+// reduce) into launches on a chip of `cus` CUs with `slabs` partial-tile slabs in the workspace (0: none, atomics only) and
+// cuts each into splits[i] workgroups of cps[i] chunks per tile.  Model, in chunk-times, summed over the launches:
+// ceil(sum tiles * splits / (2 * cus)) * (largest cps of the launch + a fixed price per workgroup).  Up to 8 problems every
+// partition is tried, above that problems are merged greedily in recording order.  launch[i] = launch index of problem i
+// (0 .. launches-1, numbered by their first problem).  Returns the modelled cost, < 0 on bad arguments.
+double taps_plan(int cus, int slabs, int n, const int* tiles, const int* chunks, int* launch, int* splits, int* cps);
+double taps_plan_cost(int cus, int n, const int* tiles, const int* launch, const int* splits, const int* cps);
+
 }  // namespace mr

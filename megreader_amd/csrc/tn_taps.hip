@@ -28,6 +28,11 @@
 #include "device.h"
 #include "tuning.h"
 #include "igemm_core.h"
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <type_traits>
+#include <vector>
 
 namespace mr {
 
@@ -88,6 +93,35 @@ __device__ __forceinline__ bf16x8 and_mask(bf16x8 v, u32x4 m) {
   return __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, v) & m);
 }
 
+// Grouped launch (mr_tn_defer / mr_tn_flush, launch_tn_taps_group): up to TAPS_GROUP_MAX all-taps problems in ONE launch, so
+// that the workgroup slots of the chip are filled by problems instead of by splits and the fixed price of a workgroup
+// (prologue + 147 KB partial tile) is paid once per slot, not once per layer.  Problem i owns the contiguous range
+// [end[i-1], end[i]) of the launch-wide virtual order, split-major inside: the tiles of one split still share an XCD's L2.
+// The struct travels by value in the kernarg segment.  fin == 0, 4-wave variant only.
+constexpr int TAPS_GROUP_MAX = 8;
+struct TapsGroup {
+  TapArgs a[TAPS_GROUP_MAX];
+  int end[TAPS_GROUP_MAX];   // exclusive end of problem i's virtual range (tiles * splits workgroups)
+  int tk0[TAPS_GROUP_MAX];   // first ticket of problem i
+  int n;
+};
+// the kernel's view of its argument: one problem (everything constant) or problem i of a group
+__device__ __forceinline__ const TapArgs& taps_args_of(const TapArgs& a, int) { return a; }
+__device__ __forceinline__ const TapArgs& taps_args_of(const TapsGroup& g, int i) { return g.a[i]; }
+__device__ __forceinline__ int taps_begin_of(const TapArgs&, int) { return 0; }
+__device__ __forceinline__ int taps_begin_of(const TapsGroup& g, int i) { return i > 0 ? g.end[i - 1] : 0; }
+__device__ __forceinline__ int taps_end_of(const TapArgs&, int) { return (int)gridDim.x; }
+__device__ __forceinline__ int taps_end_of(const TapsGroup& g, int i) { return g.end[i]; }
+__device__ __forceinline__ int taps_tk0_of(const TapArgs&, int) { return 0; }
+__device__ __forceinline__ int taps_tk0_of(const TapsGroup& g, int i) { return g.tk0[i]; }
+
+// launch-wide virtual block index (see the work map in the kernel)
+__device__ __forceinline__ int taps_virtual_block() {
+  const int total = gridDim.x;
+  const int xq = total >> 3, xr = total & 7, xcd = blockIdx.x & 7;
+  return xcd * xq + (xcd < xr ? xcd : xr) + (blockIdx.x >> 3);
+}
+
 // RL: log2 of the x ring length in chunks (2 -> 32 KB, 3 -> 64 KB).  HALO: chunks of x needed either side of the
 // current one (|shift| <= 64*HALO).  COLSUM: the tile_b == 0 workgroups also produce the bias gradient.
 // ABL (timing only, wrong results): bit 0 = no LDS-DMA in the loop, bit 1 = x fragments read once per chunk half and
@@ -96,8 +130,19 @@ __device__ __forceinline__ bf16x8 and_mask(bf16x8 v, u32x4 m) {
 // consecutive split ranges) that share the barriers; at the end waves 4-7 hand their accumulators to waves 0-3 through
 // LDS, so a CU produces ONE partial tile instead of two (the partials -- 147 KB per workgroup -- are what the epilogue
 // costs: their volume is (#workgroups) x (tile size), whatever the reduction scheme).
-template <int RL, int HALO, int ABL = 0, bool W8 = false>
-__global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 1 : 2) void igemm_tn_taps_kernel(TapArgs a) {
+//
+// ARGS: TapArgs = ONE problem on the whole grid; TapsGroup = several problems in one launch.  Then everything
+// problem-specific is read from the selected TapArgs (uniform index), the workgroup's indices are taken inside its problem's
+// range, slabs are indexed launch-wide (one per workgroup of the launch) and tickets start at the problem's tk0.
+template <int RL, int HALO, int ABL = 0, bool W8 = false, typename ARGS = TapArgs>
+__global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 1 : 2) void igemm_tn_taps_kernel(ARGS args) {
+  int pi = 0;   // the problem of this workgroup
+  if constexpr (std::is_same<ARGS, TapsGroup>::value) {
+    const int v = taps_virtual_block();
+    while (pi + 1 < args.n && v >= args.end[pi]) ++pi;   // uniform: scalar loads from the kernarg segment
+  }
+  const TapArgs& a = taps_args_of(args, pi);
+  const int slab0 = taps_begin_of(args, pi);   // launch-wide index of the problem's first workgroup = its first slab
   constexpr int ROWB = 128, CHB = 64 * ROWB;                 // bytes per row / per 64-row chunk
   constexpr int XRING = (1 << RL) * CHB, XMASK = XRING - 1;  // x ring bytes
   constexpr int ARING = 4 * CHB;
@@ -113,9 +158,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 1 : 2) void igemm_tn_taps_kern
   const int tiles_b = a.Cg >> 6, tiles_a = (a.NA + 63) >> 6;
   // XCD-aware work map, as igemm_tn_glds_kernel: split-major virtual order, every XCD takes a contiguous eighth, so
   // the workgroups that share an L2 stream through the same rows of dy / x.
-  const int total = gridDim.x;
-  const int xq = total >> 3, xr = total & 7, xcd = blockIdx.x & 7;
-  const int vb = xcd * xq + (xcd < xr ? xcd : xr) + (blockIdx.x >> 3);
+  const int vb = taps_virtual_block() - slab0;   // index inside the problem's range
   const int ntiles = tiles_a * tiles_b;
   const int split = vb / ntiles, tile = vb - split * ntiles;   // split = the WORKGROUP's index along the reduction
   const int tile_b = tile % tiles_b, tile_a = tile / tiles_b;
@@ -303,14 +346,14 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 1 : 2) void igemm_tn_taps_kern
     // ticket; the last arriver reads the slabs with sc1 loads (cdna guide, split-K reducer recipe, sc1 form: no
     // release / acquire fences -- a release would write back the whole XCD L2, i.e. everybody's slabs, once per
     // workgroup: measured no faster than the atomics it replaced).
-    const int nsplits = total / ntiles;
+    const int nsplits = (taps_end_of(args, pi) - slab0) / ntiles;
     const int g0 = (split / a.grp) * a.grp;
     const int gsize = a.fin == 2 ? 2 : min(a.grp, nsplits - g0);
     const rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((char*)a.ws + TAPS_TICKETS * 4, (short)0, 0x7fffffff,
                                                        0x00020000);
     if (gsize > 1) {
       int* tickets = (int*)a.ws;
-      const int so = vb * (int)TAPS_SLAB_BYTES;
+      const int so = (slab0 + vb) * (int)TAPS_SLAB_BYTES;
       if (worker) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -325,7 +368,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 1 : 2) void igemm_tn_taps_kern
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       volatile __attribute__((address_space(3))) int* bc = (volatile __attribute__((address_space(3))) int*)(lds_byte_t*)(uintptr_t)0u;
-      int* tk = tickets + (tile * ((nsplits + a.grp - 1) / a.grp) + split / a.grp) % TAPS_TICKETS;
+      int* tk = tickets + (taps_tk0_of(args, pi) + tile * ((nsplits + a.grp - 1) / a.grp) + split / a.grp) % TAPS_TICKETS;
       if (tid8 == 0) *bc = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __syncthreads();
       const int ticket = *bc;
@@ -334,7 +377,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 1 : 2) void igemm_tn_taps_kern
       for (int j = 0; worker && j < gsize && !(ABL & 512); ++j) {   // ABL 512, timing only: no slab reads
         const int vbj = (g0 + j) * ntiles + tile;
         if (vbj == vb) continue;
-        const int sj = vbj * (int)TAPS_SLAB_BYTES;
+        const int sj = (slab0 + vbj) * (int)TAPS_SLAB_BYTES;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -344,7 +387,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 1 : 2) void igemm_tn_taps_kern
     }
     if (a.fin) {   // leave the group's sum in the slab of its first split; taps_finalize_kernel adds it into dw
       if (worker) {
-        const int sg = (g0 * ntiles + tile) * (int)TAPS_SLAB_BYTES;
+        const int sg = (slab0 + g0 * ntiles + tile) * (int)TAPS_SLAB_BYTES;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -464,13 +507,43 @@ static int g_taps_abl = 0;
 int taps_set_abl(int mask) { const int old = g_taps_abl; g_taps_abl = mask; return old; }
 #endif
 
-int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream) {
-  const TapsLayout l = taps_layout(p.N, p.H, p.W, p.dil);
-  if (p.build) {
-    hipLaunchKernelGGL(taps_table_kernel, dim3(cdiv(l.len, 256)), dim3(256), 0, stream, p.N, p.H, p.W, l.Wp, l.IP,
-                       l.len, p.tab);
-    MR_CHECK_LAUNCH();
+// Host-side model of a launch, in chunk-times: every round of 2 workgroups per CU costs the chunks of its longest workgroup
+// plus a fixed price -- prologue (stream table, mask table, three staged chunks) and epilogue (147 KB partial tile, ticket,
+// the leader's slab reads and atomics) -- that does not depend on how much the workgroup reduced.
+constexpr double TAPS_FIXED_CHUNKS = 12.0;
+static double taps_launch_cost(long long blocks, int slots, int cps) {
+  return (double)((blocks + slots - 1) / slots) * (cps + TAPS_FIXED_CHUNKS);
+}
+// split count of a problem that has the launch to itself (halves: independent reduction ranges per workgroup)
+static int taps_single_splits(int tiles, int nchunks, int halves, int slots, int cus) {
+  int splits = 1;
+  double best = 1e300;
+  for (int s = 1; s * halves <= nchunks; ++s) {
+    const long long blocks = (long long)tiles * s;
+    const double cost = taps_launch_cost(blocks, slots, cdiv(nchunks, s * halves));
+    if (cost < best) { best = cost; splits = s; }
+    if (blocks > 8ll * cus) break;
   }
+  return splits;
+}
+// group size of the in-launch reduction a problem of `splits` splits asks for (1: atomics only)
+static int taps_want_group(int splits) {
+  int want = g_taps_grp ? g_taps_grp : (splits >= 4 ? 4 : (splits >= 2 ? 2 : 1));
+  if (want > splits) want = splits;
+  return want < 1 ? 1 : want;
+}
+
+int taps_build_table(const TapsProblem& p, hipStream_t stream) {
+  const TapsLayout l = taps_layout(p.N, p.H, p.W, p.dil);
+  hipLaunchKernelGGL(taps_table_kernel, dim3(cdiv(l.len, 256)), dim3(256), 0, stream, p.N, p.H, p.W, l.Wp, l.IP, l.len,
+                     p.tab);
+  MR_CHECK_LAUNCH();
+  return MR_OK;
+}
+
+// everything of TapArgs that follows from the problem alone (not cps / grp / ws / fin)
+static TapArgs taps_args(const TapsProblem& p) {
+  const TapsLayout l = taps_layout(p.N, p.H, p.W, p.dil);
   TapArgs a;
   a.A = p.dy; a.B = p.x; a.C = p.dw; a.tab = p.tab; a.colsum = p.dbias;
   a.NA = p.Cout; a.Cg = p.Cin; a.lda = p.lddy; a.ldg = p.ldx; a.ldc = 9 * p.Cin;
@@ -479,21 +552,21 @@ int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream
   a.bot_hi = (p.H - p.dil) * l.Wp;
   a.dil = p.dil;
   a.nchunks = l.len / 64;
+  a.cps = a.nchunks; a.grp = 1; a.ws = nullptr; a.fin = 0;
+  return a;
+}
+
+int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream) {
+  if (p.build)
+    if (const int rc = taps_build_table(p, stream)) return rc;
+  TapArgs a = taps_args(p);
   const int tiles = cdiv(p.Cout, 64) * (p.Cin / 64);
   const int cus = num_cus();
   const int w8 = g_taps_w8;
   const int per_cu = w8 ? 1 : 2;   // resident workgroups per CU
   const int halves = w8 ? 2 : 1;   // independent reduction ranges per workgroup
   // split count (workgroups along the reduction): a workgroup pays ~3 chunks of prologue and a 147 KB epilogue
-  int splits = 1;
-  double best = 1e300;
-  for (int s = 1; s * halves <= a.nchunks; ++s) {
-    const long long blocks = (long long)tiles * s;
-    const long long rounds = (blocks + per_cu * cus - 1) / (per_cu * cus);
-    const double cost = (double)rounds * (cdiv(a.nchunks, s * halves) + 12.0);
-    if (cost < best) { best = cost; splits = s; }
-    if (blocks > 8ll * cus) break;
-  }
+  int splits = taps_single_splits(tiles, a.nchunks, halves, per_cu * cus, cus);
   if (splits_override > 0) splits = splits_override;
   if (splits * halves > a.nchunks) splits = a.nchunks / halves > 0 ? a.nchunks / halves : 1;
   a.cps = cdiv(a.nchunks, splits * halves);
@@ -505,8 +578,7 @@ int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream
   if (!p.beside) taps_get_workspace(&g_taps_ws, &g_taps_ws_bytes);
   a.ws = g_taps_ws;
   {
-    int want = g_taps_grp ? g_taps_grp : (splits >= 4 ? 4 : (splits >= 2 ? 2 : 1));
-    if (want > splits) want = splits;
+    const int want = taps_want_group(splits);
     const long long need = TAPS_TICKETS * 4ll + (long long)tiles * splits * TAPS_SLAB_BYTES;
     if (want > 1 && g_taps_ws && need <= g_taps_ws_bytes && need < (1ll << 31) &&
         (long long)tiles * cdiv(splits, want) <= TAPS_TICKETS)
@@ -547,6 +619,189 @@ int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream
     hipLaunchKernelGGL(taps_finalize_kernel, dim3(tiles * 36), dim3(256), 0, stream,
                        (const f32x4*)((const char*)a.ws + TAPS_TICKETS * 4), a.C, tiles, p.Cin / 64, splits,
                        a.fin == 2 ? 1 : a.grp, a.NA, a.Cg, a.ldc);
+    MR_CHECK_LAUNCH();
+  }
+  return MR_OK;
+}
+
+// ---- grouped launches of recorded problems (mr_tn_defer / mr_tn_flush) ------------------------------------------------------
+namespace {
+struct TapsSetPlan { double cost; int L; };   // L = chunks per workgroup asked of every problem of the set (0: single launch)
+
+// `want` splits of a reduction of `chunks` chunks, as launch_tn_taps cuts it: equal workgroups, no empty one
+void taps_cut(int chunks, int want, int* splits, int* cps) {
+  *cps = cdiv(chunks, want);
+  *splits = cdiv(chunks, *cps);
+}
+
+// Problems `mask` of (tiles, chunks) in ONE launch: every problem is cut into workgroups of about L chunks, the launch costs
+// rounds * (its longest workgroup + the fixed price).  A launch whose problems reduce through slabs needs one slab per
+// workgroup and unique tickets; slabs == 0 (no workspace, or a flush beside another stream): atomics only.
+TapsSetPlan taps_plan_set(unsigned mask, int n, const int* tiles, const int* chunks, int cus, int slabs) {
+  TapsSetPlan best = {1e300, 0};
+  int max_chunks = 1, members = 0, first = -1;
+  for (int i = 0; i < n; ++i)
+    if (mask >> i & 1) { max_chunks = std::max(max_chunks, chunks[i]); ++members; if (first < 0) first = i; }
+  if (members == 1) {   // what launch_tn_taps does
+    int sp, cps;
+    taps_cut(chunks[first], taps_single_splits(tiles[first], chunks[first], 1, 2 * cus, cus), &sp, &cps);
+    best.cost = taps_launch_cost((long long)tiles[first] * sp, 2 * cus, cps);
+    return best;
+  }
+  if (members > TAPS_GROUP_MAX) return best;
+  for (int L = max_chunks; L >= 1; --L) {
+    long long blocks = 0, tickets = 0;
+    int longest = 0;
+    bool use_slabs = false;
+    for (int i = 0; i < n; ++i) {
+      if (!(mask >> i & 1)) continue;
+      int sp, cps;
+      taps_cut(chunks[i], cdiv(chunks[i], L), &sp, &cps);
+      blocks += (long long)tiles[i] * sp;
+      longest = std::max(longest, cps);
+      const int grp = slabs > 0 ? taps_want_group(sp) : 1;
+      if (grp > 1) { use_slabs = true; tickets += (long long)tiles[i] * cdiv(sp, grp); }
+    }
+    if (blocks > 8ll * cus && best.L) break;
+    if (use_slabs && (blocks > slabs || blocks * TAPS_SLAB_BYTES >= (1ll << 31) || tickets > TAPS_TICKETS)) continue;
+    const double cost = taps_launch_cost(blocks, 2 * cus, longest);
+    if (cost < best.cost) { best.cost = cost; best.L = L; }
+  }
+  return best;
+}
+}  // namespace
+
+double taps_plan_cost(int cus, int n, const int* tiles, const int* launch, const int* splits, const int* cps) {
+  double total = 0.0;
+  for (int l = 0; l < n; ++l) {
+    long long blocks = 0;
+    int longest = 0;
+    for (int i = 0; i < n; ++i)
+      if (launch[i] == l) { blocks += (long long)tiles[i] * splits[i]; longest = std::max(longest, cps[i]); }
+    if (blocks) total += taps_launch_cost(blocks, 2 * cus, longest);
+  }
+  return total;
+}
+
+double taps_plan(int cus, int slabs, int n, const int* tiles, const int* chunks, int* launch, int* splits, int* cps) {
+  if (n <= 0 || n > TAPS_PLAN_MAX || cus <= 0) return -1.0;
+  for (int i = 0; i < n; ++i)
+    if (tiles[i] <= 0 || chunks[i] <= 0) return -1.0;
+  // a training step records the same problems every time: remember the plans (the search is ~1 ms for 8 problems)
+  static std::mutex cache_mutex;
+  static std::map<std::vector<int>, std::vector<int>> cache;
+  std::vector<int> key = {cus, slabs, (int)g_taps_grp};
+  key.insert(key.end(), tiles, tiles + n);
+  key.insert(key.end(), chunks, chunks + n);
+  {
+    std::lock_guard<std::mutex> lock(cache_mutex);
+    const auto hit = cache.find(key);
+    if (hit != cache.end()) {
+      const std::vector<int>& v = hit->second;
+      for (int i = 0; i < n; ++i) { launch[i] = v[3 * i]; splits[i] = v[3 * i + 1]; cps[i] = v[3 * i + 2]; }
+      return taps_plan_cost(cus, n, tiles, launch, splits, cps);
+    }
+  }
+  std::vector<unsigned> sets;   // the launches, as bit masks of problems
+  if (n <= 8) {
+    // every partition: best[m] = cheapest way to launch the problems of m; the set that holds m's lowest problem is tried
+    // in every way
+    const unsigned full = (1u << n) - 1;
+    std::vector<double> set_cost(full + 1, 0.0), best(full + 1, 1e300);
+    std::vector<unsigned> pick(full + 1, 0);
+    for (unsigned m = 1; m <= full; ++m) set_cost[m] = taps_plan_set(m, n, tiles, chunks, cus, slabs).cost;
+    best[0] = 0.0;
+    for (unsigned m = 1; m <= full; ++m) {
+      const unsigned low = m & (~m + 1);
+      for (unsigned sub = m; sub; sub = (sub - 1) & m) {
+        if (!(sub & low)) continue;
+        const double c = set_cost[sub] + best[m ^ sub];
+        // ties go to the fewer problems per launch: single launches are the measured path
+        if (c < best[m] || (c == best[m] && __builtin_popcount(sub) < __builtin_popcount(pick[m]))) { best[m] = c; pick[m] = sub; }
+      }
+    }
+    for (unsigned m = full; m; m ^= pick[m]) sets.push_back(pick[m]);
+  } else {
+    // greedy, in recording order: a problem joins the launch before it when that is modelled cheaper than a launch of its own
+    unsigned cur = 1u;
+    for (int i = 1; i < n; ++i) {
+      const unsigned with = cur | (1u << i);
+      if (taps_plan_set(with, n, tiles, chunks, cus, slabs).cost <
+          taps_plan_set(cur, n, tiles, chunks, cus, slabs).cost + taps_plan_set(1u << i, n, tiles, chunks, cus, slabs).cost)
+        cur = with;
+      else { sets.push_back(cur); cur = 1u << i; }
+    }
+    sets.push_back(cur);
+  }
+  for (size_t l = 0; l < sets.size(); ++l) {
+    const TapsSetPlan sp = taps_plan_set(sets[l], n, tiles, chunks, cus, slabs);
+    for (int i = 0; i < n; ++i) {
+      if (!(sets[l] >> i & 1)) continue;
+      launch[i] = (int)l;
+      taps_cut(chunks[i], sp.L ? cdiv(chunks[i], sp.L) : taps_single_splits(tiles[i], chunks[i], 1, 2 * cus, cus), &splits[i],
+               &cps[i]);
+    }
+  }
+  {
+    std::lock_guard<std::mutex> lock(cache_mutex);
+    if (cache.size() >= 256) cache.clear();
+    std::vector<int>& v = cache[key];
+    for (int i = 0; i < n; ++i) { v.push_back(launch[i]); v.push_back(splits[i]); v.push_back(cps[i]); }
+  }
+  return taps_plan_cost(cus, n, tiles, launch, splits, cps);
+}
+
+int launch_tn_taps_group(const TapsProblem* p, int n, bool beside, hipStream_t stream) {
+  if (n <= 0) return MR_OK;
+  bool singly = n == 1 || n > TAPS_PLAN_MAX || g_taps_w8 || g_taps_fin;   // the grouped kernel is the 4-wave, fin == 0 form
+#ifdef MR_ABLATION
+  singly = singly || g_taps_abl;
+#endif
+  void* ws = nullptr;
+  long long ws_bytes = 0;
+  if (!beside) taps_get_workspace(&ws, &ws_bytes);
+  const int slabs = ws ? (int)std::min<long long>((ws_bytes - TAPS_TICKETS * 4ll) / TAPS_SLAB_BYTES, 1 << 20) : 0;
+  int tiles[TAPS_PLAN_MAX], chunks[TAPS_PLAN_MAX], launch[TAPS_PLAN_MAX], splits[TAPS_PLAN_MAX], cps[TAPS_PLAN_MAX];
+  TapArgs args[TAPS_PLAN_MAX];
+  for (int i = 0; i < n && !singly; ++i) {
+    args[i] = taps_args(p[i]);
+    tiles[i] = cdiv(p[i].Cout, 64) * (p[i].Cin / 64);
+    chunks[i] = args[i].nchunks;
+  }
+  if (!singly && taps_plan(num_cus(), slabs, n, tiles, chunks, launch, splits, cps) < 0.0) singly = true;
+  for (int l = 0; l < n; ++l) {   // launch l = the problems with launch[i] == l (none: the plan has fewer launches)
+    int idx[TAPS_PLAN_MAX], m = 0;
+    for (int i = 0; i < n; ++i)
+      if (singly ? i == l : launch[i] == l) idx[m++] = i;
+    if (m == 0) break;
+    if (m == 1) {
+      TapsProblem one = p[idx[0]];
+      one.build = 0;
+      one.beside = beside;
+      if (const int rc = launch_tn_taps(one, 0, stream)) return rc;
+      continue;
+    }
+    TapsGroup grp;
+    int end = 0, tickets = 0;
+    for (int k = 0; k < m; ++k) {
+      TapArgs a = args[idx[k]];
+      a.cps = cps[idx[k]];
+      a.grp = slabs > 0 ? taps_want_group(splits[idx[k]]) : 1;
+      a.ws = ws;
+      grp.a[k] = a;
+      grp.tk0[k] = tickets;
+      if (a.grp > 1) tickets += tiles[idx[k]] * cdiv(splits[idx[k]], a.grp);
+      end += tiles[idx[k]] * splits[idx[k]];
+      grp.end[k] = end;
+    }
+    if (end > slabs || tickets > TAPS_TICKETS || end * TAPS_SLAB_BYTES >= (1ll << 31))   // (the plan never asks for this)
+      for (int k = 0; k < m; ++k) grp.a[k].grp = 1;
+    for (int k = m; k < TAPS_GROUP_MAX; ++k) { grp.a[k] = grp.a[0]; grp.end[k] = end; grp.tk0[k] = 0; }
+    grp.n = m;
+    const int lds = (4 + 4) * 64 * 128 + 4096;
+    const void* kp = (const void*)igemm_tn_taps_kernel<2, 1, 0, false, TapsGroup>;
+    if (const int rc = ensure_dynamic_lds(kp, lds)) return rc;
+    hipLaunchKernelGGL((igemm_tn_taps_kernel<2, 1, 0, false, TapsGroup>), dim3(end), dim3(256), lds, stream, grp);
     MR_CHECK_LAUNCH();
   }
   return MR_OK;

@@ -143,7 +143,8 @@ def accumulate_multi(pairs):
 class _TnDefer(object):
     """Deferred, grouped weight-gradient launches (include/megreader_hip.h: mr_tn_defer / mr_tn_flush).  Nothing later in a
     backward pass reads a weight gradient that goes to a gradient sink, so the small weight-gradient GEMMs (ResNet 1x1 / strided
-    layers, LSTM / Linear layers) are recorded while backward runs and launched several problems per launch: at the latest from
+    layers, LSTM / Linear layers) and the 3x3 layers of the all-taps kernel (conv2..conv5 of the CRNN, the ResNet bottlenecks)
+    are recorded while backward runs and launched several problems per launch: at the latest from
     an autograd-engine callback at the end of the backward pass, earlier whenever MAX problems are waiting.  The operands of the
     recorded problems are kept alive here until the flush; parameters are reported to data-parallel wrappers
     (notify_grad_ready) only after the launch that completes their gradient.
@@ -213,7 +214,7 @@ class _TnDefer(object):
     @staticmethod
     def end(tensors, params):
         """Stop recording.  True when the calls since begin() were recorded (the caller must then NOT report its parameters
-        ready: the flush does); False when the library launched them at once (f32, all-taps kernel, mr_tuning.tn_defer = 0)."""
+        ready: the flush does); False when the library launched them at once (f32, mr_tuning.tn_defer = 0 or tn_splits != 0)."""
         lib = load()
         lib.mr_tn_defer(0)
         n = lib.mr_tn_pending()

@@ -45,6 +45,8 @@ def label(name):
     if re.search(r"igemm_tn_glds_kernel<[12]", name) or re.search(r"igemm_tn_glds_kernelILi[12]E", name):
         return "igemm_tn_kernel<bf16,conv>"
     if "igemm_tn_taps_kernel" in name:
+        if "TapsGroup" in name:   # several recorded problems in one launch (mr_tn_flush)
+            return "igemm_tn_taps_kernel<bf16,3x3,grouped>"
         return "igemm_tn_taps_kernel<bf16,3x3>"
     if "igemm_tn_glds_grouped_kernel" in name:
         return "igemm_tn_glds_grouped_kernel<bf16>"
