@@ -1108,6 +1108,52 @@ int mr_ctc_align(int dtype, const void* pred, long long sn, long long sc, long l
                  float* score, int* pos, int* begin, int* end, float* sym_lp, int* peak,
                  void* ws, long long ws_bytes, hipStream_t stream);
 
+/* ---- Reading a 2D-CTC head with the 1-D readers (csrc/ctc2d_read.hip).  The eval output of a 2D-CTC head is classify [N, C, H, W]
+ * (softmax over the classes) and mask [N, 1, H, W] (softmax over the heights).  The 2D-CTC recursion (ops/ctc_2d/csrc/cuda/
+ * ctc2d_cuda_kernel.cu:125-175) sums alpha over all heights of the previous column before every step, so alpha summed over h obeys
+ * the 1-D CTC recursion on q[n, c, w] = sum_h classify[n, c, h, w] * mask[n, 0, h, w]: the string probabilities of the 2-D head are
+ * those of the 1-D posterior q, and mr_lexicon_transcribe, mr_ctc_beam_search and mr_ctc_align read it as they read any other.  (Two
+ * differences from the training loss: it returns inf for an empty target, where the 1-D readers give the all-blank probability;
+ * and it clamps every product at `tiny` before the log, which the eval tensors are not.)  With max for sum, mr_ctc_greedy_decode of
+ * the result is the 2-D greedy rule of mr_ctc2d_greedy_decode wherever no two products of a column tie.
+ *
+ * mr_ctc2d_marginal: out[n, c, w] = reduce over h of classify[n, c, h, w] * mask[n, 0, h, w].
+ *   classify at classify + n*cn + c*cc + h*ch + w*cw, mask at mask + n*mn + h*mh + w*mw (element strides, as mr_ctc2d_greedy_decode
+ *   takes them); both MR_DTYPE_F32 or both MR_DTYPE_BF16, converted to f32 on load.  out: f32 at out + n*on + c*oc + w*ow.
+ *   Arithmetic, the same bits whatever the strides, the tile or the launch: every product is rounded to f32 on its own; reduce == 0
+ *   adds them in ascending h, one f32 addition each, starting from the product of h = 0 (nothing fused, nothing reassociated);
+ *   reduce == 1 takes fmaxf in the same order.  H == 0 gives 0.  With log_out == 1 the result is replaced by the f32 nearest to its
+ *   log (taken in f64 and rounded once; 0 gives -inf): the lp the CTC readers define for log_probs == 0, so passing the logs with
+ *   log_probs == 1 gives them the bits they would compute themselves.
+ *   One launch, capturable.  classify is read once, the mask once per tile of 32 classes x 32 columns.  Two thread mappings, by the
+ *   strides: cc == 1 (an NHWC buffer viewed as NCHW, the project's own head) reads along the classes, everything else along the
+ *   columns (a contiguous NCHW tensor: cw == 1); other strides are correct, not fast.  The stores run along w either way.
+ *   N, C, H, W >= 0; N, C or W == 0 returns MR_OK without a launch, and pointers may be null only where their tensor has no element.
+ *   MR_ERR_ARG, nothing written: a negative size, reduce or log_out outside {0, 1}, sizes times strides beyond a 64-bit offset, more
+ *   than INT_MAX tiles, a null pointer; MR_ERR_DTYPE: another dtype code.
+ *
+ * mr_ctc2d_char_rows: WHERE an alignment lies vertically.  Given a 1-D alignment the heights of its columns are independent, so the
+ *   most probable height of a column is an arg-max of its own.  targets i32 [N, S] / target_len i32 [N] and pos i32 [N, W], begin /
+ *   end i32 [N, S] as mr_ctc_align took and wrote them for the sum-marginal of the same classify and mask.
+ *   rows i32 [N, W]: for column w with position s = pos[n, w] in 0..2K (K = target_len[n] clamped to [0, S]) and class c = blank
+ *   for even s, targets[n, s / 2] for odd s: the h with the greatest f32-rounded product classify[n, c, h, w] * mask[n, 0, h, w], the
+ *   lowest h among equal values (the product of h = 0 stands until one is greater).  -1 where pos is outside 0..2K (mr_ctc_align
+ *   writes -1 for a row it could not align) or c is no class.
+ *   row_lo, row_hi i32 [N, S]: for symbol i < K with 0 <= begin < end <= W the least and the greatest rows[n, w] over w in
+ *   [begin, end); -1 for every other slot.  All three are written for every row, nothing to be zeroed.
+ *   One wave per row, one launch, no host work that depends on device data: capturable.  Only the class a column's position names
+ *   is read: S + 1 classes of a row, whatever C is.
+ *   N == 0 returns MR_OK without a launch.  MR_ERR_ARG, nothing written: N < 0, C, H or W < 1, S outside
+ *   0..MR_CTC_ALIGN_MAX_SYMBOLS, blank outside [0, C), sizes times strides beyond a 64-bit offset, a null pointer (targets, begin,
+ *   end, row_lo, row_hi may be null when S == 0); MR_ERR_DTYPE: another dtype code. */
+int mr_ctc2d_marginal(int dtype, const void* classify, long long cn, long long cc, long long ch, long long cw,
+                      const void* mask, long long mn, long long mh, long long mw, int N, int C, int H, int W,
+                      int reduce, int log_out, float* out, long long on, long long oc, long long ow, hipStream_t stream);
+int mr_ctc2d_char_rows(int dtype, const void* classify, long long cn, long long cc, long long ch, long long cw,
+                       const void* mask, long long mn, long long mh, long long mw, int N, int C, int H, int W, int blank,
+                       const int* targets, int S, const int* target_len, const int* pos, const int* begin, const int* end,
+                       int* rows, int* row_lo, int* row_hi, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

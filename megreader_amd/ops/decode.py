@@ -148,6 +148,96 @@ def ctc2d_greedy_decode(classify, mask, blank=0, unknown=1):
     return out, lengths
 
 
+def _head2d(classify, mask, who):
+    """What both readers of a 2-D head do first.  classify [N, C, H, W] and mask [N, 1, H, W] on one device, any strides, else the
+    error; the two have one dtype (TypeError); f32 and bf16 are read as they are, other types go through f32 -- after the checks.
+    Returns (classify, mask, (N, C, H, W), the library's dtype code)."""
+    require_cuda(classify, mask)
+    if classify.dim() != 4:
+        raise RuntimeError("%s: classify must be [N, C, H, W], got %s" % (who, tuple(classify.shape)))
+    N, C, H, W = classify.shape
+    if tuple(mask.shape) != (N, 1, H, W):
+        raise RuntimeError("%s: mask must be [N, 1, H, W] = %s, got %s" % (who, (N, 1, H, W), tuple(mask.shape)))
+    if mask.device != classify.device:
+        raise ValueError("%s: classify is on %s, mask on %s" % (who, classify.device, mask.device))
+    if classify.dtype != mask.dtype:
+        raise TypeError("%s: classify is %s, mask %s: one type for both" % (who, classify.dtype, mask.dtype))
+    if classify.dtype not in (torch.float32, torch.bfloat16):
+        classify, mask = classify.float(), mask.float()
+    return classify, mask, (N, C, H, W), _DT[classify.dtype]
+
+
+def ctc2d_marginal(classify, mask, reduce='sum', log=False):
+    """The 1-D CTC posterior of a 2D-CTC head (mr_ctc2d_marginal, include/megreader_hip.h): f32 [N, C, W],
+        q[n, c, w] = sum_h classify[n, c, h, w] * mask[n, 0, h, w]
+    for classify [N, C, H, W] and mask [N, 1, H, W] on the GPU, the head's eval output (any strides; an f32 or a bf16 pair is read
+    as it is, other types go through f32).  The 2D-CTC recursion sums alpha over the heights of the previous column before every
+    step, so its string probabilities are exactly the 1-D CTC probabilities of q: `ctc_beam_search_decode`, `Lexicon.transcribe`
+    and `ctc_forced_align` read q as any other posterior.  Two differences from the training loss `ctc_loss_2d`: it returns inf for
+    an empty target (its recursion does not run), where the 1-D readers give the all-blank probability; and it clamps every
+    product at `tiny` before the log, which the eval tensors are not.  reduce='max' takes the greatest product instead, and
+    `ctc_greedy_decode` of that is the 2-D greedy rule of `ctc2d_greedy_decode` wherever no two products of a column tie.
+    log=True returns the f32 nearest to the log (0 gives -inf): the readers' own lp, for their log_probs=True.
+    The arithmetic is fixed (every product rounded to f32, added or maximised in ascending h), so the bits do not depend on the
+    layout.  The result is contiguous, W fastest: a class's columns side by side, as the readers read the 1-D head's [N, C, 1, T].
+    One launch, capturable."""
+    who = "ctc2d_marginal"
+    if reduce not in ('sum', 'max'):
+        raise ValueError("%s: reduce must be 'sum' or 'max', got %r" % (who, reduce))
+    classify, mask, (N, C, H, W), code = _head2d(classify, mask, who)
+    out = torch.empty((N, C, W), dtype=torch.float32, device=classify.device)
+    cn, cc, ch, cw = classify.stride()
+    mn, _, mh, mw = mask.stride()
+    on, oc, ow = out.stride()
+    with torch.cuda.device(classify.device):
+        call("mr_ctc2d_marginal", code, ptr(classify), cn, cc, ch, cw, ptr(mask), mn, mh, mw, N, C, H, W,
+             int(reduce == 'max'), int(bool(log)), ptr(out), on, oc, ow)
+    return out
+
+
+def ctc2d_char_rows(classify, mask, targets, target_lengths, align, blank=0):
+    """WHERE the symbols of an aligned string lie vertically in a 2D-CTC head (mr_ctc2d_char_rows, include/megreader_hip.h).
+    classify, mask: as for `ctc2d_marginal`; targets i32 [N, S], target_lengths i32 [N] and `align`, the dict
+    `ctc_forced_align(ctc2d_marginal(classify, mask), targets, target_lengths)` returned (its 'pos', 'begin' and 'end' are read).
+    Given the alignment the heights of the columns are independent, so each column's most probable height is its own arg-max.
+    Returns a dict of device tensors: rows i32 [N, W], per column the h with the greatest product classify * mask of the class the
+    alignment gives the column (the blank at even positions, else the symbol; the lowest h among equal products; -1 where 'pos'
+    is); row_lo, row_hi i32 [N, S], the least and the greatest of them over the symbol's columns [begin, end), -1 past the string
+    and for a row that was not aligned.  One launch, no host work that depends on device data (capturable in a graph)."""
+    who = "ctc2d_char_rows"
+    blank = int(blank)
+    classify, mask, (N, C, H, W), code = _head2d(classify, mask, who)
+    if C < 1 or H < 1 or W < 1 or not 0 <= blank < C:
+        raise ValueError("%s: C=%d H=%d W=%d blank=%d: at least one class, height and column, the blank a class"
+                         % (who, C, H, W, blank))
+    if targets.dim() != 2 or targets.shape[0] != N:
+        raise ValueError("%s: targets must be [N=%d, S], got %s" % (who, N, tuple(targets.shape)))
+    S = targets.shape[1]
+    if S > _DEFINES["MR_CTC_ALIGN_MAX_SYMBOLS"]:
+        raise ValueError("%s: S=%d symbols per row, 0..%d are taken" % (who, S, _DEFINES["MR_CTC_ALIGN_MAX_SYMBOLS"]))
+    if tuple(target_lengths.shape) != (N,):
+        raise ValueError("%s: target_lengths must be [N=%d], got %s" % (who, N, tuple(target_lengths.shape)))
+    pos, begin, end = align['pos'], align['begin'], align['end']
+    if tuple(pos.shape) != (N, W) or tuple(begin.shape) != (N, S) or tuple(end.shape) != (N, S):
+        raise ValueError("%s: align must hold pos [N=%d, W=%d] and begin, end [N, S=%d], got %s, %s, %s"
+                         % (who, N, W, S, tuple(pos.shape), tuple(begin.shape), tuple(end.shape)))
+    require_cuda(targets, target_lengths, pos, begin, end)
+    dev = classify.device
+    if any(t.device != dev for t in (targets, target_lengths, pos, begin, end)):
+        raise ValueError("%s: classify is on %s, targets, target_lengths and align on %s"
+                         % (who, dev, ", ".join(str(t.device) for t in (targets, target_lengths, pos, begin, end))))
+    targets, target_lengths, pos, begin, end = (t.to(torch.int32).contiguous() for t in (targets, target_lengths, pos, begin, end))
+    out = {'rows': torch.empty((N, W), dtype=torch.int32, device=dev),
+           'row_lo': torch.empty((N, S), dtype=torch.int32, device=dev),
+           'row_hi': torch.empty((N, S), dtype=torch.int32, device=dev)}
+    cn, cc, ch, cw = classify.stride()
+    mn, _, mh, mw = mask.stride()
+    with torch.cuda.device(dev):
+        call("mr_ctc2d_char_rows", code, ptr(classify), cn, cc, ch, cw, ptr(mask), mn, mh, mw, N, C, H, W, blank, ptr(targets), S,
+             ptr(target_lengths), ptr(pos), ptr(begin), ptr(end), ptr(out['rows']), ptr(out['row_lo']), ptr(out['row_hi']))
+    return out
+
+
 def sequence_measure(labels, preds, blank=0, unknown=1, fold=None):
     """labels i32 [N, S], preds i32 [N, S2] (device).  Returns dict of device tensors:
     accuracy (bool [N]), edit_distance (f64 [N], the reference's normalised score), distance (i32 [N], the Levenshtein

@@ -21,7 +21,14 @@ models:
   3. `QuadCropper.crop` samples the recognition batch out of the photos still resident in the pipeline's device buffer;
   4. `recognizer` in chunks of `max_crops`, greedy decoding (or prefix beam search), `charset.label_to_string`.
 Only the boxes (a few hundred points) and the decoded ids (with the beam: ids, lengths and scores; with `chars=True` the first and
-last column and the summed log-probability of every character) cross to the host."""
+last column and the summed log-probability of every character) cross to the host.
+
+A recogniser whose eval output is the pair (classify [M, C, H, W], mask [M, 1, H, W]) with H > 1 is a 2D-CTC head
+(decoders/ctc_decoder2d.py).  Its posterior is `ctc2d_marginal(classify, mask)`, computed once per chunk: the string probabilities
+of the 2-D head are the 1-D CTC probabilities of that marginal, so the beam, the lexicon and the alignment read it unchanged.
+`decode='ctc'` is `ctc2d_greedy_decode`, the rule `CTCRepresenter2D` scores.  With `chars=True` `ctc2d_char_rows` also gives every
+character the band of heights it lies on, and its quad spans that band instead of the whole height of the crop (per chunk the
+lowest and the highest height of every character cross to the host as well)."""
 import math
 
 import numpy as np
@@ -29,7 +36,8 @@ import torch
 
 from .data.device_pipeline import DevicePipeline
 from .data.quad_crop import QuadCropper
-from .ops.decode import ctc_beam_search_decode, ctc_forced_align, ctc_greedy_decode
+from .ops.decode import (ctc2d_char_rows, ctc2d_greedy_decode, ctc2d_marginal, ctc_beam_search_decode, ctc_forced_align,
+                         ctc_greedy_decode)
 from .ops.lexicon import Lexicon
 from ._lib import _DEFINES
 from .structure.seg_detector_representer import SegDetectorRepresenter
@@ -39,7 +47,7 @@ class TextReader(object):
     def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
                  rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
                  lexicon_max_distance=None, lexicon_rule='nearest', beam_width=8, nbest=1, beam_top_classes=16, chars=False,
-                 column_geometry=None):
+                 column_geometry=None, row_geometry=None):
         if lexicon_rule not in ('nearest', 'likelihood'):
             raise ValueError("lexicon_rule must be 'nearest' or 'likelihood', got %r" % (lexicon_rule,))
         if lexicon_rule == 'likelihood' and decode != 'ctc':
@@ -58,6 +66,11 @@ class TextReader(object):
             if not (stride > 0.0 and math.isfinite(stride) and math.isfinite(offset)):
                 raise ValueError("column_geometry must be (stride > 0, offset) in canvas pixels, got %r" % (column_geometry,))
             column_geometry = (stride, offset)
+        if row_geometry is not None:
+            stride, offset = (float(v) for v in row_geometry)
+            if not (stride > 0.0 and math.isfinite(stride) and math.isfinite(offset)):
+                raise ValueError("row_geometry must be (stride > 0, offset) in canvas pixels, got %r" % (row_geometry,))
+            row_geometry = (stride, offset)
         self.detector = detector
         self.recognizer = recognizer
         self.charset = charset
@@ -69,6 +82,7 @@ class TextReader(object):
         self.scores = bool(scores)
         self.chars = bool(chars)
         self.column_geometry = column_geometry
+        self.row_geometry = row_geometry
         if lexicon is not None and not isinstance(lexicon, Lexicon):
             lexicon = Lexicon(lexicon, charset)
         self.lexicon = lexicon
@@ -83,15 +97,27 @@ class TextReader(object):
         batch = self.det_pipeline.upload(staged, layout)
         return batch, self.det_pipeline.photos(batch, layout)
 
-    def _decode(self, pred, post):
-        """The decode step of one chunk (pred: the recogniser's output, post: its CTC posterior): (ids [M, S] and lengths [M] or
-        None, on the device; None or, with decode='beam', per crop the dict of the keys the beam adds to an item)."""
+    @staticmethod
+    def _head2d(pred):
+        """(classify [M, C, H, W], mask [M, 1, H, W]) when `pred` is the eval output of a 2D-CTC head -- a pair whose first member
+        has four dimensions and more than one height -- else None."""
+        if isinstance(pred, (tuple, list)) and len(pred) == 2 and torch.is_tensor(pred[0]) and torch.is_tensor(pred[1]) \
+                and pred[0].dim() == 4 and pred[0].shape[2] > 1:
+            return pred[0], pred[1]
+        return None
+
+    def _decode(self, pred, post, head2d=None):
+        """The decode step of one chunk (pred: the recogniser's output, post: its CTC posterior, head2d: `_head2d(pred)`): (ids
+        [M, S] and lengths [M] or None, on the device; None or, with decode='beam', per crop the dict of the keys the beam adds
+        to an item).  The greedy string of a 2-D head is `ctc2d_greedy_decode`'s, the rule `CTCRepresenter2D` scores."""
         if self.decode == 'beam':
             return self._beam(post)
         if callable(self.decode):
             return tuple(self.decode(pred)) + (None,)
         if self.decode == 'ids':
             return pred, None, None
+        if head2d is not None:
+            return ctc2d_greedy_decode(head2d[0], head2d[1], blank=self.blank, unknown=self.unknown) + (None,)
         return ctc_greedy_decode(post, blank=self.blank, unknown=self.unknown) + (None,)
 
     @staticmethod
@@ -121,12 +147,15 @@ class TextReader(object):
                                          for j in range(k)]
         return out['ids'][:, 0], out['lengths'][:, 0], extras
 
-    def _align(self, pred, ids, lengths, found):
-        """One chunk's FINAL strings aligned to its posterior (`ctc_forced_align`): (begin, end, sym_lp) as numpy [M, S] and the
-        number of columns T.  The final ids are the decoded ones (greedy, or the beam's first hypothesis), or `Lexicon.ids` of the
+    def _align(self, pred, ids, lengths, found, head2d=None):
+        """One chunk's FINAL strings aligned to its posterior (`ctc_forced_align`): (begin, end, sym_lp) as numpy [M, S], the
+        number of columns T and None or, for a 2-D head, (row_lo, row_hi as numpy [M, S], the number of heights H).  The final
+        ids are the decoded ones (greedy, or the beam's first hypothesis), or `Lexicon.ids` of the
         word where one was taken; a lexicon word is aligned to the posterior over the folded alphabet (`Lexicon._folded`), the
         rows that kept their raw string to the posterior as it is: two calls per chunk at most, each with length -1 (unalignable,
-        no work) for the other call's rows.  Only the three arrays cross to the host."""
+        no work) for the other call's rows.  Each alignment of a 2-D head (pred: its sum-marginal, head2d: classify and mask)
+        goes on through `ctc2d_char_rows`, a lexicon word's over classify folded as the posterior was.  Only the arrays returned
+        cross to the host."""
         if pred.dim() == 4:
             pred = pred.select(2, 0)
         dev = pred.device
@@ -143,23 +172,36 @@ class TextReader(object):
             targets = torch.where(took[:, None], words, targets)
             lens = torch.where(took, word_lens, lens)
             fold = self.lexicon._tensors(dev)[2]
+
+        def align(post, heads, lens):
+            out = ctc_forced_align(post, targets, lens, blank=self.blank, unknown=self.unknown)
+            if heads is not None:
+                out.update(ctc2d_char_rows(heads[0], heads[1], targets, lens, out, blank=self.blank))
+            return out
+
+        keys = ('begin', 'end', 'sym_lp') + (('row_lo', 'row_hi') if head2d is not None else ())
         if fold is None:                                        # one posterior for every row
-            out = ctc_forced_align(pred, targets, lens, blank=self.blank, unknown=self.unknown)
+            out = align(pred, head2d, lens)
         else:
             none = torch.full_like(lens, -1)
-            raw = ctc_forced_align(pred, targets, torch.where(took, none, lens), blank=self.blank, unknown=self.unknown)
-            folded = ctc_forced_align(self.lexicon._folded(pred, fold, False), targets, torch.where(took, lens, none),
-                                      blank=self.blank, unknown=self.unknown)
-            out = {k: torch.where(took[:, None], folded[k], raw[k]) for k in ('begin', 'end', 'sym_lp')}
-        return out['begin'].cpu().numpy(), out['end'].cpu().numpy(), out['sym_lp'].cpu().numpy(), int(pred.shape[2])
+            raw = align(pred, head2d, torch.where(took, none, lens))
+            heads = None if head2d is None else (self.lexicon._folded(head2d[0], fold, False), head2d[1].float())
+            folded = align(self.lexicon._folded(pred, fold, False), heads, torch.where(took, lens, none))
+            out = {k: torch.where(took[:, None], folded[k], raw[k]) for k in keys}
+        begin, end, sym_lp = (out[k].cpu().numpy() for k in keys[:3])
+        bands = None if head2d is None else (out['row_lo'].cpu().numpy(), out['row_hi'].cpu().numpy(), int(head2d[0].shape[2]))
+        return begin, end, sym_lp, int(pred.shape[2]), bands
 
-    def _spans(self, symbols, begin, end, sym_lp, T):
-        """What `read` makes one crop's 'chars' of: [(character, first column, one past the last, summed log-probability)] and T,
-        or None when the string could not be aligned (the slots of its symbols are then empty)."""
+    def _spans(self, symbols, begin, end, sym_lp, T, bands=None):
+        """What `read` makes one crop's 'chars' of: [(character, first column, one past the last, summed log-probability, lowest
+        height, highest height)], T and H, or None when the string could not be aligned (the slots of its symbols are then
+        empty).  `bands`: this crop's row_lo, row_hi and H for a 2-D head; None gives None for the heights and for H."""
         n = int((begin >= 0).sum())
         if n != len(symbols):
             return None
-        return [(ch, int(begin[k]), int(end[k]), float(sym_lp[k])) for k, ch in enumerate(symbols)], T
+        lo, hi, H = bands if bands is not None else (None, None, None)
+        return [(ch, int(begin[k]), int(end[k]), float(sym_lp[k])) + ((None, None) if H is None else (int(lo[k]), int(hi[k])))
+                for k, ch in enumerate(symbols)], T, H
 
     def recognize(self, crops):
         """crops: f32 [M, 3, H, W] on the device -> M strings (with a lexicon: the nearest words, see `read`)."""
@@ -203,10 +245,11 @@ class TextReader(object):
                 for rec, score in zip(records, found['score'].cpu().tolist()):
                     rec['lexicon_score'] = score
         if aligned is not None:
-            begin, end, sym_lp, T = aligned
+            begin, end, sym_lp, T, bands = aligned
             for m, (rec, row, k) in enumerate(zip(records, ids, lengths)):
                 own = [self.charset.label_to_string(row[j:j + 1]) for j in range(int(k))]      # the raw string: its own ids
-                rec['spans'] = self._spans(list(rec['text']) if rec['word'] else own, begin[m], end[m], sym_lp[m], T)
+                rec['spans'] = self._spans(list(rec['text']) if rec['word'] else own, begin[m], end[m], sym_lp[m], T,
+                                           None if bands is None else (bands[0][m], bands[1][m], bands[2]))
         return records
 
     def _recognize(self, crops):
@@ -216,30 +259,41 @@ class TextReader(object):
           'lexicon_score'     with the likelihood rule: log p(word | posterior);
           'extras'            with decode='beam': the dict of the keys the beam adds to an item;
           'spans'             with chars=True: what `_spans` returns for the final text (None: it could not be aligned).
-        Per chunk of `max_crops`: decode, lexicon and align on the device, then one step that copies to the host."""
+        Per chunk of `max_crops`: (the marginal of a 2-D head,) decode, lexicon and align on the device, then one step that copies
+        to the host."""
         records = []
         for lo in range(0, crops.shape[0], self.max_crops):
             pred = self._eval(self.recognizer, crops[lo:lo + self.max_crops])
-            post = pred[0] if isinstance(pred, (tuple, list)) else pred     # (of a CTC recogniser)
-            ids, lengths, extras = self._decode(pred, post)
+            head2d = self._head2d(pred)
+            if head2d is not None:                                          # (of a 2D-CTC recogniser: once per chunk)
+                post = ctc2d_marginal(head2d[0], head2d[1])
+            else:
+                post = pred[0] if isinstance(pred, (tuple, list)) else pred     # (of a CTC recogniser)
+            ids, lengths, extras = self._decode(pred, post, head2d)
             found = self._lexicon(post, ids, lengths)
-            aligned = self._align(post, ids, lengths, found) if self.chars else None
+            aligned = self._align(post, ids, lengths, found, head2d) if self.chars else None
             records.extend(self._to_host(ids, lengths, extras, found, aligned))
         return records
 
     def _chars(self, plan, spans):
-        """One item's 'chars' from its crop's plan and aligned spans: the canvas rectangle of each character's columns, clamped to
-        the valid canvas, carried to the photo by `CropPlan.canvas_to_photo`."""
+        """One item's 'chars' from its crop's plan and aligned spans: the canvas rectangle of each character's columns (of a 2-D
+        head: and of its band of heights), clamped to the valid canvas, carried to the photo by `CropPlan.canvas_to_photo`."""
         if spans is None:
             return None
-        spans, T = spans
+        spans, T, rows = spans
         H, W = plan.canvas
         stride, offset = self.column_geometry if self.column_geometry is not None else (float(W) / T, 0.0)
+        if rows is not None:                                                   # a 2-D head: the band of heights too
+            row_stride, row_offset = self.row_geometry if self.row_geometry is not None else (float(H) / rows, 0.0)
         chars = []
-        for ch, begin, end, lp in spans:
+        for ch, begin, end, lp, lo, hi in spans:
             u0 = min(max(offset + begin * stride, 0.0), float(plan.dst_w))
             u1 = min(max(offset + end * stride, 0.0), float(plan.dst_w))
-            quad = plan.canvas_to_photo([[u0, 0.0], [u1, 0.0], [u1, float(H)], [u0, float(H)]])
+            v0, v1 = 0.0, float(H)
+            if rows is not None:
+                v0 = min(max(row_offset + lo * row_stride, 0.0), float(H))
+                v1 = min(max(row_offset + (hi + 1) * row_stride, 0.0), float(H))
+            quad = plan.canvas_to_photo([[u0, v0], [u1, v0], [u1, v1], [u0, v1]])
             chars.append({'char': ch, 'quad': quad.tolist(), 'score': math.exp(lp / (end - begin))})
         return chars
 
@@ -268,7 +322,14 @@ class TextReader(object):
         vertical crop gives boxes stacked along the photo's vertical axis.  `column_geometry` is (stride, offset) in canvas pixels;
         None means (W / T, 0): the posterior's columns partition the canvas evenly.  A model whose columns are not spread evenly
         (the CRNN's 33 columns over 128 pixels) should pass its own.  A text that cannot be aligned (a lexicon word of more
-        symbols than columns, or one reachable only through zero probabilities) gets 'chars': None."""
+        symbols than columns, or one reachable only through zero probabilities) gets 'chars': None.  A 2D-CTC recogniser (eval
+        output (classify [M, C, H, W], mask [M, 1, H, W]), H > 1) is read through `ctc2d_marginal(classify, mask)`, the 1-D
+        posterior with the 2-D head's string probabilities: every mode above works on it as on a 1-D head's, `decode='ctc'` being
+        `ctc2d_greedy_decode`.  With `chars=True` a character's quad is then the canvas rectangle of its columns and of the rows
+        V in [row_offset + row_lo * row_stride, row_offset + (row_hi + 1) * row_stride], clamped to the canvas, row_lo and row_hi
+        the lowest and highest of the most probable heights of its columns (`ctc2d_char_rows`; a lexicon word's over the folded
+        alphabet); `row_geometry` is (row_stride, row_offset) in canvas pixels, None means (H_canvas / H, 0).  'score' stays
+        exp(sym_lp / (end - begin)) on the marginal."""
         images = list(images)
         results = [[] for _ in images]
         if not images:
