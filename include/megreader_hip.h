@@ -1154,6 +1154,78 @@ int mr_ctc2d_char_rows(int dtype, const void* classify, long long cn, long long 
                        const int* targets, int S, const int* target_len, const int* pos, const int* begin, const int* end,
                        int* rows, int* row_lo, int* row_hi, hipStream_t stream);
 
+/* ---- Reading with the attention decoder (csrc/attn_read.hip, csrc/attn_beam.hip): the probability of the decoded string and of
+ * every character, where each character lies on the feature grid, and the n best strings by beam search.  The decode loop
+ * (mr_decode_greedy_fwd, or the per-step kernels) leaves its words and its hidden states H_all [S+1][N][H] behind; given those,
+ * the attention map of step s depends on H_all[s] alone and its output distribution on H_all[s + 1] alone, so both are computed
+ * for all S steps in parallel BEHIND the loop ("replay read") and the loop itself is not touched.
+ *
+ * mr_attn_read.  Operands MR_DTYPE_F32 or MR_DTYPE_BF16 (hproj, eproj, logits; converted to f32 on load), v f32 [H]:
+ *     hproj   row (s, n) at hproj + (s * N + n) * ldh, H values: the attention half of the hidden projection of H_all[s], s < S
+ *     eproj   [N][T][H] contiguous: the encoder half (with the bias)
+ *     logits  row (s, n) at logits + (s * N + n) * ldl, C values: the output layer of H_all[s + 1]
+ *     words   int32, words[n * ldp + s]: the word emitted at step s (the greedy kernel's pred, or a beam hypothesis)
+ *     the grid height x width = T positions, t = y * width + x;  1 <= T <= MR_ATTN_READ_MAX_T;  blank in [0, C).
+ *   For every (s, n):
+ *     att[n][s][t] (f32 [N][S][T], nullable) = softmax_t(e_t), e_t = sum_h v[h] * tanh(hproj[s][n][h] + eproj[n][t][h]) -- the map
+ *       step s of the loop computes from the previous state; tanh in the exp2 / rcp form of the attention kernels (absolute error
+ *       ~2e-7); e_t added per lane in ascending h (h = 8 lane + q + 512 k for bf16, 4 lane + q + 256 k for f32; lane + 64 k when H
+ *       is no multiple of the 16-byte vector) and then over the 64 lanes by the xor tree 32, 16, .., 1; the softmax as
+ *       exp(e - max) / sum with the sums of a row taken per lane in ascending t = lane + 64 k and then by the same tree.
+ *     moments[n][s][0..3] (f32) = cx, cy, sx, sy: the mean and the standard deviation of (x + 0.5, y + 0.5) under att, in grid
+ *       cells; the variance as sum_t att * (x + 0.5 - cx)^2, same order of summation.
+ *     sym_lp[n][s] (f32) = log_softmax(logits[s][n])[words[n][s]] = (l_w - max) - log(sum_c exp(l_c - max)), the sum per lane in
+ *       ascending c = lane + 64 k, then the tree.  A word outside [0, C) (the -1 of a timed-out row) gives -inf.
+ *   A second launch, per row n:
+ *     length[n] (i32) = the index of the first `blank` in words[n][0..S), or S when there is none;
+ *     score[n] (f32) = sym_lp[n][0] + sym_lp[n][1] + .. + sym_lp[n][min(length, S - 1)] added in that order: the log-probability
+ *       of the string, its terminating blank included when it has one.
+ *   A workgroup owns one image and up to 8 consecutive steps and reads eproj[n] once for all of them.  Two launches on `stream`,
+ *   no allocation, no synchronisation, no host work that depends on device data: capturable in a graph.  Every output is written
+ *   for every row; nothing has to be zeroed.  N == 0 returns MR_OK without a launch.  MR_ERR_ARG, nothing launched: S, H or C < 1,
+ *   T outside 1..MR_ATTN_READ_MAX_T, height * width != T, blank outside [0, C), ldh < H, ldl < C, ldp < S, (2 H + T) * 4 bytes
+ *   above 64 KiB, more than INT_MAX workgroups, a null pointer (only att may be null); MR_ERR_DTYPE: another dtype code.
+ *
+ * mr_attn_beam_step: the selection of ONE decode step s of a beam search; the B hypotheses of image n are the rows n * B + b of
+ *   the per-step kernels, 1 <= B <= MR_ATTN_BEAM_MAX.  logits: row n * B + b at logits + (n * B + b) * ldl, C values, the output
+ *   layer of the new states hprime [N * B][H].  State, read and then rewritten in place (one workgroup per image): score f32
+ *   [N * B], finished i32 [N * B], length i32 [N * B].  At s == 0 the state is NOT read: slot 0 of every image is live with score 0
+ *   (h0 = 0, fed `blank`), every other slot is dead.
+ *     Candidates.  A live, unfinished hypothesis b offers (b, c) for every class c with the value
+ *       score[b] + ((logit[b][c] - m_b) - log sum_c' exp(logit[b][c'] - m_b)),  m_b = max_c logit[b][c],
+ *     all f32, the sum per lane in ascending c = lane + 64 k and then by the xor tree 32, .., 1.  A finished hypothesis offers only
+ *     (b, blank) with score[b] unchanged.  A dead slot (score -inf), and a value that is -inf or NaN, offers nothing.
+ *     Selection.  The B candidates with the greatest value, in descending order; between equal values (-0 = +0) the smaller
+ *     b * C + c comes first.  No length normalisation.  Fewer than B candidates leave dead slots at the end.
+ *     Outputs for the new slot j: parent[(s * N + n) * B + j] = b and word[(s * N + n) * B + j] = c (i32 [S][N][B]); score = the
+ *     candidate's value; finished = 1 when b was finished or c == blank; length = length[b] when b was finished, else s when
+ *     c == blank (the string ended BEFORE this step's blank), else s + 1; feed[n * B + j] = c as int64, the `idx` of mr_gru_fwd2 for
+ *     the next step; h_next[n * B + j][0..H) = hprime[n * B + b][0..H) (h_next must not be hprime).  A dead slot: parent 0, word
+ *     blank, score -inf, finished 0, length 0.
+ *   One launch, no host work that depends on device data: the S steps of a search can be enqueued, and captured, as a whole.
+ *   N == 0 returns MR_OK without a launch.  MR_ERR_ARG, nothing launched: s outside [0, S), B out of range, C < 1 or above
+ *   INT_MAX / 64, ldl < C, blank outside [0, C), H < 1, a null pointer, h_next == hprime; MR_ERR_DTYPE: another dtype code.
+ *
+ * mr_attn_beam_trace: after step S - 1 the slots of an image are its hypotheses in descending order of score.  For n and
+ *   j < nbest <= B, following parent back from slot j: ids[n][j][s] = the word of step s (i32 [N][nbest][S]; blank from the end of
+ *   a finished string on), lengths[n][j] = the length (S for a hypothesis that never emitted blank), scores[n][j] its score,
+ *   path[n][j][s] (i32 [N][nbest][S + 1]) = the slot -- the row of the per-step kernels -- the hypothesis occupied ENTERING step s
+ *   (path[.][0] = 0, path[.][S] = j): with H_steps [S + 1][N * B][H] holding every step's hprime at [s + 1], its hidden state after
+ *   step s is H_steps[s + 1][n * B + path[n][j][s]].  count[n] = the live hypotheses among the nbest; a dead one gets all blank,
+ *   length 0, score -inf, path 0.  One launch, capturable.  MR_ERR_ARG: S < 1, B or nbest out of range, N * nbest * (S + 1) above
+ *   INT_MAX, a null pointer. */
+#define MR_ATTN_READ_MAX_T 4096     /* positions of the feature grid */
+#define MR_ATTN_BEAM_MAX 64         /* hypotheses per image */
+int mr_attn_read(int dtype, const void* hproj, long long ldh, const void* eproj, const float* v, const void* logits,
+                 long long ldl, const int* words, long long ldp, int blank, int N, int S, int T, int H, int C, int height,
+                 int width, float* att, float* sym_lp, float* moments, int* length, float* score, hipStream_t stream);
+int mr_attn_beam_step(int dtype, const void* logits, long long ldl, const void* hprime, void* h_next, int H, float* score,
+                      int* finished, int* length, int* parent, int* word, long long* feed, int s, int S, int N, int B, int C,
+                      int blank, hipStream_t stream);
+int mr_attn_beam_trace(const int* parent, const int* word, const float* score, const int* finished, const int* length, int S,
+                       int N, int B, int nbest, int blank, int* ids, int* lengths, float* scores, int* count, int* path,
+                       hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

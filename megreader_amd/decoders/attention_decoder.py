@@ -78,13 +78,14 @@ def _trim_pred(pred, blank):
     return pred
 
 
-def _greedy_decode(enc, eproj, v, cat, ic, G, out, blank, max_size, trim=True):
+def _greedy_decode(enc, eproj, v, cat, ic, G, out, blank, max_size, trim=True, states=False):
     """Greedy decoding of enc [N, T, Ep] / eproj [N, T, H] (bf16) as persistent launches: int32 [N, max_size].  cat / ic / out are
     the `_SeqLinear` stacks of the training loop ([W_attn[:, :H]; W_hh], W_ih's context columns, the output layer), G the word table
     [C, >= 3H].  Batches beyond 64 rows go as consecutive launches of at most 64 rows on the current stream, then ONE trim over
     the whole batch.  Every launch zeroes its own exchange workspace (a memset node under capture; never the ZeroArena, which only
     the fused optimizers' zero_grad() re-zeroes) and its status word joins nn.functional.LSTM_STATUS.  Nothing here waits for
-    the device."""
+    the device.  states=True also returns the hidden states H_all [max_size + 1, N, H] the kernel stored ([0] = the zero start
+    state): (pred, H_all)."""
     from ..nn import functional as F_
     N, T, Ep = enc.shape
     Hd = eproj.shape[2]
@@ -99,13 +100,106 @@ def _greedy_decode(enc, eproj, v, cat, ic, G, out, blank, max_size, trim=True):
     vf = v.detach().float().contiguous()
     pred = torch.empty((N, max_size), dtype=torch.int32, device=dev)
     h0 = torch.zeros((min(N, GREEDY_ROWS), Hd), dtype=dtype, device=dev)
+    kept = []
     for r0 in range(0, N, GREEDY_ROWS):
         n = min(GREEDY_ROWS, N - r0)
         ws, nbytes = F_.persistent_workspace(load().mr_decode_persist_ws_bytes(n), dev, arena=False)
+        if states:
+            kept.append(torch.empty((max_size + 1, n, Hd), dtype=dtype, device=dev))
         call("mr_decode_greedy_fwd", ptr(cat.w_n), ptr(cat.bias_d), ptr(ic.w_n), Ep, ptr(G), G.shape[1], ptr(out.w_n),
-             ptr(out.bias_d), C, ptr(eproj[r0]), ptr(enc[r0]), ptr(vf), ptr(h0), int(blank), ptr(pred[r0]), max_size, 0, ptr(ws),
-             nbytes, max_size, n, T, Ep)
-    return _trim_pred(pred, blank) if trim else pred
+             ptr(out.bias_d), C, ptr(eproj[r0]), ptr(enc[r0]), ptr(vf), ptr(h0), int(blank), ptr(pred[r0]), max_size,
+             ptr(kept[-1]) if states else 0, ptr(ws), nbytes, max_size, n, T, Ep)
+    pred = _trim_pred(pred, blank) if trim else pred
+    if states:
+        return pred, (kept[0] if len(kept) == 1 else torch.cat(kept, 1))
+    return pred
+
+
+BEAM_IMAGES = 64            # images of one chunk of the beam search (their beam x 64 hypotheses are the rows of its step kernels)
+
+
+def _beam_decode(enc, eproj, v, cat, ic, G, out, blank, max_size, beam=1, nbest=1):
+    """Beam search over enc [N, T, Ep] / eproj [N, T, H] (f32 or bf16; T <= 64, what mr_attn_fwd2 takes) with the per-step kernels
+    of the training loop: the `beam` hypotheses of image n are the rows n * beam + b of mr_gemm_nt / mr_attn_fwd2 / mr_gru_fwd2,
+    and one mr_attn_beam_step per step selects the survivors, writes the words they are fed next and gathers their states (6
+    launches a step).  beam = 1 is greedy decoding -- the first of equal logits, as the greedy kernels -- that keeps its states.
+    cat / ic / out / G as for `_greedy_decode`.  Returns the dict of `attention_beam_trace` (ids [N, nbest, S], lengths, scores,
+    count, path) with 'states': H_all [S + 1, N, H] of every image's FIRST hypothesis ([0] = the zero start state), what
+    `_replay_read` reads.  All S steps are enqueued without looking at the device: capturable.
+    Memory: enc and eproj are expanded `beam` times (repeat_interleave) once per chunk of at most 64 images, and every step's
+    states are kept: 64 * beam * (T * (Ep + H) + (S + 1) * H) elements -- at beam = 64, T = 32, Ep = 552, H = 512, S = 32 in bf16
+    that is 145 + 134 + 138 = 417 MB per chunk, at beam = 8 an eighth of it."""
+    from ..ops.decode import attention_beam_step, attention_beam_trace
+    N, T, Ep = enc.shape
+    Hd = eproj.shape[2]
+    C, S, B = out.nout, int(max_size), int(beam)
+    dtype, dev = enc.dtype, enc.device
+    dt = dtype_code(dtype)
+    es = 2 if dtype == torch.bfloat16 else 4
+    H3, HC = 3 * Hd, 4 * Hd
+    if T > 64:
+        raise RuntimeError("the per-step attention kernel takes T <= 64 positions, got %d" % T)
+    assert cat.np_ == HC and ic.np_ == H3 and ic.kp == Ep and out.kp == Hd and cat.kp == Hd
+    assert G.dtype == dtype and G.is_contiguous() and G.shape[0] >= C and G.shape[1] >= H3
+    assert enc.is_contiguous() and eproj.is_contiguous() and eproj.dtype == dtype and eproj.shape[:2] == (N, T)
+    vf = v.detach().float().contiguous()
+    ldG = G.shape[1]
+    parts = []
+    for r0 in range(0, N, BEAM_IMAGES):
+        n = min(BEAM_IMAGES, N - r0)
+        R = n * B
+        enc_x, eproj_x = enc[r0:r0 + n], eproj[r0:r0 + n]
+        if B > 1:
+            enc_x, eproj_x = enc_x.repeat_interleave(B, 0), eproj_x.repeat_interleave(B, 0)
+        H_steps = torch.empty((S + 1, R, Hd), dtype=dtype, device=dev)
+        H_steps[0].zero_()
+        h = torch.zeros((R, Hd), dtype=dtype, device=dev)
+        hc = torch.empty((R, HC), dtype=dtype, device=dev)
+        w_att = torch.empty((R, T), dtype=torch.float32, device=dev)
+        ctx = torch.empty((R, Ep), dtype=dtype, device=dev)
+        gic = torch.empty((R, H3), dtype=dtype, device=dev)
+        save = torch.empty((R, H3), dtype=torch.float32, device=dev)
+        logits = torch.empty((R, out.np_), dtype=dtype, device=dev)                 # (pad columns are never read)
+        score = torch.empty((n, B), dtype=torch.float32, device=dev)                # (step 0 does not read the state)
+        finished = torch.empty((n, B), dtype=torch.int32, device=dev)
+        length = torch.empty((n, B), dtype=torch.int32, device=dev)
+        parent = torch.empty((S, n, B), dtype=torch.int32, device=dev)
+        word = torch.empty((S, n, B), dtype=torch.int32, device=dev)
+        feed = torch.full((n, B), int(blank), dtype=torch.int64, device=dev)
+        for s in range(S):
+            call("mr_gemm_nt", dt, ptr(h), Hd, ptr(cat.w_n), Hd, ptr(hc), HC, ptr(cat.bias_d), 0, R, HC, Hd)
+            call("mr_attn_fwd2", dt, ptr(hc), HC, ptr(eproj_x), ptr(vf), ptr(enc_x), ptr(w_att), ptr(ctx), R, T, Hd, Ep)
+            call("mr_gemm_nt", dt, ptr(ctx), Ep, ptr(ic.w_n), Ep, ptr(gic), H3, 0, 0, R, H3, Ep)
+            call("mr_gru_fwd2", dt, ptr(G), ldG, ptr(feed), ptr(gic), ptr(hc) + Hd * es, HC, ptr(h), ptr(H_steps[s + 1]), ptr(save),
+                 R, Hd)
+            call("mr_gemm_nt", dt, ptr(H_steps[s + 1]), Hd, ptr(out.w_n), Hd, ptr(logits), out.np_, ptr(out.bias_d), 0, R, C, Hd)
+            attention_beam_step(logits, H_steps[s + 1], h, score, finished, length, parent, word, feed, s, blank, classes=C)
+        tr = attention_beam_trace(parent, word, score, finished, length, nbest, blank)
+        # the first hypothesis' state after step s sits in the row it occupied entering step s
+        rows = torch.arange(n, device=dev)[:, None] * B + tr['path'][:, 0, :S].long()            # [n, S]
+        first = torch.gather(H_steps[1:], 1, rows.t()[:, :, None].expand(S, n, Hd))
+        tr['states'] = torch.cat((H_steps[:1, :n], first), 0)                       # ([0] is zero in every row)
+        parts.append(tr)
+    if len(parts) == 1:
+        return parts[0]
+    return {k: torch.cat([p[k] for p in parts], 1 if k == 'states' else 0) for k in parts[0]}
+
+
+def _replay_read(H_all, words, eproj, v, cat, out, blank, height, width, attention=False):
+    """Scores and attention maps of a decoded batch from its hidden states (`attention_read`): H_all [S + 1, N, H] as the greedy
+    kernel or `_beam_decode` left it, words int32 [N, S].  The attention half of the hidden projection of H_all[0..S-1] and the
+    output layer of H_all[1..S] are one mr_gemm_nt each over all S * N rows."""
+    from ..ops.decode import attention_read
+    S, N, Hd = H_all.shape[0] - 1, H_all.shape[1], H_all.shape[2]
+    dtype, dev = H_all.dtype, H_all.device
+    dt = dtype_code(dtype)
+    assert H_all.is_contiguous() and cat.kp == Hd and out.kp == Hd and cat.nout >= Hd
+    hproj = torch.empty((S, N, Hd), dtype=dtype, device=dev)
+    # (rows 0..H-1 of the stacked projection are W_attn[:, :H]; their bias block is zero)
+    call("mr_gemm_nt", dt, ptr(H_all), Hd, ptr(cat.w_n), Hd, ptr(hproj), Hd, 0, 0, S * N, Hd, Hd)
+    logits = torch.empty((S, N, out.np_), dtype=dtype, device=dev)
+    call("mr_gemm_nt", dt, ptr(H_all[1]), Hd, ptr(out.w_n), Hd, ptr(logits), out.np_, ptr(out.bias_d), 0, S * N, out.nout, Hd)
+    return attention_read(hproj, eproj, v, logits[:, :, :out.nout], words, blank, height, width, attention=attention)
 
 
 def _ceil_to(x, m):
@@ -629,23 +723,93 @@ class AttentionDecoder(nn.Module):
             parts.append(torch.zeros((N, T, Ep - E), dtype=dtype, device=dev))
         return torch.cat(parts, dim=2).contiguous(), E, dtype
 
-    def forward(self, feature, targets=None, lengths=None, train=False):
+    def _encoded(self, feature):
+        """What every forward starts with: (enc [N, T, Ep], E, dtype, eproj [N, T, H] = the encoder half of the attention
+        projection with its bias, and the two `_SeqLinear` of the word path, W_ih[:, :H] and word_linear)."""
         if not feature.is_cuda:
             raise NotImplementedError("megreader_amd decoders run on the GPU only")
         enc, E, dtype = self._sequence(feature)
         N, T, Ep = enc.shape
         Hd = self.inner_channels
         cell = self.decoder
-        C = len(self.charset)
-        dev = enc.device
         Wa = cell.attn.attn.weight
         lin_e = _SeqLinear(Wa[:, Hd:Hd + E], cell.attn.attn.bias, Ep, dtype)
         lin_iw = _SeqLinear(cell.rnn.weight_ih[:, :Hd], cell.rnn.bias_ih, Hd, dtype)
-        Cp = _ceil_to(C, vec_of(dtype))
+        Cp = _ceil_to(len(self.charset), vec_of(dtype))
         lin_word = _SeqLinear(cell.word_linear.weight, cell.word_linear.bias, Cp, dtype)
         eproj = lin_e(enc.view(N * T, Ep))[:, :Hd].reshape(N, T, Hd)
         if not eproj.is_contiguous():
             eproj = eproj.contiguous()
+        return enc, E, dtype, eproj, lin_iw, lin_word
+
+    def _loop_operands(self, lin_iw, lin_word, E, Ep, dtype, dev):
+        """The operands of the decode loop that do not depend on the image (call under no_grad): the word table G [C, 3H] of the
+        training branch and the `_SeqLinear` stacks cat = [W_attn[:, :H]; W_hh], ic = W_ih's context columns, out."""
+        cell = self.decoder
+        Hd, C = self.inner_channels, len(self.charset)
+        Wa = cell.attn.attn.weight
+        rows = _EmbedRowsFn.apply(torch.arange(C, device=dev), cell.embedding.weight, lin_word.kp, dtype)
+        G = lin_iw(lin_word(rows))
+        cat = _SeqLinear([Wa[:, :Hd], cell.rnn.weight_hh], [None, cell.rnn.bias_hh], Hd, dtype)
+        ic = _SeqLinear(cell.rnn.weight_ih[:, Hd:Hd + E], None, Ep, dtype)
+        out = _SeqLinear(cell.out.weight, cell.out.bias, Hd, dtype)
+        return G, cat, ic, out
+
+    def read(self, feature, beam=1, nbest=1, attention=False):
+        """Decode in eval mode AND say how sure the decoder is and where it looked.  Returns a dict of device tensors:
+          ids i32 [N, nbest, S] (S = max_size; blank from the end of a string on), lengths i32 [N, nbest] (the symbols before the
+          first blank; S when there is none), scores f32 [N, nbest] descending, the log-probability of each string with its
+          terminating blank, count i32 [N] (the hypotheses returned; slots past it: length 0, score -inf);
+          of the FIRST hypothesis: sym_lp f32 [N, S], the log-probability of the word emitted at every step, and moments f32
+          [N, S, 4], the mean and standard deviation (cx, cy, sx, sy) of the step's attention map over the height x max_size
+          feature grid, in cells; with attention=True also att f32 [N, S, height, max_size], the maps themselves.  The entries of
+          the steps behind a string's terminating blank belong to no string: the loop ran on, on whatever it fed itself.
+        beam = 1 is the greedy string of `forward` before its early-stop trim: the one persistent launch where it takes the shape
+        (with its hidden states stored; the words it emits behind a row's own blank are masked to blank, so every path returns the
+        same ids), else the per-step kernels.  beam > 1 (up to 64, nbest <= beam) is a beam search over the
+        per-step kernels in either dtype (`_beam_decode` states its memory); there is no length normalisation.  The scores and the
+        maps come from ONE parallel pass behind the loop (`_replay_read`): given the hidden states, no step depends on another.
+        Nothing waits for the device: the call is capturable in a graph."""
+        beam, nbest = int(beam), int(nbest)
+        if not 1 <= nbest <= beam <= 64:
+            raise ValueError("read needs 1 <= nbest <= beam <= 64, got nbest=%d beam=%d" % (nbest, beam))
+        if self.training:
+            raise RuntimeError("AttentionDecoder.read is an eval-mode call: call .eval() first")
+        with torch.no_grad():
+            enc, E, dtype, eproj, lin_iw, lin_word = self._encoded(feature)
+            N, T, Ep = enc.shape
+            S, blank = self.max_size, int(self.charset.blank)
+            G, cat, ic, out = self._loop_operands(lin_iw, lin_word, E, Ep, dtype, enc.device)
+            v = self.decoder.attn.v
+            if beam == 1 and _greedy_persist_ok(dtype, N, T, self.inner_channels, Ep, len(self.charset)):
+                pred, H_all = _greedy_decode(enc, eproj, v, cat, ic, G, out, blank, S, trim=False, states=True)
+                found = {'ids': pred.view(N, 1, S)}
+            else:
+                found = _beam_decode(enc, eproj, v, cat, ic, G, out, blank, S, beam=beam, nbest=nbest)
+                H_all = found.pop('states')
+                del found['path']
+            words = found['ids'][:, 0]
+            seen = _replay_read(H_all, words, eproj, v, cat, out, blank, self.height, self.max_size, attention=attention)
+            if 'scores' not in found:                 # greedy: the one string's length and score are the replay's
+                # the kernel goes on feeding its arg-max behind a row's own blank (the trim only cuts where EVERY row is blank):
+                # those words belong to no string, and the per-step path returns blank there
+                beyond = torch.arange(S, device=enc.device)[None, :] > seen['length'][:, None]
+                found.update(ids=pred.masked_fill(beyond, blank).view(N, 1, S), lengths=seen['length'].view(N, 1),
+                             scores=seen['score'].view(N, 1), count=torch.ones((N,), dtype=torch.int32, device=enc.device))
+            found.update(sym_lp=seen['sym_lp'], moments=seen['moments'])
+            if attention:
+                found['att'] = seen['att'].view(N, S, self.height, self.max_size)
+            return found
+
+    def forward(self, feature, targets=None, lengths=None, train=False):
+        enc, E, dtype, eproj, lin_iw, lin_word = self._encoded(feature)
+        N, T, Ep = enc.shape
+        Hd = self.inner_channels
+        cell = self.decoder
+        C = len(self.charset)
+        dev = enc.device
+        Wa = cell.attn.attn.weight
+        Cp = lin_word.kp
         if self.training:
             targets = targets.to(device=dev, dtype=torch.long)
             lengths_d = lengths.to(dev)
@@ -666,11 +830,7 @@ class AttentionDecoder(nn.Module):
         # persistent launch per 64 rows and the early stop as a trim behind it -- no host synchronisation (_greedy_decode)
         if _greedy_persist_ok(dtype, N, T, Hd, Ep, C):
             with torch.no_grad():
-                rows = _EmbedRowsFn.apply(torch.arange(C, device=dev), cell.embedding.weight, Cp, dtype)
-                G = lin_iw(lin_word(rows))                      # the word table of the training branch
-                cat = _SeqLinear([Wa[:, :Hd], cell.rnn.weight_hh], [None, cell.rnn.bias_hh], Hd, dtype)
-                ic = _SeqLinear(cell.rnn.weight_ih[:, Hd:Hd + E], None, Ep, dtype)
-                out = _SeqLinear(cell.out.weight, cell.out.bias, Hd, dtype)
+                G, cat, ic, out = self._loop_operands(lin_iw, lin_word, E, Ep, dtype, dev)
                 return _greedy_decode(enc, eproj, cell.attn.v, cat, ic, G, out, self.charset.blank, self.max_size)
         # otherwise one step at a time
         lin_h = _SeqLinear(Wa[:, :Hd], None, Hd, dtype)

@@ -238,6 +238,106 @@ def ctc2d_char_rows(classify, mask, targets, target_lengths, align, blank=0):
     return out
 
 
+def _rows2d(t, who, name, dtype=None):
+    """A [.., K] tensor whose last dimension is contiguous and whose leading dimensions are one even run of rows: its leading
+    dimension in elements."""
+    if t.dim() < 2 or t.stride(-1) != 1 or (dtype is not None and t.dtype != dtype):
+        raise ValueError("%s: %s must be %s with a contiguous last dimension, got %s %s strides %s"
+                         % (who, name, dtype or "a matrix", t.dtype, tuple(t.shape), t.stride()))
+    ld = t.stride(-2)
+    for d in range(t.dim() - 2):
+        if t.shape[d] > 1 and t.stride(d) != t.stride(d + 1) * t.shape[d + 1]:
+            raise ValueError("%s: the rows of %s are not evenly spaced (strides %s)" % (who, name, t.stride()))
+    return ld
+
+
+def attention_read(hproj, eproj, v, logits, words, blank, height, width, attention=False):
+    """The replay read of an attention decoder (mr_attn_read, include/megreader_hip.h): what every step of a decode loop saw and
+    said, from its hidden states, for all steps in parallel.  hproj [S, N, >= H] (the attention half of the hidden projection of
+    H_all[0..S-1]; a column slice of a wider GEMM output is fine), eproj [N, T, H] contiguous, v [H], logits [S, N, >= C] (the
+    output layer of H_all[1..S]) -- one dtype, f32 or bf16 -- and words int32 [N, >= S], the word emitted at every step; the grid
+    height x width = T.  `C` is `logits.shape[2]` and `H` is `eproj.shape[2]`: pass views of exactly that many columns.
+    Returns a dict of device tensors: sym_lp f32 [N, S], the log-probability of every emitted word; moments f32 [N, S, 4], the
+    mean and standard deviation (cx, cy, sx, sy) of the attention map in grid cells; length i32 [N], the index of the first
+    blank (S: none); score f32 [N], the log-probability of the string with its terminating blank; and with attention=True att
+    f32 [N, S, T].  Two launches, capturable."""
+    who = "attention_read"
+    require_cuda(hproj, eproj, v, logits, words)
+    if eproj.dim() != 3 or hproj.dim() != 3 or logits.dim() != 3 or words.dim() != 2:
+        raise ValueError("%s: hproj [S, N, H], eproj [N, T, H], logits [S, N, C], words [N, S]; got %s %s %s %s"
+                         % (who, tuple(hproj.shape), tuple(eproj.shape), tuple(logits.shape), tuple(words.shape)))
+    N, T, H = eproj.shape
+    S, C = logits.shape[0], logits.shape[2]
+    if tuple(hproj.shape) != (S, N, H) or logits.shape[1] != N or words.shape[0] != N or words.shape[1] < S \
+            or tuple(v.shape) != (H,):
+        raise ValueError("%s: shapes do not agree: hproj %s eproj %s v %s logits %s words %s"
+                         % (who, tuple(hproj.shape), tuple(eproj.shape), tuple(v.shape), tuple(logits.shape), tuple(words.shape)))
+    dtype = eproj.dtype
+    if dtype not in (torch.float32, torch.bfloat16) or hproj.dtype != dtype or logits.dtype != dtype:
+        raise TypeError("%s: hproj, eproj and logits share one of float32 / bfloat16, got %s %s %s"
+                        % (who, hproj.dtype, eproj.dtype, logits.dtype))
+    if not eproj.is_contiguous():
+        raise ValueError("%s: eproj must be contiguous" % who)
+    ldh, ldl = _rows2d(hproj, who, "hproj"), _rows2d(logits, who, "logits")
+    ldp = _rows2d(words, who, "words", torch.int32)
+    vf = v.detach().float().contiguous()
+    dev = eproj.device
+    out = {'sym_lp': torch.empty((N, S), dtype=torch.float32, device=dev),
+           'moments': torch.empty((N, S, 4), dtype=torch.float32, device=dev),
+           'length': torch.empty((N,), dtype=torch.int32, device=dev),
+           'score': torch.empty((N,), dtype=torch.float32, device=dev)}
+    if attention:
+        out['att'] = torch.empty((N, S, T), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        call("mr_attn_read", _DT[dtype], ptr(hproj), ldh, ptr(eproj), ptr(vf), ptr(logits), ldl, ptr(words), ldp, int(blank), N, S,
+             T, H, C, int(height), int(width), ptr(out.get('att')), ptr(out['sym_lp']), ptr(out['moments']), ptr(out['length']),
+             ptr(out['score']))
+    return out
+
+
+def attention_beam_step(logits, hprime, h_next, score, finished, length, parent, word, feed, s, blank, classes=None):
+    """One selection step of the attention beam search (mr_attn_beam_step, include/megreader_hip.h), in place on the caller's
+    buffers: logits [N * B, >= C] and hprime, h_next [N * B, H] of one dtype (f32 / bf16, contiguous rows); score f32, finished
+    i32, length i32 [N, B]; parent, word i32 [S, N, B]; feed i64 [N, B]; step s.  `classes` = C when the logits rows are
+    padded.  One launch, capturable."""
+    who = "attention_beam_step"
+    require_cuda(logits, hprime, h_next, score, finished, length, parent, word, feed)
+    S, N, B = parent.shape
+    C = logits.shape[1] if classes is None else int(classes)
+    H = hprime.shape[1]
+    state = ((score, torch.float32), (finished, torch.int32), (length, torch.int32), (feed, torch.int64))
+    if any(tuple(t.shape) != (N, B) or t.dtype != dt or not t.is_contiguous() for t, dt in state) \
+            or any(tuple(t.shape) != (S, N, B) or t.dtype != torch.int32 or not t.is_contiguous() for t in (parent, word)):
+        raise ValueError("%s: score f32, finished i32, length i32, feed i64 [N, B] and parent, word i32 [S, N, B], contiguous" % who)
+    if logits.shape[0] != N * B or tuple(hprime.shape) != (N * B, H) or tuple(h_next.shape) != (N * B, H) \
+            or not (hprime.is_contiguous() and h_next.is_contiguous()) or logits.stride(1) != 1 \
+            or hprime.dtype != logits.dtype or h_next.dtype != logits.dtype or logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("%s: logits [N * B, C] and hprime, h_next [N * B, H] of one dtype (f32 / bf16), rows contiguous" % who)
+    with torch.cuda.device(logits.device):
+        call("mr_attn_beam_step", _DT[logits.dtype], ptr(logits), logits.stride(0), ptr(hprime), ptr(h_next), H, ptr(score),
+             ptr(finished), ptr(length), ptr(parent), ptr(word), ptr(feed), int(s), S, N, B, C, int(blank))
+
+
+def attention_beam_trace(parent, word, score, finished, length, nbest, blank):
+    """The hypotheses of a finished attention beam search (mr_attn_beam_trace, include/megreader_hip.h) from the buffers
+    `attention_beam_step` filled: a dict of device tensors ids i32 [N, nbest, S] blank padded, lengths i32 [N, nbest], scores f32
+    [N, nbest] descending, count i32 [N], path i32 [N, nbest, S + 1] (the row a hypothesis occupied entering every step).  One
+    launch, capturable."""
+    require_cuda(parent, word, score, finished, length)
+    S, N, B = parent.shape
+    nbest = int(nbest)
+    dev = parent.device
+    out = {'ids': torch.empty((N, nbest, S), dtype=torch.int32, device=dev),
+           'lengths': torch.empty((N, nbest), dtype=torch.int32, device=dev),
+           'scores': torch.empty((N, nbest), dtype=torch.float32, device=dev),
+           'count': torch.empty((N,), dtype=torch.int32, device=dev),
+           'path': torch.empty((N, nbest, S + 1), dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        call("mr_attn_beam_trace", ptr(parent), ptr(word), ptr(score), ptr(finished), ptr(length), S, N, B, nbest, int(blank),
+             ptr(out['ids']), ptr(out['lengths']), ptr(out['scores']), ptr(out['count']), ptr(out['path']))
+    return out
+
+
 def sequence_measure(labels, preds, blank=0, unknown=1, fold=None):
     """labels i32 [N, S], preds i32 [N, S2] (device).  Returns dict of device tensors:
     accuracy (bool [N]), edit_distance (f64 [N], the reference's normalised score), distance (i32 [N], the Levenshtein

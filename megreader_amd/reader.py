@@ -28,7 +28,12 @@ A recogniser whose eval output is the pair (classify [M, C, H, W], mask [M, 1, H
 of the 2-D head are the 1-D CTC probabilities of that marginal, so the beam, the lexicon and the alignment read it unchanged.
 `decode='ctc'` is `ctc2d_greedy_decode`, the rule `CTCRepresenter2D` scores.  With `chars=True` `ctc2d_char_rows` also gives every
 character the band of heights it lies on, and its quad spans that band instead of the whole height of the crop (per chunk the
-lowest and the highest height of every character cross to the host as well)."""
+lowest and the highest height of every character cross to the host as well).
+
+An attention recogniser (a backbone and an `AttentionDecoder`) has no posterior to read; `decode='attention'` goes through
+`AttentionDecoder.read` instead: the probability of the string and of every character under the decoder, n-best strings by beam
+search, and character boxes from the mean and spread of each step's attention map (per chunk the words' log-probabilities
+and four moments per character cross to the host)."""
 import math
 
 import numpy as np
@@ -46,21 +51,36 @@ from .structure.seg_detector_representer import SegDetectorRepresenter
 class TextReader(object):
     def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
                  rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
-                 lexicon_max_distance=None, lexicon_rule='nearest', beam_width=8, nbest=1, beam_top_classes=16, chars=False,
-                 column_geometry=None, row_geometry=None):
+                 lexicon_max_distance=None, lexicon_rule='nearest', beam_width=None, nbest=1, beam_top_classes=16, chars=False,
+                 column_geometry=None, row_geometry=None, attention_extent=1.5):
         if lexicon_rule not in ('nearest', 'likelihood'):
             raise ValueError("lexicon_rule must be 'nearest' or 'likelihood', got %r" % (lexicon_rule,))
         if lexicon_rule == 'likelihood' and decode != 'ctc':
             raise ValueError("lexicon_rule='likelihood' scores CTC posteriors: it needs decode='ctc', got %r" % (decode,))
-        if not (decode in ('ctc', 'ids', 'beam') or callable(decode)):
-            raise ValueError("decode must be 'ctc', 'beam', 'ids' or a callable pred -> (ids, lengths), got %r" % (decode,))
+        if not (decode in ('ctc', 'ids', 'beam', 'attention') or callable(decode)):
+            raise ValueError("decode must be 'ctc', 'beam', 'ids', 'attention' or a callable pred -> (ids, lengths), got %r"
+                             % (decode,))
+        if beam_width is None:                              # the CTC beam's default is 8 prefixes, the attention reader's greedy
+            beam_width = 1 if decode == 'attention' else 8
         if decode == 'beam' and not (1 <= int(nbest) <= int(beam_width) <= 64 and 1 <= int(beam_top_classes) <= 64):
             raise ValueError("decode='beam' needs 1 <= nbest <= beam_width <= 64 and 1 <= beam_top_classes <= 64, got nbest=%r "
                              "beam_width=%r beam_top_classes=%r" % (nbest, beam_width, beam_top_classes))
         if int(max_crops) < 1:
             raise ValueError("max_crops must be at least 1, got %r" % (max_crops,))
-        if chars and decode not in ('ctc', 'beam'):
-            raise ValueError("chars=True aligns the text to a CTC posterior: it needs decode='ctc' or 'beam', got %r" % (decode,))
+        if decode == 'attention':
+            if not 1 <= int(nbest) <= int(beam_width) <= 64:
+                raise ValueError("decode='attention' needs 1 <= nbest <= beam_width <= 64, got nbest=%r beam_width=%r"
+                                 % (nbest, beam_width))
+            if not (callable(getattr(recognizer, 'read', None))
+                    or (hasattr(recognizer, 'backbone') and callable(getattr(getattr(recognizer, 'decoder', None), 'read', None)))):
+                raise ValueError("decode='attention' needs a recogniser with read(crops, beam=, nbest=), or with .backbone and "
+                                 ".decoder (an AttentionDecoder), got %r" % (type(recognizer).__name__,))
+            if not (math.isfinite(float(attention_extent)) and float(attention_extent) >= 0.0):
+                raise ValueError("attention_extent must be a finite number of standard deviations >= 0, got %r"
+                                 % (attention_extent,))
+        if chars and decode not in ('ctc', 'beam', 'attention'):
+            raise ValueError("chars=True aligns the text to a CTC posterior or reads an attention decoder's maps: it needs "
+                             "decode='ctc', 'beam' or 'attention', got %r" % (decode,))
         if column_geometry is not None:
             stride, offset = (float(v) for v in column_geometry)
             if not (stride > 0.0 and math.isfinite(stride) and math.isfinite(offset)):
@@ -83,6 +103,7 @@ class TextReader(object):
         self.chars = bool(chars)
         self.column_geometry = column_geometry
         self.row_geometry = row_geometry
+        self.attention_extent = float(attention_extent)
         if lexicon is not None and not isinstance(lexicon, Lexicon):
             lexicon = Lexicon(lexicon, charset)
         self.lexicon = lexicon
@@ -121,14 +142,15 @@ class TextReader(object):
         return ctc_greedy_decode(post, blank=self.blank, unknown=self.unknown) + (None,)
 
     @staticmethod
-    def _eval(module, x):
-        """module(x) under no_grad, in eval mode for the call (a module that was training is put back)."""
+    def _eval(module, x, call=None):
+        """module(x) -- or call(x), which runs `module` -- under no_grad, in eval mode for the call (a module that was training is
+        put back)."""
         was_training = bool(getattr(module, 'training', False))
         if was_training:
             module.eval()
         try:
             with torch.no_grad():
-                return module(x)
+                return module(x) if call is None else call(x)
         finally:
             if was_training:
                 module.train()
@@ -138,14 +160,7 @@ class TextReader(object):
         nbest > 1, {'alternatives'}).  The ids, lengths and scores of the hypotheses are all that crosses to the host."""
         out = ctc_beam_search_decode(pred, beam=self.beam_width, nbest=self.nbest, top_classes=self.beam_top_classes,
                                      blank=self.blank, unknown=self.unknown)
-        scores, count = out['scores'].cpu().tolist(), out['count'].cpu().tolist()
-        extras = [{'text_score': float(row[0]) if k > 0 else float('-inf')} for row, k in zip(scores, count)]
-        if self.nbest > 1:
-            ids, lengths = out['ids'].cpu().numpy(), out['lengths'].cpu().numpy()
-            for extra, rows, lens, row_scores, k in zip(extras, ids, lengths, scores, count):
-                extra['alternatives'] = [(self.charset.label_to_string(rows[j][:int(lens[j])]), float(row_scores[j]))
-                                         for j in range(k)]
-        return out['ids'][:, 0], out['lengths'][:, 0], extras
+        return out['ids'][:, 0], out['lengths'][:, 0], self._hypotheses(out)
 
     def _align(self, pred, ids, lengths, found, head2d=None):
         """One chunk's FINAL strings aligned to its posterior (`ctc_forced_align`): (begin, end, sym_lp) as numpy [M, S], the
@@ -258,10 +273,16 @@ class TextReader(object):
           'raw_text', 'lexicon_distance'   with a lexicon: the decoded string, and the distance of the word found (taken or not);
           'lexicon_score'     with the likelihood rule: log p(word | posterior);
           'extras'            with decode='beam': the dict of the keys the beam adds to an item;
-          'spans'             with chars=True: what `_spans` returns for the final text (None: it could not be aligned).
+          'spans'             with chars=True: what `_spans` returns for the final text (None: it could not be aligned);
+          'marks'             with decode='attention' and chars=True: per character of the decoded string (character, sym_lp, cx,
+                              cy, sx, sy), and the decoder's grid (height, max_size).
         Per chunk of `max_crops`: (the marginal of a 2-D head,) decode, lexicon and align on the device, then one step that copies
         to the host."""
         records = []
+        if self.decode == 'attention':
+            for lo in range(0, crops.shape[0], self.max_crops):
+                records.extend(self._read_attention(crops[lo:lo + self.max_crops]))
+            return records
         for lo in range(0, crops.shape[0], self.max_crops):
             pred = self._eval(self.recognizer, crops[lo:lo + self.max_crops])
             head2d = self._head2d(pred)
@@ -274,6 +295,61 @@ class TextReader(object):
             aligned = self._align(post, ids, lengths, found, head2d) if self.chars else None
             records.extend(self._to_host(ids, lengths, extras, found, aligned))
         return records
+
+    def _hypotheses(self, out):
+        """What a beam's n-best adds to the items of one chunk (out: ids, lengths, scores and count on the device): per crop
+        {'text_score'} and, with nbest > 1, {'alternatives'}.  The ids, lengths and scores are all that crosses to the host."""
+        scores, count = out['scores'].cpu().tolist(), out['count'].cpu().tolist()
+        extras = [{'text_score': float(row[0]) if k > 0 else float('-inf')} for row, k in zip(scores, count)]
+        if self.nbest > 1:
+            ids, lengths = out['ids'].cpu().numpy(), out['lengths'].cpu().numpy()
+            for extra, rows, lens, row_scores, k in zip(extras, ids, lengths, scores, count):
+                extra['alternatives'] = [(self.charset.label_to_string(rows[j][:int(lens[j])]), float(row_scores[j]))
+                                         for j in range(k)]
+        return extras
+
+    def _read_attention(self, crops):
+        """One chunk's records with decode='attention': the recogniser's `read` (or its decoder's, behind the backbone), the
+        nearest lexicon word of the decoded string, and with chars=True the 'marks' of the decoded string -- per chunk sym_lp
+        and moments up to the chunk's longest string cross to the host besides the ids, lengths and scores.  A step that
+        emitted `unknown` spells nothing in 'text' (`label_to_string` drops it) and gets no mark either."""
+        rec = self.recognizer
+        kw = dict(beam=self.beam_width, nbest=self.nbest)
+        if callable(getattr(rec, 'read', None)):
+            decoder, out = rec, self._eval(rec, crops, lambda x: rec.read(x, **kw))
+        else:
+            decoder, out = rec.decoder, self._eval(rec, crops, lambda x: rec.decoder.read(rec.backbone(x), **kw))
+        ids, lengths = out['ids'][:, 0], out['lengths'][:, 0]
+        found = self._lexicon(None, ids, lengths)
+        ids, lengths = ids.cpu(), lengths.cpu()                               # (the one copy: `_to_host` and the marks read it)
+        records = self._to_host(ids, lengths, self._hypotheses(out), found, None)
+        if self.chars:
+            grid = (int(decoder.height), int(decoder.max_size))
+            rows, lens = ids.numpy(), lengths.numpy()
+            longest = int(lens.max()) if len(lens) else 0
+            sym_lp, moments = out['sym_lp'][:, :longest].cpu().numpy(), out['moments'][:, :longest].cpu().numpy()
+            for m, rec_ in enumerate(records):
+                spelt = [(self.charset.label_to_string(rows[m][j:j + 1]), float(sym_lp[m][j]))
+                         + tuple(float(x) for x in moments[m][j]) for j in range(int(lens[m]))]
+                rec_['marks'] = ([mark for mark in spelt if mark[0]], grid)
+        return records
+
+    def _attention_chars(self, plan, marks):
+        """One item's 'chars' from its crop's plan and the decoder's marks: the rectangle around the mean of each character's
+        attention map (`read`), on the canvas, clamped to it, carried to the photo."""
+        marks, (height, width) = marks
+        H, W = plan.canvas
+        cell_w, cell_h = float(W) / width, float(H) / height
+        chars = []
+        for ch, lp, cx, cy, sx, sy in marks:
+            hx, hy = max(self.attention_extent * sx, 0.5), max(self.attention_extent * sy, 0.5)
+            u0 = min(max((cx - hx) * cell_w, 0.0), float(plan.dst_w))
+            u1 = min(max((cx + hx) * cell_w, 0.0), float(plan.dst_w))
+            v0 = min(max((cy - hy) * cell_h, 0.0), float(H))
+            v1 = min(max((cy + hy) * cell_h, 0.0), float(H))
+            quad = plan.canvas_to_photo([[u0, v0], [u1, v0], [u1, v1], [u0, v1]])
+            chars.append({'char': ch, 'quad': quad.tolist(), 'score': math.exp(lp)})
+        return chars
 
     def _chars(self, plan, spans):
         """One item's 'chars' from its crop's plan and aligned spans: the canvas rectangle of each character's columns (of a 2-D
@@ -329,7 +405,20 @@ class TextReader(object):
         V in [row_offset + row_lo * row_stride, row_offset + (row_hi + 1) * row_stride], clamped to the canvas, row_lo and row_hi
         the lowest and highest of the most probable heights of its columns (`ctc2d_char_rows`; a lexicon word's over the folded
         alphabet); `row_geometry` is (row_stride, row_offset) in canvas pixels, None means (H_canvas / H, 0).  'score' stays
-        exp(sym_lp / (end - begin)) on the marginal."""
+        exp(sym_lp / (end - begin)) on the marginal.
+        With `decode='attention'` the recogniser is an attention decoder: a module with `read(crops, beam=, nbest=)`, or one with
+        `.backbone` and `.decoder` (an `AttentionDecoder`), read through `AttentionDecoder.read` with `beam_width` (None: 1,
+        greedy) hypotheses.  'text' is the first hypothesis up to its first blank and every item also has 'text_score', the
+        log-probability of that string with its terminating blank under the decoder (no length normalisation); with `nbest > 1`
+        also 'alternatives' as above.  With a lexicon (the `nearest` rule only) the nearest word is searched for the decoded
+        string as for `decode='beam'`.  With `chars=True` every item also has 'chars', one {'char', 'quad', 'score'} per
+        character of the DECODED string -- with a lexicon the boxes stay those of 'raw_text', also where a word was taken: the
+        decoder has attended to what it read, not to the word; a step that emitted `unknown` spells nothing and has no entry -- where 'score' is the probability of the character at its step,
+        exp(sym_lp), and 'quad' comes from the step's attention map over the decoder's height x max_size feature grid: with
+        (cx, cy) its mean and (sx, sy) its standard deviation in cells, the rectangle cx +- max(attention_extent * sx, 0.5) by
+        cy +- max(attention_extent * sy, 0.5) cells, scaled by W_canvas / max_size and H_canvas / height, clamped to the valid
+        canvas and carried to the photo by `CropPlan.canvas_to_photo`.  An attention map says where the decoder looked, which is
+        not a segmentation: `attention_extent` (1.5 standard deviations) is a choice, and half a cell the least box."""
         images = list(images)
         results = [[] for _ in images]
         if not images:
@@ -358,6 +447,8 @@ class TextReader(object):
             item.update(rec.get('extras', ()))
             if 'spans' in rec:
                 item['chars'] = self._chars(plan, rec['spans'])
+            if 'marks' in rec:
+                item['chars'] = self._attention_chars(plan, rec['marks'])
             results[i].append(item)
         if self.scores:                                                        # ... and so are their scores
             dropped = set(layout.dropped)
