@@ -880,6 +880,38 @@ int mr_jpeg_plan(int n, const void* const* blobs, const long long* lens, mr_jpeg
 int mr_jpeg_decode(const void* blobs_dev, const void* plan_dev, int n_images, int n_items, void* workspace, void* out,
                    int* status, int rgb, hipStream_t stream);
 
+/* ---- Parallel decode inside one long work item (csrc/jpeg_split.hip): a photo without restart markers is ONE item, which one
+ * wavefront decodes serially.  mr_jpeg_plan_split, host only and after mr_jpeg_plan, describes every item longer than split_above
+ * bytes in splits[] (items[i].reserved becomes 1 + its index there; the single-wave kernel skips such items) and grows totals[2],
+ * the workspace, by their regions.  The item is cut into n_sub sub-sequences of subseq_bytes UNSTUFFED bytes (a multiple of 4 in
+ * [16, 1024]; n_sub = ceil(len / subseq_bytes) from the stuffed length, an upper bound -- sub-sequences behind the data are
+ * empty), 256 per workgroup.  *n_splits is the number of such items; when it exceeds max_splits nothing was written: call again
+ * with room.  With no item above split_above the plan is left byte for byte as it was.
+ * mr_jpeg_decode_split = mr_jpeg_decode + the split stages between the status kernel and the colour kernel: unstuff, decoder
+ * synchronisation (1 + (largest n_wg - 1) launches: a sub-sequence is re-decoded until the state it was decoded from equals the
+ * state its predecessor produced, so every entry state is the serial decoder's), block-offset scan, coefficient write, DC prefix
+ * sum, inverse DCT.  splits_host / splits_dev: the same n_splits entries on the host (launch sizes) and on the device, 16-byte
+ * aligned.  Pixels and status equal mr_jpeg_decode's on the same stream of bytes.  n_splits == 0: exactly mr_jpeg_decode's three
+ * launches.  No host synchronisation, no waiting between workgroups. */
+typedef struct mr_jpeg_split {
+  int item, image;
+  int subseq_bytes, n_sub, n_wg;     /* n_wg = ceil(n_sub / 256) */
+  int n_blocks;                      /* blocks the item holds: nmcu * blocks_per_mcu */
+  int blocks_per_mcu, reserved;
+  long long meta_off;                /* workspace offsets, 16-byte aligned.  meta: int [4] = unstuffed bytes, blocks completed */
+  long long raw_off, raw_bytes;      /* the unstuffed bytes, zero from the last one up to raw_bytes */
+  long long in_off, exit_off;        /* per sub-sequence {u32 bit position; u32 blocks << 16 | block slot << 8 | zigzag index} */
+  long long wg_exit_off;             /* [2][n_wg] such states */
+  long long block_off;               /* int [n_sub]: exclusive prefix sum of completed blocks */
+  long long coef_off, coef_bytes;    /* int dc[n_blocks] (padded to 16 bytes), short coef[n_blocks][64], zigzag order */
+} mr_jpeg_split;
+int mr_sizeof_jpeg_split(void);
+int mr_jpeg_plan_split(int n_images, const mr_jpeg_image* images, mr_jpeg_item* items, long long n_items, long long split_above,
+                       int subseq_bytes, mr_jpeg_split* splits, long long max_splits, long long* totals, long long* n_splits);
+int mr_jpeg_decode_split(const void* blobs_dev, const void* plan_dev, int n_images, int n_items, const mr_jpeg_split* splits_host,
+                         const void* splits_dev, int n_splits, void* workspace, void* out, int* status, int rgb,
+                         hipStream_t stream);
+
 /* ---- DB detector augmentation (csrc/image_sample.hip): the image half of data/processes/augment_data.py
  * (`AugmentDetectionData`: Fliplr, Affine rotate, Resize), data/processes/random_crop_data.py (`RandomCropData`) and
  * data/processes/normalize_image.py in ONE bilinear pass.  The host composes the chain into one affine map per image

@@ -18,6 +18,8 @@
 //   The coefficient index stops at 63, every loop is bounded by the item's MCU count, block positions come from the MCU number
 //   alone: a malformed stream ends as MR_JPEG_CORRUPT in the image's status word (invalid code, DC size > 11, a run past 63, more
 //   bits used than the item has), never as an access outside the planes.
+//   Items that the split plan took (mr_jpeg_plan_split marks them through `reserved`) are skipped here: csrc/jpeg_split.hip decodes
+//   each of them with many lanes into the same planes, between this kernel and Stage B.
 // Stage B, jpeg_color_kernel: elementwise over output pixels, chroma upsampling + YCbCr -> RGB, 4 pixels = three aligned dword
 // stores per thread over the image's flat h*w*3 bytes (rows have no padding, so alignment follows the flat index, not the row).
 //
@@ -28,6 +30,7 @@
 #include <stddef.h>
 
 #include "common.h"
+#include "jpeg_idct.h"
 #include "jpeg_plan.h"
 #include "../../include/megreader_hip.h"
 
@@ -35,6 +38,7 @@ namespace mr {
 
 using jpeg::Image;
 using jpeg::Item;
+using namespace jpeg_dev;
 
 static_assert(sizeof(Image) == sizeof(mr_jpeg_image) && sizeof(Image) % 8 == 0, "csrc/jpeg_plan.h restates mr_jpeg_image");
 static_assert(offsetof(Image, blob_off) == offsetof(mr_jpeg_image, blob_off) &&
@@ -49,11 +53,6 @@ static_assert(sizeof(Item) == sizeof(mr_jpeg_item) && offsetof(Item, off) == off
 namespace {
 
 constexpr int WIN_BYTES = 1024;   // unstuffed bytes the LDS window holds
-constexpr int BLK_STRIDE = 72;    // dwords between the 8 waiting blocks
-
-__device__ const unsigned char ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -156,61 +155,6 @@ __device__ __forceinline__ int extend(int v, int nbits) {   // T.81 F.2.2.1
   return nbits && v < (1 << (nbits - 1)) ? v - (1 << nbits) + 1 : v;
 }
 
-// One pass of the slow-integer inverse DCT over 8 values.
-__device__ __forceinline__ void idct8(const int v[8], int out[8], int shift) {
-  int z2 = v[2], z3 = v[6];
-  int z1 = (z2 + z3) * 4433;
-  const int t2 = z1 - z3 * 15137, t3 = z1 + z2 * 6270;
-  const int t0 = (v[0] + v[4]) << 13, t1 = (v[0] - v[4]) << 13;
-  const int e0 = t0 + t3, e3 = t0 - t3, e1 = t1 + t2, e2 = t1 - t2;
-  int o0 = v[7], o1 = v[5], o2 = v[3], o3 = v[1];
-  z1 = o0 + o3, z2 = o1 + o2, z3 = o0 + o2;
-  int z4 = o1 + o3;
-  const int z5 = (z3 + z4) * 9633;
-  o0 *= 2446, o1 *= 16819, o2 *= 25172, o3 *= 12299;
-  z1 *= -7373, z2 *= -20995;
-  z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
-  o0 += z1 + z3, o1 += z2 + z4, o2 += z2 + z3, o3 += z1 + z4;
-  const int r = 1 << (shift - 1);
-  out[0] = (e0 + o3 + r) >> shift, out[7] = (e0 - o3 + r) >> shift;
-  out[1] = (e1 + o2 + r) >> shift, out[6] = (e1 - o2 + r) >> shift;
-  out[2] = (e2 + o1 + r) >> shift, out[5] = (e2 - o1 + r) >> shift;
-  out[3] = (e3 + o0 + r) >> shift, out[4] = (e3 - o0 + r) >> shift;
-}
-
-// The range-limit table of the IDCT output, indexed by the low 10 bits: as a signed 10-bit number x it holds clamp(x + 128).
-__device__ __forceinline__ unsigned range_limit(int v) {
-  const int x = ((v & 1023) ^ 512) - 512;
-  return (unsigned)min(max(x + 128, 0), 255);
-}
-
-// Inverse DCT of the `ns` waiting blocks: lane = (block, column), then (block, row); 8 bytes per lane to dst[block] + row * pitch.
-__device__ __forceinline__ void flush_blocks(int* blk, const long long* dst, const int* pitch, int ns, unsigned char* ws,
-                                             int lane) {
-  const int b = lane >> 3, c = lane & 7;
-  __syncthreads();
-  if (b < ns) {
-    int v[8], o[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = blk[b * BLK_STRIDE + r * 8 + c];
-    idct8(v, o, 11);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) blk[b * BLK_STRIDE + r * 8 + c] = o[r];
-  }
-  __syncthreads();
-  if (b < ns) {
-    int v[8], o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = blk[b * BLK_STRIDE + c * 8 + j];
-    idct8(v, o, 18);
-    uint2 px;
-    px.x = range_limit(o[0]) | range_limit(o[1]) << 8 | range_limit(o[2]) << 16 | range_limit(o[3]) << 24;
-    px.y = range_limit(o[4]) | range_limit(o[5]) << 8 | range_limit(o[6]) << 16 | range_limit(o[7]) << 24;
-    *(uint2*)(ws + dst[b] + (long long)c * pitch[b]) = px;   // planes are 16-byte aligned with pitches that are multiples of 8
-  }
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(64) void jpeg_entropy_idct_kernel(const unsigned char* blobs, const Image* images,
                                                                const Item* items, unsigned char* ws, int* status) {
   __shared__ __attribute__((aligned(16))) unsigned char win[WIN_BYTES + 16];
@@ -221,6 +165,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_idct_kernel(const unsigned ch
   const int lane = threadIdx.x;
   const Item it = items[blockIdx.x];
   const Image* im = images + it.image;
+  if (it.reserved != 0) return;         // an item of the split plan: csrc/jpeg_split.hip decodes it
   if (im->status != jpeg::OK) return;   // an image the caller re-marked for the host decoder after planning
   const int ncomp = im->ncomp, mcu_w = im->mcu_w;
   // this lane's share of the tables: code-length entries (lanes 0..15), the quantiser and the zigzag position of coefficient `lane`
@@ -368,6 +313,11 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const Image* images, co
 }
 
 }  // namespace
+
+// csrc/jpeg_split.hip: the stages that decode the items of the split plan
+int jpeg_split_stages(const unsigned char* blobs, const Image* images, const Item* items, const jpeg::Split* host,
+                      const jpeg::Split* dev, int n_splits, unsigned char* ws, int* status, hipStream_t stream);
+
 }  // namespace mr
 
 using namespace mr;
@@ -388,14 +338,17 @@ int mr_jpeg_plan(int n, const void* const* blobs, const long long* lens, mr_jpeg
   return MR_OK;
 }
 
-int mr_jpeg_decode(const void* blobs_dev, const void* plan_dev, int n_images, int n_items, void* workspace, void* out,
-                   int* status, int rgb, hipStream_t stream) {
-  MR_CHECK_ARG(n_images >= 0 && n_items >= 0, "mr_jpeg_decode: bad counts n_images=%d n_items=%d", n_images, n_items);
+int mr_jpeg_decode_split(const void* blobs_dev, const void* plan_dev, int n_images, int n_items, const mr_jpeg_split* splits_host,
+                         const void* splits_dev, int n_splits, void* workspace, void* out, int* status, int rgb,
+                         hipStream_t stream) {
+  MR_CHECK_ARG(n_images >= 0 && n_items >= 0 && n_splits >= 0 && n_splits <= 65535 && n_splits <= n_items,
+               "mr_jpeg_decode: bad counts n_images=%d n_items=%d n_splits=%d", n_images, n_items, n_splits);
   if (n_images == 0) return MR_OK;
   MR_CHECK_ARG(plan_dev != nullptr && status != nullptr, "mr_jpeg_decode: null pointer");
   MR_CHECK_ARG(((uintptr_t)blobs_dev & 15) == 0 && ((uintptr_t)plan_dev & 15) == 0 && ((uintptr_t)workspace & 15) == 0 &&
-                   ((uintptr_t)out & 15) == 0,
-               "mr_jpeg_decode: the blob buffer, the plan, the workspace and the output must be 16-byte aligned");
+                   ((uintptr_t)out & 15) == 0 && ((uintptr_t)splits_dev & 15) == 0,
+               "mr_jpeg_decode: the blob buffer, the plan, the split table, the workspace and the output must be 16-byte aligned");
+  MR_CHECK_ARG(n_splits == 0 || (splits_host != nullptr && splits_dev != nullptr), "mr_jpeg_decode_split: null split table");
   const Image* images = (const Image*)plan_dev;
   const Item* items = (const Item*)(images + n_images);
   hipLaunchKernelGGL(jpeg_status_kernel, dim3(cdiv(n_images, 256)), dim3(256), 0, stream, images, n_images, status);
@@ -405,10 +358,20 @@ int mr_jpeg_decode(const void* blobs_dev, const void* plan_dev, int n_images, in
   hipLaunchKernelGGL(jpeg_entropy_idct_kernel, dim3(n_items), dim3(64), 0, stream, (const unsigned char*)blobs_dev, images, items,
                      (unsigned char*)workspace, status);
   MR_CHECK_LAUNCH();
+  if (n_splits > 0) {
+    const int rc = jpeg_split_stages((const unsigned char*)blobs_dev, images, items, (const jpeg::Split*)splits_host,
+                                     (const jpeg::Split*)splits_dev, n_splits, (unsigned char*)workspace, status, stream);
+    if (rc != MR_OK) return rc;
+  }
   hipLaunchKernelGGL(jpeg_color_kernel, dim3(n_images, 8), dim3(256), 0, stream, images, (const unsigned char*)workspace,
                      (unsigned char*)out, rgb);
   MR_CHECK_LAUNCH();
   return MR_OK;
+}
+
+int mr_jpeg_decode(const void* blobs_dev, const void* plan_dev, int n_images, int n_items, void* workspace, void* out,
+                   int* status, int rgb, hipStream_t stream) {
+  return mr_jpeg_decode_split(blobs_dev, plan_dev, n_images, n_items, nullptr, nullptr, 0, workspace, out, status, rgb, stream);
 }
 
 }  // extern "C"

@@ -245,5 +245,71 @@ static inline void plan(int n, const void* const* blobs, const long long* lens, 
   *totals = t;
 }
 
+// ---- The split plan (csrc/jpeg_split.hip): items too long for one wavefront are cut into sub-sequences of `subseq_bytes`
+// UNSTUFFED bytes that 256-lane workgroups decode in parallel.  The number of unstuffed bytes is known only on the device, so
+// the count comes from the stuffed length, an upper bound: n_sub = ceil(len / subseq_bytes); sub-sequences behind the last
+// unstuffed byte are empty.  Split is the layout of mr_jpeg_split; every offset is into the workspace and 16-byte aligned.
+struct Split {
+  int item, image;                // the work item (items[item].reserved = 1 + this entry's index) and its image
+  int subseq_bytes, n_sub, n_wg;  // n_wg = ceil(n_sub / 256) workgroups
+  int n_blocks;                   // nmcu * B blocks wanted, B = hs * vs + 2 (colour) or 1 (gray)
+  int blocks_per_mcu, reserved;
+  long long meta_off;             // int [4]: unstuffed bytes, blocks completed, 0, 0
+  long long raw_off, raw_bytes;   // the unstuffed bytes, zero behind the last one up to raw_bytes
+  long long in_off, exit_off;     // per sub-sequence, 8 bytes each: the state it was decoded from / the state it produced
+  long long wg_exit_off;          // [2][n_wg] x 8 bytes: the exit state of each workgroup, one copy per pass parity
+  long long block_off;            // int [n_sub]: blocks completed in front of each sub-sequence
+  long long coef_off, coef_bytes; // int dc[n_blocks], then short coef[n_blocks][64] in zigzag order (zeroed by the decoder)
+};
+
+constexpr int SPLIT_WG = 256;                       // sub-sequences per workgroup
+constexpr long long SPLIT_MAX_LEN = 1LL << 27;      // bit positions stay below 2^31
+
+static inline bool split_wanted(const Image* images, const Item& it, long long split_above) {
+  return it.reserved == 0 && images[it.image].status == OK && it.len > split_above && it.len > 0 && it.len < SPLIT_MAX_LEN &&
+         it.nmcu > 0;
+}
+
+// Describes every item longer than `split_above` bytes in splits[] and appends its regions to *workspace_bytes.  Returns the
+// number of such items; when that exceeds max_splits NOTHING is written (call again with room).  subseq_bytes: a multiple of 4
+// in [16, 1024] (the caller checks).
+static inline long long plan_split(const Image* images, Item* items, long long n_items, long long split_above, int subseq_bytes,
+                                   Split* splits, long long max_splits, long long* workspace_bytes) {
+  long long count = 0;
+  for (long long i = 0; i < n_items; ++i) count += split_wanted(images, items[i], split_above) ? 1 : 0;
+  if (count > max_splits) return count;
+  long long ws = align16(*workspace_bytes), k = 0;
+  auto take = [&ws](long long bytes) {
+    const long long at = ws;
+    ws = align16(ws + bytes);
+    return at;
+  };
+  for (long long i = 0; i < n_items; ++i) {
+    if (!split_wanted(images, items[i], split_above)) continue;
+    const Image& im = images[items[i].image];
+    Split s;
+    memset(&s, 0, sizeof(s));
+    s.item = (int)i, s.image = items[i].image;
+    s.subseq_bytes = subseq_bytes;
+    s.n_sub = (int)((items[i].len + subseq_bytes - 1) / subseq_bytes);
+    s.n_wg = (s.n_sub + SPLIT_WG - 1) / SPLIT_WG;
+    s.blocks_per_mcu = im.ncomp == 3 ? im.hs * im.vs + 2 : 1;
+    s.n_blocks = items[i].nmcu * s.blocks_per_mcu;
+    s.meta_off = take(16);
+    s.raw_bytes = align16((long long)s.n_sub * subseq_bytes) + 16;
+    s.raw_off = take(s.raw_bytes);
+    s.in_off = take(8LL * s.n_sub);
+    s.exit_off = take(8LL * s.n_sub);
+    s.wg_exit_off = take(16LL * s.n_wg);
+    s.block_off = take(4LL * s.n_sub);
+    s.coef_bytes = align16(4LL * s.n_blocks) + 128LL * s.n_blocks;
+    s.coef_off = take(s.coef_bytes);
+    items[i].reserved = (int)k + 1;
+    splits[k++] = s;
+  }
+  *workspace_bytes = ws;
+  return count;
+}
+
 }  // namespace jpeg
 }  // namespace mr

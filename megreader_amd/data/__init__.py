@@ -2,6 +2,6 @@
 from .device_pipeline import DevicePipeline, EncodedDevicePipeline, Prefetcher  # noqa: F401
 from .jpeg_decode import JpegDecoder  # noqa: F401
 from .detection_augment import AugmentPlan, DetectionAugmenter, WarpDesc  # noqa: F401
-from .detection_pipeline import DetectionPipeline  # noqa: F401
+from .detection_pipeline import DetectionPipeline, EncodedDetectionPipeline  # noqa: F401
 from .quad_crop import CropPlan, QuadCropper, plan_crop, rect_corners  # noqa: F401
 from .msgpack_records import UnpackMsgpackData, records_to_batch  # noqa: F401

@@ -26,7 +26,7 @@ import torch
 
 from .._lib import STRUCTS, call, load, ptr
 from ..charsets import EnglishCharset
-from .staging import Sections, Staging, align16, check_images, upload
+from .staging import Sections, Staging, check_images, upload
 
 RGB_MEAN = (122.67891434, 116.66876762, 104.00698793)   # data/processes/normalize_image.py:9 (applied to BGR as is)
 
@@ -176,43 +176,39 @@ class EncodedDevicePipeline(DevicePipeline):
     batch); the encoded bytes cross PCIe and the device decodes them (csrc/jpeg.hip) into the buffer that `mr_resize_normalize`
     reads.  What the device does not decode (PNG, progressive JPEG, ...; `JpegDecoder.plan`) is decoded on the host as before and
     staged as raw pixels beside the blobs.  The batch also carries 'jpeg_status', int32 [n] on the device: MR_JPEG_CORRUPT where
-    an image's stream turned out to be damaged (nothing synchronises to look at it here).  Pixels are BGR, as the mean is."""
+    an image's stream turned out to be damaged (nothing synchronises to look at it here).  Pixels are BGR, as the mean is.
+    split_above: work items longer than that many bytes -- whole photos without restart markers -- are decoded by many lanes each
+    (csrc/jpeg_split.hip) and `host_above` applies to the others only; None: every item is one wavefront's, as before."""
 
-    def __init__(self, image_size=(32, 128), mode='resize', charset=None, max_size=32, device=None, host_above=None):
+    def __init__(self, image_size=(32, 128), mode='resize', charset=None, max_size=32, device=None, host_above=None,
+                 split_above=None):
         super().__init__(image_size, mode, charset, max_size, device)
         from .jpeg_decode import HOST_ABOVE, JpegDecoder
-        self.decoder = JpegDecoder(self.device, 'BGR', HOST_ABOVE if host_above is None else host_above)
+        self.decoder = JpegDecoder(self.device, 'BGR', HOST_ABOVE if host_above is None else host_above, split_above)
 
     def pack(self, blobs, texts, slot=0):
         """Host side: ONE staging buffer [blobs | plan | host-decoded pixels | descriptors | text].  The device buffer of
         `upload` is [staged bytes | workspace | decoded pixels]; the `ImgDesc` offsets point into its decoded region for the
         images the device decodes and at the staged pixels for the others.  Raises ValueError for blobs whose headers are
         corrupt."""
+        from .jpeg_decode import plan_layout, stage_plan
         plan = self.decoder.plan(blobs)
         if plan.corrupt():
             raise ValueError("corrupt JPEG data at batch indices %s" % plan.corrupt())
         n = plan.n
-        host = sorted(plan.host)
         descs = self._describe([plan.shape(i) for i in range(n)])
-        lay = Sections(plan.sections() + [plan.host[i] for i in host] + [descs] + self._text(texts), pad_end=True)
-        workspace_off = lay.total
-        out_off = workspace_off + align16(plan.workspace_bytes)
-        at = dict(zip(host, lay.offsets[3:]))
+        lay, jpeg = plan_layout(plan, [descs] + self._text(texts))
+        at = dict(zip(sorted(plan.host), lay.offsets[lay.first:]))
         for i, d in enumerate(descs):
-            d.offset = at[i] if i in at else out_off + plan.images[i].out_off
-        staged, views = self._staging.stage(slot, lay)
-        plan.fill_blobs(views[0])
-        jpeg = (plan, lay.offsets[0], lay.offsets[1], workspace_off, out_off, out_off + plan.out_bytes)
-        return staged, (n,) + tuple(lay.offsets[3 + len(host):]) + (descs, jpeg)
+            d.offset = at[i] if i in at else jpeg[4] + plan.images[i].out_off
+        staged, _ = stage_plan(plan, lay, self._staging, slot)
+        return staged, (n,) + tuple(lay.offsets[-3:]) + (descs, jpeg)
 
     def upload(self, staged, layout):
         """One device buffer, one async H2D copy of the staged part, then mr_jpeg_decode and the two kernels of
         `DevicePipeline`, on the CURRENT stream."""
-        from .jpeg_decode import launch
-        plan, blob_off, plan_off, workspace_off, out_off, total = layout[5]
-        dbuf = torch.empty((total,), dtype=torch.uint8, device=self.device)
-        dbuf[:staged.numel()].copy_(staged, non_blocking=True)
-        status = launch(plan, dbuf, blob_off, plan_off, workspace_off, out_off, False)
+        from .jpeg_decode import upload_and_launch
+        dbuf, status = upload_and_launch(staged, layout[5], self.device)
         batch = self._kernels(dbuf, layout)
         batch['jpeg_status'] = status
         return batch

@@ -39,7 +39,8 @@ import math
 import numpy as np
 import torch
 
-from .data.device_pipeline import DevicePipeline
+from .data.device_pipeline import DevicePipeline, EncodedDevicePipeline
+from .data.jpeg_decode import SPLIT_ABOVE
 from .data.quad_crop import QuadCropper
 from .ops.decode import (ctc2d_char_rows, ctc2d_greedy_decode, ctc2d_marginal, ctc_beam_search_decode, ctc_forced_align,
                          ctc_greedy_decode)
@@ -52,7 +53,7 @@ class TextReader(object):
     def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
                  rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
                  lexicon_max_distance=None, lexicon_rule='nearest', beam_width=None, nbest=1, beam_top_classes=16, chars=False,
-                 column_geometry=None, row_geometry=None, attention_extent=1.5):
+                 column_geometry=None, row_geometry=None, attention_extent=1.5, encoded=False):
         if lexicon_rule not in ('nearest', 'likelihood'):
             raise ValueError("lexicon_rule must be 'nearest' or 'likelihood', got %r" % (lexicon_rule,))
         if lexicon_rule == 'likelihood' and decode != 'ctc':
@@ -109,7 +110,12 @@ class TextReader(object):
         self.lexicon = lexicon
         self.lexicon_max_distance = None if lexicon_max_distance is None else int(lexicon_max_distance)
         self.lexicon_rule = lexicon_rule
-        self.det_pipeline = DevicePipeline(image_size=det_size, mode='resize', charset=charset)
+        self.encoded = bool(encoded)
+        if self.encoded:    # `read` takes the photos as encoded files; the device decodes them (data/jpeg_decode.py), whole photos
+            self.det_pipeline = EncodedDevicePipeline(image_size=det_size, mode='resize', charset=charset,    # by many lanes each
+                                                      split_above=SPLIT_ABOVE)
+        else:
+            self.det_pipeline = DevicePipeline(image_size=det_size, mode='resize', charset=charset)
         self.cropper = QuadCropper(image_size=rec_size, mode=rec_mode, rectify=rectify)
 
     def _upload(self, images):
@@ -374,7 +380,8 @@ class TextReader(object):
         return chars
 
     def read(self, images):
-        """images: a list of uint8 HWC numpy arrays.  Returns, per image, a list of {'quad': [[x, y] * 4], 'text': str} in the
+        """images: a list of uint8 HWC numpy arrays -- with `encoded=True` a list of `bytes`, the encoded files (JPEG decoded on the
+        device, what it does not decode on the host; a file whose header is corrupt raises ValueError).  Returns, per image, a list of {'quad': [[x, y] * 4], 'text': str} in the
         representer's box order; [] for an image without boxes.  With `scores=True` every item also has 'score': the mean of the
         detector's probability map inside the box (`SegDetectorRepresenter.represent_scored`).  With a lexicon (a `Lexicon` or a
         list of words, encoded with the reader's charset) 'text' is the lexicon word nearest to the greedy string when its edit
@@ -427,7 +434,7 @@ class TextReader(object):
         pred = self._eval(self.detector, batch['image'])
         if not isinstance(pred, dict):
             pred = {'binary': pred}
-        det_batch = {'image': batch['image'], 'shape': [im.shape[:2] for im in images]}
+        det_batch = {'image': batch['image'], 'shape': [tuple(p.shape[:2]) for p in photos]}
         if self.scores:
             boxes, box_scores, _ = self.representer.represent_scored(det_batch, pred)
         else:
