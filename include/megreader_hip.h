@@ -157,6 +157,22 @@ int mr_tn_taps_would_run(int N, int H, int W, int Cin, int ldx, int Cout, int ld
  * launches, < 0 on bad arguments. */
 int mr_tn_taps_plan(int cus, int slabs, int n, const int* tiles, const int* chunks, int* launch, int* splits, int* cps,
                     double* cost);
+/* host only: how mr_tn_flush launches n <= 64 recorded problems of the 128x128 TN GEMM kernel, in recording order, on a chip of
+ * `cus` CUs.  tiles[i] = 128 x 128 output tiles, steps[i] = 64-row p-steps of the reduction, modes[i] = 0 (dense B operand) or 2
+ * (conv operand through a row table); both modes share a launch.  The records are cut into ceil(n / mr_tn_capacity(0)) runs of
+ * equal length; a run is one launch, or one launch per mode where the model prices that lower (problems of very different depth).
+ * out: launch[i] (numbered by first problem), splits[i] (workgroups per tile, each of ceil(steps / splits) p-steps, none empty), begin[i] (first
+ * workgroup of problem i inside its launch, a multiple of 8; a problem owns tiles * splits workgroups rounded up to 8), *cost =
+ * the modelled cost in dense p-steps: per launch ceil(workgroups / (2 * cus)) * (longest workgroup + 20) * (1.3 when workgroups
+ * share CUs), a conv p-step counting 1.02 dense ones.  The splits are chosen per problem to minimise it.  A problem alone in
+ * its launch is launched as an immediate call would launch it.  Plans are cached by their inputs.  Returns the number of
+ * launches, < 0 on bad arguments. */
+int mr_tn_group_plan(int cus, int n, const int* tiles, const int* steps, const int* modes, int* launch, int* splits, int* begin,
+                     double* cost);
+/* host only: *cost = the modelled cost (as above) of ONE launch of n problems cut into the given splits[i] <= steps[i] */
+int mr_tn_group_cost(int cus, int n, const int* tiles, const int* steps, const int* modes, const int* splits, double* cost);
+/* host only: problems per launch of mr_tn_flush; kind 0: the 128x128 TN GEMM kernel, kind 1: the all-taps kernel, else 0 */
+int mr_tn_capacity(int kind);
 /* tile (BM*1000+BN) the NT kernels pick for an M x N problem; host-only query used for profiling labels */
 int mr_nt_tile_code(int M, int N);
 /* same, including the big-tile policy (returns 256256 for the 8-wave 256x256 kernel); cg = channels of the gathered
@@ -177,8 +193,8 @@ int mr_gemm_tn2(int dtype, const void* A, long long lda, const void* B, long lon
  * of 16..64 output tiles: alone, each has to cut its pixel loop into 8..32 splits to fill the chip.  Nothing later in the backward
  * pass reads them, so they can wait and run side by side.  mr_tn_defer(1): on the calling host thread, bf16 launches that would
  * take the 128x128 TN GEMM kernel (mr_gemm_tn, mr_conv2d_wgrad_tab) are RECORDED (operand pointers and geometry) instead of
- * launched; mr_tn_defer(0) stops recording.  mr_tn_flush launches everything recorded, up to 12 problems per launch, each with
- * 1 / n-th of the splits.  The 3x3 layers that mr_conv2d_wgrad_tab gives to the all-taps kernel are recorded too (their stream
+ * launched; mr_tn_defer(0) stops recording.  mr_tn_flush launches everything recorded, up to mr_tn_capacity(0) = 16 problems per
+ * launch, dense and conv problems together, each cut as mr_tn_group_plan says.  The 3x3 layers that mr_conv2d_wgrad_tab gives to the all-taps kernel are recorded too (their stream
  * table is still built at once): every workgroup of that kernel pays a fixed price -- prologue and a 147 KB partial tile --
  * whatever it reduced, so the flush packs up to 8 of them into one launch with fewer splits each (mr_tn_taps_plan); under
  * mr_tuning.tn_taps_fin / tn_taps_w8 / tn_splits they are launched one by one.  The caller keeps every operand alive and unmodified until the flush, flushes on the
@@ -187,6 +203,8 @@ int mr_gemm_tn2(int dtype, const void* A, long long lda, const void* B, long lon
  * no-op (A/B). */
 int mr_tn_defer(int on);
 int mr_tn_pending(void);
+/* host only: the recorded problems of one kernel; kind 0: the 128x128 TN GEMM kernel, kind 1: the all-taps kernel (mr_tn_capacity) */
+int mr_tn_pending_of(int kind);
 /* The queue is per DEVICE and process-wide (records pushed by one host thread are flushed by whichever thread calls mr_tn_flush
  * with that device current); mr_tn_discard drops the current device's records without launching them and switches recording off
  * for the calling thread -- for a caller whose backward pass raised and is about to release the recorded operands (round 6). */

@@ -10,6 +10,8 @@
 #include "../../include/megreader_hip.h"
 
 #include <algorithm>
+#include <cmath>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -451,11 +453,11 @@ static int launch_tn_big(TnArgs a, const ConvGeom& g, int total_steps, hipStream
 // ---- deferred / grouped weight-gradient launches (mr_tn_defer, mr_tn_flush; igemm_tn_glds_grouped_kernel) ----------------
 // While deferral is on for the calling host thread, bf16 launches of the 128x128 TN GEMM kernel (dense: BMODE 0, conv with a row
 // table: BMODE 2) are RECORDED instead of launched; mr_tn_flush launches everything recorded so far, up to TN_GROUP_MAX problems
-// per launch.  The split of every problem is chosen for the GROUP: one p-step count L per workgroup for all problems, so that
-// the workgroups of the launch finish together and the chip is filled by problems, not by splits.  All-taps problems
-// (mr_conv2d_wgrad_tab, tn_taps.hip) are recorded on a queue of their own; launch_tn_taps_group plans and launches them.
+// per launch, both modes in the same launch.  The split of every problem is chosen for the GROUP (tn_group_plan): the chip is
+// filled by problems, not by splits, and the workgroups of a launch finish together.  All-taps problems (mr_conv2d_wgrad_tab,
+// tn_taps.hip) are recorded on a queue of their own; launch_tn_taps_group plans and launches them.
 #define g_tn_defer MR_TUNE(tn_defer)   // 1 (default): mr_tn_defer(1) records; 0: it is ignored (every launch immediate)
-struct TnRecord { TnArgs a; ConvGeom g; };
+struct TnRecord { TnArgs a; ConvGeom g; int mode; };   // mode: the BMODE the problem was recorded with (0 or 2)
 // Recording is switched per host THREAD (the bracket mr_tn_defer(1) ... mr_tn_defer(0) is one autograd node's), the QUEUE is per
 // DEVICE and process-wide behind a mutex: records are pushed on an autograd device worker thread, while the
 // end-of-backward callback that flushes them runs on whichever thread completes the graph task -- with a thread-local queue
@@ -463,10 +465,10 @@ struct TnRecord { TnArgs a; ConvGeom g; };
 struct TnDeferState { bool on = false; };
 static thread_local TnDeferState g_tn_defer_state;
 struct TnQueue {
-  std::vector<TnRecord> q[2];       // [0]: BMODE 0, [1]: BMODE 2
+  std::vector<TnRecord> q;          // 128x128 TN GEMM kernel, both modes, in recording order
   std::vector<TapsProblem> taps;    // all-taps kernel (tn_taps.hip): planned and launched by launch_tn_taps_group
-  size_t size() const { return q[0].size() + q[1].size() + taps.size(); }
-  void clear() { q[0].clear(); q[1].clear(); taps.clear(); }
+  size_t size() const { return q.size() + taps.size(); }
+  void clear() { q.clear(); taps.clear(); }
 };
 static std::mutex g_tn_queue_mutex;
 static TnQueue g_tn_queue[MR_MAX_DEVICES];
@@ -475,45 +477,198 @@ static TnQueue* tn_queue_of_current_device() {     // (call with g_tn_queue_mute
   return dev >= 0 ? &g_tn_queue[dev] : nullptr;
 }
 
-template <int BMODE>
-static int launch_tn_group(const TnRecord* recs, int n, hipStream_t stream) {
+// The makespan model of the 128x128 TN kernel, in units of one dense p-step of a workgroup that has its CU to itself
+// (~0.95 us on MI355X; tools/microbench_tn_dense.py): launch, address prologue and the 64 KB atomic epilogue cost a workgroup
+// TN_FIXED_STEPS of them whatever it reduces, two workgroups per CU run their p-steps TN_SHARE times slower than one.
+constexpr double TN_FIXED_STEPS = 20.0, TN_SHARE = 1.3;
+// One p-step of a row-table conv problem (BMODE 2) against a dense one.  Source: profiles/r08_crnn_step_sequence_grouped.txt --
+// the launch of conv1 + conv6 alone (66 p-steps per workgroup, 448 workgroups) takes 108 us = 87.4 units of TN_SHARE * 0.95 us,
+// i.e. (87.4 - 20) / 66 = 1.02 dense steps per conv step; the dense launches of the same sequence (52 us at 22 steps, 64 us at
+// 33) give 1.0 by construction.  The gather costs address work, not time, at these depths: the row table is one 8-byte load per
+// row, issued a step ahead.
+constexpr double TN_CONV_STEP = 1.02;
+static double tn_step_cost(int mode) { return mode == 0 ? 1.0 : TN_CONV_STEP; }
+
+// modelled cost of ONE launch: problem i runs tiles[i] * splits[i] workgroups (its range padded to a multiple of 8) of
+// ceil(steps[i] / splits[i]) p-steps; rounds * (longest workgroup + fixed cost) over 2 * cus workgroup slots
+static double tn_launch_cost(int cus, int n, const int* tiles, const int* steps, const int* modes, const int* splits) {
+  long long blocks = 0;
+  double longest = 0.0;
+  for (int i = 0; i < n; ++i) {
+    blocks += (long long)cdiv(tiles[i] * splits[i], 8) * 8;
+    longest = std::max(longest, cdiv(steps[i], splits[i]) * tn_step_cost(modes[i]));
+  }
+  const long long rounds = (blocks + 2 * cus - 1) / (2 * cus);
+  return (double)rounds * (longest + TN_FIXED_STEPS) * (blocks > cus ? TN_SHARE : 1.0);
+}
+
+// split count of a problem launched alone (launch_tn_now): workgroups run 2 per CU and are latency-bound, so time ~
+// rounds(blocks / 2*CUs) * (p-steps per split + epilogue)
+static int tn_single_splits(int bmode, int tiles, int total_steps, int cus) {
+  int splits = 1;
+  double best = 1e300;
+  for (int s = 1; s <= 1024 && 2 * s <= total_steps + 1; ++s) {
+    const long long blocks = (long long)tiles * s;
+    const long long rounds = (blocks + 2 * cus - 1) / (2 * cus);
+    // the epilogue is a full 128x128 tile of f32 atomics (~8 p-steps of time)
+    double cost = (double)rounds * (cdiv(total_steps, s) + 8.0);
+    // dense GEMMs (LSTM / Linear weight gradients: 4..64 output tiles) were measured per split count
+    // (tools/microbench_tn_dense.py): launch + prologue + atomic epilogue cost ~20 p-steps, not 8, and a workgroup
+    // that shares its CU with a second one runs its p-steps ~1.3x slower -- so "one workgroup per CU" wins over
+    // "two per CU with half the steps" (dW_hh: 21 us at 16 splits vs 32 us at the 32 the old model chose)
+    if (bmode == 0 || g_tn_model == 1)
+      cost = (double)rounds * (cdiv(total_steps, s) + TN_FIXED_STEPS) * (blocks > cus ? TN_SHARE : 1.0);
+    if (cost < best) { best = cost; splits = s; }
+  }
+  return splits;
+}
+
+// The splits of the problems of ONE grouped launch (2 <= n <= TN_GROUP_MAX).  Every bound T on a workgroup's loop time (in
+// dense steps) is tried: problem i gets the fewest splits that keep its workgroups within T, i.e. floor(T / step cost of its
+// mode) p-steps each, and the launch costs rounds * (its longest workgroup + fixed cost).  Ties go to the larger T (fewer
+// splits: fewer atomics).  Returns the modelled cost.
+static double tn_plan_launch(int cus, int n, const int* tiles, const int* steps, const int* modes, int* splits) {
+  double tmax = 1.0;
+  for (int i = 0; i < n; ++i) tmax = std::max(tmax, steps[i] * tn_step_cost(modes[i]));
+  double best = 1e300;
+  int cand[TN_GROUP_MAX];
+  for (int T = (int)std::ceil(tmax); T >= 1; --T) {
+    long long blocks = 0;
+    for (int i = 0; i < n; ++i) {
+      const int L = std::min(steps[i], std::max(1, (int)(T / tn_step_cost(modes[i]))));
+      cand[i] = cdiv(steps[i], L);
+      blocks += (long long)cdiv(tiles[i] * cand[i], 8) * 8;
+    }
+    if (blocks > 16ll * cus && best < 1e300) break;   // beyond 8 rounds the fixed costs only add up
+    const double cost = tn_launch_cost(cus, n, tiles, steps, modes, cand);
+    if (cost < best) { best = cost; std::copy(cand, cand + n, splits); }
+  }
+  return best;
+}
+
+// The plan of mr_tn_flush for n recorded TN problems in recording order (tiles[i] 128x128 output tiles, steps[i] 64-row
+// p-steps, modes[i] 0 / 2).  The records are cut into ceil(n / TN_GROUP_MAX) runs of equal length; a run is one launch, or one
+// launch per mode where the model prices that lower.  launch[i] = the launch of problem i, numbered by first problem;
+// splits[i]; begin[i] = the first workgroup of its range inside that launch (a multiple of 8; the ranges follow each other by
+// falling workgroup time, so that the longest workgroups are dispatched first).  A problem alone in its launch runs through
+// launch_tn_now with the splits of tn_single_splits.  Returns the modelled cost, < 0 on bad arguments.
+constexpr int TN_PLAN_MAX = 64;
+static double tn_group_plan(int cus, int n, const int* tiles, const int* steps, const int* modes, int* launch, int* splits,
+                            int* begin) {
+  if (n <= 0 || n > TN_PLAN_MAX || cus <= 0) return -1.0;
+  for (int i = 0; i < n; ++i)
+    if (tiles[i] <= 0 || steps[i] <= 0 || (modes[i] != 0 && modes[i] != 2)) return -1.0;
+  // a training step records the same problems every time: remember the plans
+  static std::mutex cache_mutex;
+  static std::map<std::vector<int>, std::vector<int>> cache;
+  static std::map<std::vector<int>, double> cache_cost;
+  std::vector<int> key = {cus, (int)g_tn_model};
+  key.insert(key.end(), tiles, tiles + n);
+  key.insert(key.end(), steps, steps + n);
+  key.insert(key.end(), modes, modes + n);
+  {
+    std::lock_guard<std::mutex> lock(cache_mutex);
+    const auto hit = cache.find(key);
+    if (hit != cache.end()) {
+      const std::vector<int>& v = hit->second;
+      for (int i = 0; i < n; ++i) { launch[i] = v[3 * i]; splits[i] = v[3 * i + 1]; begin[i] = v[3 * i + 2]; }
+      return cache_cost[key];
+    }
+  }
+  // splits and modelled cost of the problems idx[0..m) as ONE launch
+  auto plan_set = [&](const int* idx, int m) {
+    int t[TN_GROUP_MAX], st[TN_GROUP_MAX], md[TN_GROUP_MAX], sp[TN_GROUP_MAX];
+    for (int k = 0; k < m; ++k) { t[k] = tiles[idx[k]]; st[k] = steps[idx[k]]; md[k] = modes[idx[k]]; }
+    double c;
+    if (m == 1) {
+      sp[0] = cdiv(st[0], cdiv(st[0], tn_single_splits(md[0], t[0], st[0], cus)));
+      c = tn_launch_cost(cus, 1, t, st, md, sp);
+    } else {
+      c = tn_plan_launch(cus, m, t, st, md, sp);
+    }
+    for (int k = 0; k < m; ++k) splits[idx[k]] = sp[k];
+    return c;
+  };
+  // launch number and workgroup ranges of a planned set: by falling workgroup time
+  auto place = [&](const int* idx, int m, int l) {
+    int order[TN_GROUP_MAX];
+    std::copy(idx, idx + m, order);
+    std::stable_sort(order, order + m, [&](int x, int y) {
+      return cdiv(steps[x], splits[x]) * tn_step_cost(modes[x]) > cdiv(steps[y], splits[y]) * tn_step_cost(modes[y]);
+    });
+    int end = 0;
+    for (int k = 0; k < m; ++k) {
+      launch[order[k]] = l;
+      begin[order[k]] = end;
+      end += cdiv(tiles[order[k]] * splits[order[k]], 8) * 8;
+    }
+  };
+  const int chunks = cdiv(n, TN_GROUP_MAX), per = cdiv(n, chunks);
+  double total = 0.0;
+  int l = 0;
+  for (int c = 0; c < chunks; ++c) {
+    const int i0 = c * per, m = std::min(per, n - i0);
+    int all[TN_GROUP_MAX], by_mode[2][TN_GROUP_MAX], nm[2] = {0, 0};
+    for (int k = 0; k < m; ++k) {
+      all[k] = i0 + k;
+      const int w = modes[i0 + k] == 0 ? 0 : 1;
+      by_mode[w][nm[w]++] = i0 + k;
+    }
+    // Together, or each mode in a launch of its own when that is modelled cheaper: problems of very different depth (a
+    // stride-4 1x1 layer of 8192 p-steps beside Linear layers of 32) need more than one round of workgroups together, and a
+    // round is priced by its longest workgroup.  Ties go to the single launch.
+    double apart = 1e300;
+    if (nm[0] && nm[1]) apart = plan_set(by_mode[0], nm[0]) + plan_set(by_mode[1], nm[1]);
+    const double together = plan_set(all, m);
+    if (apart < together) {
+      total += plan_set(by_mode[0], nm[0]) + plan_set(by_mode[1], nm[1]);
+      const int first = modes[i0] == 0 ? 0 : 1;      // launches are numbered by their first problem
+      place(by_mode[first], nm[first], l++);
+      place(by_mode[1 - first], nm[1 - first], l++);
+    } else {
+      total += together;
+      place(all, m, l++);
+    }
+  }
+  {
+    std::lock_guard<std::mutex> lock(cache_mutex);
+    if (cache.size() >= 256) { cache.clear(); cache_cost.clear(); }
+    std::vector<int>& v = cache[key];
+    v.clear();
+    for (int i = 0; i < n; ++i) { v.push_back(launch[i]); v.push_back(splits[i]); v.push_back(begin[i]); }
+    cache_cost[key] = total;
+  }
+  return total;
+}
+
+// One grouped launch: recs[0..n) with the planned splits[] and begin[] (tn_group_plan)
+static int launch_tn_group(const TnRecord* recs, int n, const int* splits, const int* begin, hipStream_t stream) {
   const void* z = zero_page();
   if (!z) { set_error("zero page allocation failed"); return MR_ERR_LAUNCH; }
-  const int cus = num_cus();
-  int tiles[TN_GROUP_MAX], steps[TN_GROUP_MAX], max_steps = 1;
-  for (int i = 0; i < n; ++i) {
-    tiles[i] = cdiv(recs[i].a.NA, 128) * cdiv(recs[i].a.NB, 128);
-    steps[i] = cdiv(recs[i].a.P, 64);
-    if (steps[i] > max_steps) max_steps = steps[i];
-  }
-  // L = p-steps per workgroup: makespan model of launch_tn (launch + prologue + atomic epilogue ~ 20 p-steps; two
-  // workgroups per CU run their p-steps ~1.3x slower than one)
-  int bestL = max_steps;
-  double best = 1e300;
-  for (int L = 1; L <= max_steps; ++L) {
-    long long blocks = 0;
-    for (int i = 0; i < n; ++i) blocks += (long long)cdiv(tiles[i] * cdiv(steps[i], L), 8) * 8;
-    const long long rounds = (blocks + 2 * cus - 1) / (2 * cus);
-    const double cost = (double)rounds * (L + 20.0) * (blocks > cus ? 1.3 : 1.0);
-    if (cost < best) { best = cost; bestL = L; }
-  }
+  int order[TN_GROUP_MAX];
+  for (int i = 0; i < n; ++i) order[i] = i;
+  std::sort(order, order + n, [&](int x, int y) { return begin[x] < begin[y]; });
   TnGroup grp;
   int end = 0;
-  for (int i = 0; i < n; ++i) {
-    TnArgs a = recs[i].a;
-    int splits = cdiv(steps[i], bestL);
-    a.p_chunk = cdiv(cdiv(a.P, splits), 64) * 64;
-    splits = cdiv(a.P, a.p_chunk);
+  for (int k = 0; k < n; ++k) {
+    const TnRecord& r = recs[order[k]];
+    TnArgs a = r.a;
+    const int tiles = cdiv(a.NA, 128) * cdiv(a.NB, 128);
+    a.p_chunk = cdiv(cdiv(a.P, splits[order[k]]), 64) * 64;
+    const int sp = cdiv(a.P, a.p_chunk);      // no empty workgroup
     a.grp = 1; a.ws = nullptr; a.fin = 0;     // split partials of a grouped launch: f32 atomics (few splits per problem)
-    grp.a[i] = a;
-    grp.g[i] = recs[i].g;
-    grp.nblk[i] = tiles[i] * splits;
-    end += cdiv(grp.nblk[i], 8) * 8;
-    grp.blk_end[i] = end;
+    grp.a[k] = a;
+    grp.g[k] = r.g;
+    grp.mode[k] = r.mode;
+    grp.nblk[k] = tiles * sp;
+    end = begin[order[k]] + cdiv(grp.nblk[k], 8) * 8;
+    grp.blk_end[k] = end;
   }
-  for (int i = n; i < TN_GROUP_MAX; ++i) { grp.a[i] = grp.a[0]; grp.g[i] = grp.g[0]; grp.nblk[i] = 0; grp.blk_end[i] = end; }
+  for (int k = n; k < TN_GROUP_MAX; ++k) {
+    grp.a[k] = grp.a[0]; grp.g[k] = grp.g[0]; grp.mode[k] = grp.mode[0]; grp.nblk[k] = 0; grp.blk_end[k] = end;
+  }
   grp.n = n;
-  hipLaunchKernelGGL((igemm_tn_glds_grouped_kernel<BMODE>), dim3(end), dim3(256), 0, stream, grp, z);
+  hipLaunchKernelGGL(igemm_tn_glds_grouped_kernel<true>, dim3(end), dim3(256), 0, stream, grp, z);
   MR_CHECK_LAUNCH();
   return MR_OK;
 }
@@ -531,26 +686,39 @@ static int tn_flush(hipStream_t stream, bool beside) {
   {
     std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
     if (TnQueue* dq = tn_queue_of_current_device()) {
-      mine.q[0].swap(dq->q[0]);
-      mine.q[1].swap(dq->q[1]);
+      mine.q.swap(dq->q);
       mine.taps.swap(dq->taps);
     }
   }
   for (size_t i = 0; i < mine.taps.size() && rc == MR_OK; i += TAPS_PLAN_MAX)
     rc = launch_tn_taps_group(&mine.taps[i], (int)std::min<size_t>(TAPS_PLAN_MAX, mine.taps.size() - i), beside, stream);
-  for (int m = 0; m < 2 && rc == MR_OK; ++m) {
-    std::vector<TnRecord>& q = mine.q[m];
-    size_t i = 0;
-    while (i < q.size() && rc == MR_OK) {
-      const int n = (int)std::min<size_t>(TN_GROUP_MAX, q.size() - i);
-      if (n == 1)
-        rc = m == 0 ? launch_tn_now<bf16_t, 0>(q[i].a, q[i].g, beside, stream)
-                    : launch_tn_now<bf16_t, 2>(q[i].a, q[i].g, beside, stream);
-      else
-        rc = m == 0 ? launch_tn_group<0>(&q[i], n, stream) : launch_tn_group<2>(&q[i], n, stream);
-      i += n;
+  const std::vector<TnRecord>& q = mine.q;
+  for (size_t i0 = 0; i0 < q.size() && rc == MR_OK; i0 += TN_PLAN_MAX) {
+    const int n = (int)std::min<size_t>(TN_PLAN_MAX, q.size() - i0);
+    int tiles[TN_PLAN_MAX], steps[TN_PLAN_MAX], modes[TN_PLAN_MAX], launch[TN_PLAN_MAX], splits[TN_PLAN_MAX], begin[TN_PLAN_MAX];
+    for (int i = 0; i < n; ++i) {
+      const TnArgs& a = q[i0 + i].a;
+      tiles[i] = cdiv(a.NA, 128) * cdiv(a.NB, 128);
+      steps[i] = cdiv(a.P, 64);
+      modes[i] = q[i0 + i].mode;
     }
-    q.clear();
+    if (tn_group_plan(num_cus(), n, tiles, steps, modes, launch, splits, begin) < 0.0) {
+      set_error("mr_tn_flush: no plan for %d recorded problems", n);
+      rc = MR_ERR_LAUNCH;
+      break;
+    }
+    for (int l = 0; l < n && rc == MR_OK; ++l) {   // launch l = the records with launch[i] == l (none: the plan has fewer)
+      TnRecord recs[TN_GROUP_MAX];
+      int sp[TN_GROUP_MAX], bg[TN_GROUP_MAX], m = 0;
+      for (int i = 0; i < n; ++i)
+        if (launch[i] == l && m < TN_GROUP_MAX) { recs[m] = q[i0 + i]; sp[m] = splits[i]; bg[m] = begin[i]; ++m; }
+      if (m == 0) break;
+      if (m == 1)
+        rc = recs[0].mode == 0 ? launch_tn_now<bf16_t, 0>(recs[0].a, recs[0].g, beside, stream)
+                               : launch_tn_now<bf16_t, 2>(recs[0].a, recs[0].g, beside, stream);
+      else
+        rc = launch_tn_group(recs, m, sp, bg, stream);
+    }
   }
   st.on = was_on;
   return rc;
@@ -566,7 +734,7 @@ static int launch_tn(TnArgs a, const ConvGeom& g, bool beside, hipStream_t strea
         g_tn_splits == 0 && tn_fits_buffer(a, g, BMODE)) {
       std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
       if (TnQueue* dq = tn_queue_of_current_device()) {
-        dq->q[BMODE == 0 ? 0 : 1].push_back(TnRecord{a, g});
+        dq->q.push_back(TnRecord{a, g, BMODE});
         return MR_OK;
       }
     }
@@ -578,23 +746,9 @@ template <typename T, int BMODE>
 static int launch_tn_now(TnArgs a, const ConvGeom& g, bool beside, hipStream_t stream) {
   constexpr int BP = TnCfg<T>::BP;
   const int tiles = cdiv(a.NA, 128) * cdiv(a.NB, 128);
-  // split count: workgroups run 2 per CU and are latency-bound, so time ~ rounds(blocks / 2*CUs) * (p-steps per
-  // split + epilogue); the epilogue is a full 128x128 tile of f32 atomics (~8 p-steps of time)
   const int cus = num_cus();
   const int total_steps = cdiv(a.P, BP);
-  int splits = 1;
-  double best = 1e300;
-  for (int s = 1; s <= 1024 && 2 * s <= total_steps + 1; ++s) {
-    const long long blocks = (long long)tiles * s;
-    const long long rounds = (blocks + 2 * cus - 1) / (2 * cus);
-    double cost = (double)rounds * (cdiv(total_steps, s) + 8.0);
-    // dense GEMMs (LSTM / Linear weight gradients: 4..64 output tiles) were measured per split count
-    // (tools/microbench_tn_dense.py): launch + prologue + atomic epilogue cost ~20 p-steps, not 8, and a workgroup
-    // that shares its CU with a second one runs its p-steps ~1.3x slower -- so "one workgroup per CU" wins over
-    // "two per CU with half the steps" (dW_hh: 21 us at 16 splits vs 32 us at the 32 the old model chose)
-    if (BMODE == 0 || g_tn_model == 1) cost = (double)rounds * (cdiv(total_steps, s) + 20.0) * (blocks > cus ? 1.3 : 1.0);
-    if (cost < best) { best = cost; splits = s; }
-  }
+  int splits = tn_single_splits(BMODE, tiles, total_steps, cus);
   if (g_tn_splits > 0) splits = g_tn_splits < total_steps ? g_tn_splits : total_steps;
   if constexpr (sizeof(T) == 2) {
     // wide-tile variants (mode 1: 256x256, mode 2: 128x256; one 8-wave workgroup per CU): they cut the L2 -> LDS
@@ -776,6 +930,32 @@ int mr_tn_taps_plan(int cus, int slabs, int n, const int* tiles, const int* chun
   return launches;
 }
 
+// host only: the launch plan of mr_tn_flush for n recorded problems of the 128x128 TN kernel (tn_group_plan)
+int mr_tn_group_plan(int cus, int n, const int* tiles, const int* steps, const int* modes, int* launch, int* splits, int* begin,
+                     double* cost) {
+  const double c = tiles && steps && modes && launch && splits && begin
+                       ? tn_group_plan(cus, n, tiles, steps, modes, launch, splits, begin) : -1.0;
+  if (c < 0.0) {
+    set_error("mr_tn_group_plan: need 1 <= n <= %d, cus > 0, tiles > 0, steps > 0, modes 0 / 2 and non-null arrays", TN_PLAN_MAX);
+    return -1;
+  }
+  if (cost) *cost = c;
+  return *std::max_element(launch, launch + n) + 1;
+}
+
+// host only: the modelled cost of ONE launch of the grouped TN kernel with the given splits (any cut, not only the planner's)
+int mr_tn_group_cost(int cus, int n, const int* tiles, const int* steps, const int* modes, const int* splits, double* cost) {
+  bool ok = cus > 0 && n >= 1 && n <= TN_PLAN_MAX && tiles && steps && modes && splits && cost;
+  for (int i = 0; ok && i < n; ++i)
+    ok = tiles[i] > 0 && steps[i] > 0 && splits[i] > 0 && splits[i] <= steps[i] && (modes[i] == 0 || modes[i] == 2);
+  MR_CHECK_ARG(ok, "mr_tn_group_cost: need 1 <= n <= %d, cus > 0, tiles > 0, 1 <= splits <= steps, modes 0 / 2", TN_PLAN_MAX);
+  *cost = tn_launch_cost(cus, n, tiles, steps, modes, splits);
+  return MR_OK;
+}
+
+// host only: problems per launch of mr_tn_flush -- kind 0: the 128x128 TN GEMM kernel, kind 1: the all-taps kernel
+int mr_tn_capacity(int kind) { return kind == 0 ? TN_GROUP_MAX : kind == 1 ? TAPS_PLAN_MAX : 0; }
+
 // Which NT tile (BM*1000 + BN) a problem of M rows x N columns is dispatched to (profiling / bench labels).
 int mr_nt_tile_code(int M, int N) {
   const TileChoice t = nt_tile(M, N);
@@ -835,6 +1015,12 @@ int mr_tn_pending(void) {
   std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
   const TnQueue* dq = tn_queue_of_current_device();
   return dq ? (int)dq->size() : 0;
+}
+// the same per kernel: kind 0 = the 128x128 TN GEMM kernel, kind 1 = the all-taps kernel (cf. mr_tn_capacity)
+int mr_tn_pending_of(int kind) {
+  std::lock_guard<std::mutex> lock(g_tn_queue_mutex);
+  const TnQueue* dq = tn_queue_of_current_device();
+  return !dq ? 0 : kind == 0 ? (int)dq->q.size() : kind == 1 ? (int)dq->taps.size() : 0;
 }
 // Drops the current device's recorded problems WITHOUT launching them (a backward pass that raised: its records point at operands
 // the caller is about to release) and switches recording off for the calling thread; returns how many were dropped.  Host only.

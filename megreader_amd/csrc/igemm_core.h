@@ -2282,22 +2282,29 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_glds_kernel(TnArgs a, ConvGeo
   tn_glds_body<BMODE, BUF, ABL>(a, g, zero, (int)blockIdx.x, (int)gridDim.x, smem);
 }
 
-// Grouped launch: up to TN_GROUP_MAX independent weight-gradient problems of one BMODE in ONE launch (mr_tn_defer /
+// Grouped launch: up to TN_GROUP_MAX independent weight-gradient problems (BMODE 0 and 2 mixed) in ONE launch (mr_tn_defer /
 // mr_tn_flush, gemm_conv.hip).  Why: the weight gradients of the small layers (ResNet 1x1 / strided layers at batch 32, the
 // LSTM / Linear layers of the CRNN) are launches of 16..64 output tiles whose P loop had to be cut into 8..32 splits to fill
 // the chip -- a 2..8-step main loop between an address prologue and a 64 KB atomic epilogue per workgroup.  Several such
 // problems side by side fill the chip with 1/8 of the splits each: longer loops, 1/8 of the atomics.  Problem i owns the
 // workgroups [blk_end[i-1], blk_end[i]) (each range padded to a multiple of 8: blockIdx & 7 stays the XCD inside a range; the
 // pad workgroups leave at once); the struct travels by value in the kernarg segment, indexed with a uniform index.
-constexpr int TN_GROUP_MAX = 12;
+// Problems of BOTH operand modes share a launch: mode[i] (0: dense B, 2: conv B through a row table) is uniform per workgroup,
+// so the kernel branches once, after it has found its problem, into the body of that mode.  The two bodies are separate
+// straight-line regions with nothing live across the branch: the kernel's register budget is the larger of the two
+// (DESIGN.md section 4a has the numbers), LDS and occupancy are those of either body alone.
+constexpr int TN_GROUP_MAX = 16;
 struct TnGroup {
   TnArgs a[TN_GROUP_MAX];
   ConvGeom g[TN_GROUP_MAX];
   int blk_end[TN_GROUP_MAX];   // exclusive end of problem i's workgroup range (multiple of 8)
   int nblk[TN_GROUP_MAX];      // tiles * splits of problem i (<= the range's length)
+  int mode[TN_GROUP_MAX];      // BMODE of problem i: 0 or 2
   int n;
 };
-template <int BMODE>
+// the struct is the kernel's first argument, passed by value: it and the zero-page pointer must fit the 4 KB kernarg segment
+static_assert(sizeof(TnGroup) + sizeof(void*) <= 4096, "TnGroup does not fit the kernarg segment: lower TN_GROUP_MAX");
+template <bool BUF>   // (a template so that only the file that launches it instantiates it)
 __global__ __launch_bounds__(256, 2) void igemm_tn_glds_grouped_kernel(TnGroup grp, const void* zero) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[4 * 64 * 256];
   const int b = (int)blockIdx.x;
@@ -2306,7 +2313,10 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_glds_grouped_kernel(TnGroup g
   const int b0 = i > 0 ? grp.blk_end[i - 1] : 0;
   const int bid = b - b0;
   if (bid >= grp.nblk[i]) return;
-  tn_glds_body<BMODE, true, 0>(grp.a[i], grp.g[i], zero, bid, grp.nblk[i], smem);
+  if (grp.mode[i] == 0)
+    tn_glds_body<0, BUF, 0>(grp.a[i], grp.g[i], zero, bid, grp.nblk[i], smem);
+  else
+    tn_glds_body<2, BUF, 0>(grp.a[i], grp.g[i], zero, bid, grp.nblk[i], smem);
 }
 
 // C += sum over the splits of a tile's slabs (TnArgs.fin == 2).  One workgroup per (tile, accumulator tile k = i*4 + j); thread tid

@@ -31,7 +31,7 @@ int launch_tn_taps(const TapsProblem& p, int splits_override, hipStream_t stream
 
 // ---- recorded problems (mr_tn_defer / mr_tn_flush): several problems per launch, so that the workgroup slots of the chip are
 // filled by problems, not by splits, and the fixed price of a workgroup is paid once per slot instead of once per layer.
-constexpr int TAPS_PLAN_MAX = 12;   // problems per plan (= TN_GROUP_MAX)
+constexpr int TAPS_PLAN_MAX = 12;   // problems per plan
 int taps_build_table(const TapsProblem& p, hipStream_t stream);   // what p.build != 0 does, for a problem that is recorded
 // Launches p[0..n) (tables built, n <= TAPS_PLAN_MAX) as taps_plan partitions them; a problem alone in its launch goes through
 // launch_tn_taps.  p[i].build / p[i].beside are ignored: `beside` is the flush's.

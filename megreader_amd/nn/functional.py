@@ -1204,9 +1204,12 @@ class BiLSTMFn(Function):
 
         if _wgrad(lstm_grouped, use_sinks and dtype == torch.bfloat16 and T > 1, (dgates, x, out), list(ctx.params),
                   immediate=lstm_immediate):
-            # one launch for the layer (and the Linear layers recorded behind it); a data-parallel wrapper wants the
-            # gradients as they complete, and the next layer's recurrence is a latency chain that leaves the CUs idle anyway
-            _TnDefer.flush(final=False)
+            # A data-parallel wrapper wants the gradients as they complete: with one listening (in-graph capture included) the
+            # layer and the Linear layers recorded behind it flush here, as one launch.  Otherwise the problems wait for the
+            # end-of-backward flush with everything else (one grouped launch for the whole step): dgates, x and out stay alive
+            # in _TnDefer.keep until then.
+            if _TnDefer.listening(ctx.params):
+                _TnDefer.flush(final=False)
         elif use_sinks:
             for p in ctx.params:
                 notify_grad_ready(p)

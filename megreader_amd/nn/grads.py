@@ -1,6 +1,7 @@
 """Gradient plumbing of the autograd layer; nn/functional.py re-exports every name here.  The gradient-sink protocol of the fused
 optimizers (grad_sink, notify_grad_ready, GradDest), the pre-zeroed scratch arena and batched fills shared with `zero_grad()`, and
 the deferred, grouped weight-gradient launches (_TnDefer, _wgrad).  All state lives on the classes."""
+import contextlib
 import ctypes
 import os
 
@@ -145,14 +146,19 @@ class _TnDefer(object):
     backward pass reads a weight gradient that goes to a gradient sink, so the small weight-gradient GEMMs (ResNet 1x1 / strided
     layers, LSTM / Linear layers) and the 3x3 layers of the all-taps kernel (conv2..conv5 of the CRNN, the ResNet bottlenecks)
     are recorded while backward runs and launched several problems per launch: at the latest from
-    an autograd-engine callback at the end of the backward pass, earlier whenever MAX problems are waiting.  The operands of the
-    recorded problems are kept alive here until the flush; parameters are reported to data-parallel wrappers
-    (notify_grad_ready) only after the launch that completes their gradient.
+    an autograd-engine callback at the end of the backward pass, earlier as soon as one of the two kernels has a full launch
+    waiting (mr_tn_capacity: 16 problems of the 128x128 TN GEMM kernel, dense and conv together, or 12 of the all-taps kernel),
+    so that a deep network does not keep every layer's operands until the end.  The CRNN step records 13 + 4 and flushes once.
+    The operands of the recorded problems are kept alive here until the flush; parameters are reported to data-parallel
+    wrappers (notify_grad_ready) only after the launch that completes their gradient.  A node may flush earlier itself when
+    such a wrapper listens to its parameters (listening(); BiLSTMFn.backward): without one nothing reads a gradient before the
+    optimizer, and on the single backward stream an early flush overlaps nothing -- it only costs a launch.
+    The flush runs under the device of the kept operands: the end-of-backward callback runs on the thread that called
+    backward(), whose current device may be another one than the model's, and the library's queue is per device.
     MEGREADER_TN_DEFER=0 (or mr_tuning.tn_defer = 0): every launch immediate (A/B).
     Every launch stays on the backward stream: forking weight-gradient launches onto side streams was measured slower in
     every step (CHANGELOG.md, "Retired: the side-stream weight-gradient switches")."""
     enabled = os.environ.get("MEGREADER_TN_DEFER", "1") != "0"
-    MAX = 12
     keep = []
     notify = []
     queued = False
@@ -217,20 +223,26 @@ class _TnDefer(object):
         ready: the flush does); False when the library launched them at once (f32, mr_tuning.tn_defer = 0 or tn_splits != 0)."""
         lib = load()
         lib.mr_tn_defer(0)
-        n = lib.mr_tn_pending()
-        if n == _TnDefer.mark:
+        if lib.mr_tn_pending() == _TnDefer.mark:
             return False
         _TnDefer.keep.extend(t for t in tensors if t is not None)
         _TnDefer.notify.extend(params)
-        if n >= _TnDefer.MAX:
+        if any(lib.mr_tn_pending_of(kind) >= lib.mr_tn_capacity(kind) for kind in (0, 1)):
             _TnDefer.flush(final=False)
         return True
 
     @staticmethod
+    def listening(params):
+        """True when a data-parallel wrapper waits for the gradient of one of `params` (its hooks fire from notify_grad_ready)."""
+        return any(getattr(p, "_mr_grad_ready_hooks", None) for p in params)
+
+    @staticmethod
     def flush(final=True):
         """Launch what is recorded and report its parameters ready; final: the end-of-backward callback of the graph task."""
-        if load().mr_tn_pending():
-            call("mr_tn_flush")
+        dev = next((t.device for t in _TnDefer.keep if t.is_cuda), None)
+        with (torch.cuda.device(dev) if dev is not None else contextlib.nullcontext()):     # nothing kept: nothing recorded
+            if load().mr_tn_pending():
+                call("mr_tn_flush")
         ready, _TnDefer.notify = _TnDefer.notify, []
         del _TnDefer.keep[:]
         if final:
