@@ -1112,6 +1112,51 @@ int mr_ctc_beam_search(int dtype, const void* pred, long long sn, long long sc, 
                        int log_probs, int blank, int unknown, int beam, int nbest, int top_classes,
                        int* ids, int* lengths, float* scores, int* count, void* ws, long long ws_bytes, hipStream_t stream);
 
+/* ---- CTC prefix beam search with a character n-gram language model (csrc/ctc_beam.hip): Hannun et al., Algorithm 1, WITH the
+ * language model.  The strings are ranked by log p_ctc(string | y) + alpha * log p_lm(string) + beta * |string|, so that a reader
+ * without a closed lexicon prefers "the" to "tbe".  Posterior, parameters, hypotheses, workspace (mr_ctc_beam_ws_bytes) and the
+ * two launches are those of mr_ctc_beam_search; what is added:
+ *   Model.  A backoff n-gram model (ARPA's) over the class ids, of order 1..MR_NGRAM_ORDER_MAX, as a finite automaton with `states`
+ *     states: one per listed context shorter than the order, state 0 the empty context.  For a state s and a class c
+ *       g(c | s) = arc_lp(s, c) if the arc (s, c) is listed, else bow[s] + g(c | backoff[s]);  no arc at state 0: -inf
+ *     accumulated in f32 in that order: acc = 0, acc += bow[s] for every state backed off through, g = acc + arc_lp.  The state
+ *     after c is arc_next of the arc that was found: the longest suffix of context + c that is a state.
+ *     Arcs: an open-addressing table of `slots` entries in three arrays, lm_keys u64 (key (s << 32) | (c + 1); 0 = empty),
+ *     lm_arc_lp f32, lm_arc_next i32.  Hash and probing, in 32-bit unsigned arithmetic (host and kernel follow this one rule):
+ *       h = (s * 0x9E3779B1) ^ ((c + 1) * 0x85EBCA6B);  h = (h ^ (h >> 15)) % slots;  then h, h + 1, .. (wrapping at slots)
+ *     An arc lies within the first max_probe slots of its sequence with no empty slot before it (max_probe = the longest probe
+ *     sequence of the table as built, >= 1): a lookup that meets an empty slot, or has read max_probe slots, is a miss.
+ *     Per state: lm_bow f32, lm_backoff i32 (the state of the context without its first symbol, -1 for state 0), lm_end_lp f32
+ *     (g(</s> | s) backed off to the end on the host; 0 for a model without </s>).  The caller guarantees: every lm_arc_next and
+ *     every lm_backoff but that of state 0 lies in [0, states), backoff chains reach state 0 within order - 1 steps, state 0 lists
+ *     every class that may be a symbol (neither blank nor `unknown`), all values are finite.  (megreader_amd/ops/language_model.py
+ *     builds and checks such an image.)  The kernel stops a chain at a state outside [0, states) as at a miss in state 0.
+ *   Rule.  Every hypothesis also carries a model state and an f32 sum lm(p); the empty prefix starts with (start_state, 0).
+ *       lm(p + c) = lm(p) + (alpha * g(c | state(p)) + beta),  state(p + c) = the state after c
+ *     every operation rounded to f32 on its own (no fused multiply-add).  Both are functions of the string alone, so an extension
+ *     that merges into a stay (step 4) agrees with it and a prefix that re-enters the beam gets the same values back.  pb, pnb and
+ *     total stay the pure CTC masses: steps 1 to 4 are those of mr_ctc_beam_search bit for bit, and step 1 still picks the
+ *     column's symbols by lp alone.  An extension whose g is -inf is dropped.
+ *       5. Keep.  The B prefixes with the greatest total + lm survive (one f32 addition; -inf is dropped).
+ *     After the last column, with end != 0, lm(p) += alpha * lm_end_lp[state(p)] for every survivor, and the K greatest by
+ *     total + lm are returned in descending order.
+ *   Outputs.  ids, lengths, count as mr_ctc_beam_search; scores f32 [N, K] = total + lm, the ranked value; ctc_scores f32 [N, K] =
+ *     total, still a lower bound of log p(string | y) and exact when nothing is pruned; lm_scores f32 [N, K] = lm.  Slots past
+ *     count get -inf in all three.  With alpha == 0, beta == 0 and end == 0 ids, lengths, count and ctc_scores are those of
+ *     mr_ctc_beam_search and lm_scores is 0.  Deterministic and row-independent as mr_ctc_beam_search; the model arrays are only read.
+ * One lookup per extension (p, j), by the lanes that build the extension keys: at most `order` levels of at most max_probe probes.
+ * N == 0 returns MR_OK without a launch.  MR_ERR_ARG, nothing written: everything mr_ctc_beam_search refuses; a null model
+ * pointer; order outside 1..MR_NGRAM_ORDER_MAX; states < 1; slots < 1; max_probe < 1; start_state outside [0, states); alpha or
+ * beta not finite.  MR_ERR_DTYPE: another dtype code. */
+#define MR_NGRAM_ORDER_MAX 8        /* symbols per n-gram */
+int mr_ctc_beam_search_lm(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T,
+                          int log_probs, int blank, int unknown, int beam, int nbest, int top_classes,
+                          const unsigned long long* lm_keys, const float* lm_arc_lp, const int* lm_arc_next,
+                          const float* lm_bow, const int* lm_backoff, const float* lm_end_lp, int states, int slots,
+                          int max_probe, int start_state, int order, float alpha, float beta, int end,
+                          int* ids, int* lengths, float* scores, float* ctc_scores, float* lm_scores, int* count,
+                          void* ws, long long ws_bytes, hipStream_t stream);
+
 /* ---- Forced CTC alignment (csrc/ctc_align.hip): WHERE the symbols of a given string lie in a CTC posterior and how probable each
  * is there -- the single most probable alignment of the string (Viterbi), where mr_lexicon_transcribe sums over all of them.  It
  * answers what neither a lexicon word nor a beam hypothesis can: which columns carry which character (character boxes, per-

@@ -20,6 +20,9 @@
 // and for its last symbol among the column's, adds that extension's mass to its own pnb' and strikes the extension's key out.
 // Only the <= B survivors that are new are looked up or created (64-bit compare-and-swap, probes read past the L1); node ids depend
 // on the probing order and never reach an output.  The strings are unwound once at the end.
+//   ctc_beam_lm_kernel        the row kernel WITH the language model (mr_ctc_beam_search_lm): a sibling, so that the one above stays
+//                             the code it was.  Same columns, same trie; a model state and an f32 sum per beam entry, the candidate
+//                             keys order total + lm, the model is a read-only automaton looked up once per extension.
 #include <limits.h>
 #include "device.h"
 #include "ctc_posterior.h"
@@ -228,6 +231,223 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const PT* pred, long long 
   }
 }
 
+// ---- with a character n-gram model (mr_ctc_beam_search_lm): the same search, ranked by total + lm ----
+
+// the model as the header lays it out: a finite automaton, its arcs in an open-addressing table keyed by (state, symbol)
+struct CtcbModel {
+  const u64* keys;
+  const float* arc_lp;
+  const int* arc_next;
+  const float* bow;
+  const int* backoff;
+  const float* end_lp;
+  int states;
+  unsigned slots;
+  int max_probe, start_state, order;
+  float alpha, beta;
+  int end;
+};
+
+// g(sym | state) and the state after sym: at most `order` levels (the state, then its backoff chain) of at most max_probe
+// probes each; the bows are added first, then the arc's value.  -inf: no arc down to state 0.  Plain loads: the model is read only.
+// A level is one memory round trip where its first two slots decide it (a table at most half full: nearly always): the two keys,
+// the first slot's value and next state, and the state's bow and backoff are loaded together, before any of them is looked at,
+// so neither a hit nor a miss waits for a second load behind the first.
+__device__ __forceinline__ float ctcb_lm_step(const CtcbModel& lm, int state, int sym, int& next) {
+  float acc = 0.f;
+  next = 0;
+  for (int level = 0; level < lm.order; ++level) {
+    if ((unsigned)state >= (unsigned)lm.states) break;
+    const u64 entry = ((u64)(unsigned)state << 32) | (u64)(unsigned)(sym + 1);
+    unsigned h = ((unsigned)state * 0x9E3779B1u) ^ ((unsigned)(sym + 1) * 0x85EBCA6Bu);
+    h = (h ^ (h >> 15)) % lm.slots;
+    const unsigned h1 = h + 1 == lm.slots ? 0u : h + 1;
+    const u64 k0 = lm.keys[h], k1 = lm.keys[h1];
+    const float v0 = lm.arc_lp[h], bow = lm.bow[state];
+    const int n0 = lm.arc_next[h], backoff = lm.backoff[state];   // -1 behind state 0: the range check above ends the chain
+    if (k0 == entry) {
+      next = n0;
+      return __fadd_rn(acc, v0);
+    }
+    if (k0 != 0ull && lm.max_probe > 1) {
+      h = h1;
+      u64 cur = k1;
+      for (int probe = 1;;) {
+        if (cur == entry) {
+          next = lm.arc_next[h];
+          return __fadd_rn(acc, lm.arc_lp[h]);
+        }
+        if (cur == 0ull || ++probe >= lm.max_probe) break;
+        h = h + 1 == lm.slots ? 0u : h + 1;
+        cur = lm.keys[h];
+      }
+    }
+    acc = __fadd_rn(acc, bow);
+    state = backoff;
+  }
+  return CTC_NEG_INF;
+}
+
+// lm(p + c) from lm(p) and g: every operation rounded on its own
+__device__ __forceinline__ float ctcb_lm_add(const CtcbModel& lm, float sum, float g) {
+  return __fadd_rn(sum, __fadd_rn(__fmul_rn(lm.alpha, g), lm.beta));
+}
+
+// a total as mr_ctc_beam_search takes it back out of a key: -0 is +0
+__device__ __forceinline__ float ctcb_plus_zero(float v) { return v == 0.f ? 0.f : v; }
+
+// ctc_beam_kernel with two more registers per beam entry, the model state and the f32 sum lm, mirrored in LDS like the others.
+// The masses are computed exactly as there; only the candidate keys order total + lm, so a survivor's total is taken again from
+// its masses (the same operations, the same bits) where ctc_beam_kernel reads it back out of the key.  The lanes that build the
+// extension keys look the model up, one lookup per (p, j), independent of each other; the <= B lanes whose survivor is an
+// extension repeat theirs for the new state instead of keeping 4 096 states in LDS.
+template <typename PT>
+__global__ __launch_bounds__(64) void ctc_beam_lm_kernel(const PT* pred, long long sn, long long sc, long long st, int C, int T,
+                                                         int log_probs, int blank, int B, int K, int Kc, const int* sym_id,
+                                                         const float* sym_lp, u64* tables, unsigned slots, CtcbModel lm, int* ids,
+                                                         int* lengths, float* scores, float* ctc_scores, float* lm_scores,
+                                                         int* count) {
+  __shared__ u64 keys[MR_CTC_BEAM_MAX + MR_CTC_BEAM_MAX * MR_CTC_BEAM_TOP_MAX];
+  __shared__ float b_pb[64], b_pnb[64], b_tot[64], b_lm[64], s_pb[64], s_pnb[64], c_lp[64];
+  __shared__ int b_last[64], b_len[64], b_node[64], b_par[64], b_state[64], c_id[64];
+  const int lane = threadIdx.x, n = blockIdx.x;
+  u64* tab = tables + (long long)n * slots;
+  for (unsigned i = lane; i < slots; i += 64) tab[i] = 0ull;
+  float pb = lane == 0 ? 0.f : CTC_NEG_INF, pnb = CTC_NEG_INF, tot = pb, lms = 0.f;
+  int last = -1, len = 0, node = 0, par = -1, nb = 1, state = lm.start_state;
+  __syncthreads();
+  for (int t = 0; t < T; ++t) {
+    const PT* col = pred + (long long)n * sn + (long long)t * st;
+    const long long list = ((long long)n * T + t) * Kc;
+    const int cid = lane < Kc ? sym_id[list + lane] : -1;
+    const float clp = lane < Kc ? sym_lp[list + lane] : CTC_NEG_INF;
+    const float lpb = ctc_lp_at(col, sc, blank, log_probs != 0);
+    const int kc = __popcll(__ballot(cid >= 0));
+    b_pb[lane] = pb; b_pnb[lane] = pnb; b_tot[lane] = tot; b_lm[lane] = lms;
+    b_last[lane] = last; b_len[lane] = len; b_node[lane] = node; b_par[lane] = par; b_state[lane] = state;
+    c_id[lane] = cid; c_lp[lane] = clp;
+    __syncthreads();
+    // stay: the masses of ctc_beam_kernel; the string is the same one, so are its state and lm
+    u64 key = 0ull;
+    int merged = -1;
+    if (lane < nb) {
+      const float npb = tot + lpb;
+      float npnb = CTC_NEG_INF;
+      if (len > 0) {
+        int jl = -1;
+        for (int j = 0; j < kc; ++j)
+          if (c_id[j] == last) jl = j;
+        npnb = pnb + (jl >= 0 ? c_lp[jl] : ctc_lp_at(col, sc, last, log_probs != 0));
+        if (jl >= 0) {
+          int p = -1;
+          for (int i = 0; i < nb; ++i)
+            if (b_node[i] == par) p = i;
+          if (p >= 0) {
+            const float from = (b_len[p] > 0 && b_last[p] == last) ? b_pb[p] : b_tot[p];
+            npnb = ctc_lse2(npnb, from + c_lp[jl]);
+            merged = p * kc + jl;
+          }
+        }
+      }
+      s_pb[lane] = npb; s_pnb[lane] = npnb;
+      key = ctc_key(__fadd_rn(ctc_lse2(npb, npnb), lms), (unsigned)lane, CTCB_MERGE_ZEROS);
+    }
+    keys[lane] = key;
+    const int ne = nb * kc;
+    for (int e = lane; e < ne; e += 64) {
+      const int p = e / kc, j = e - p * kc;
+      const float from = (b_len[p] > 0 && b_last[p] == c_id[j]) ? b_pb[p] : b_tot[p];
+      int next;
+      const float g = ctcb_lm_step(lm, b_state[p], c_id[j], next);
+      const float ranked = g > CTC_NEG_INF ? __fadd_rn(from + c_lp[j], ctcb_lm_add(lm, b_lm[p], g)) : CTC_NEG_INF;
+      keys[64 + e] = ctc_key(ranked, (unsigned)(64 + e), CTCB_MERGE_ZEROS);
+    }
+    __syncthreads();
+    if (merged >= 0) keys[64 + merged] = 0ull;
+    __syncthreads();
+    u64 mine = keys[lane];
+    for (int e = lane; e < ne; e += 64) mine = keys[64 + e] > mine ? keys[64 + e] : mine;
+    u64 got = 0ull;
+    int kept = 0;
+    for (int r = 0; r < B; ++r) {
+      const u64 w = ctc_wave_max(mine);
+      if (w == 0ull) break;
+      if (lane == r) got = w;
+      ++kept;
+      if (mine == w) {
+        u64 m = keys[lane] < w ? keys[lane] : 0ull;
+        for (int e = lane; e < ne; e += 64) {
+          const u64 k = keys[64 + e];
+          if (k < w && k > m) m = k;
+        }
+        mine = m;
+      }
+    }
+    nb = kept;
+    if (lane < nb) {
+      const int idx = (int)(0xffffffffu - (unsigned)(got & 0xffffffffull));
+      if (idx < 64) {
+        pb = s_pb[idx]; pnb = s_pnb[idx]; last = b_last[idx]; len = b_len[idx]; node = b_node[idx]; par = b_par[idx];
+        state = b_state[idx]; lms = b_lm[idx];
+        tot = ctcb_plus_zero(ctc_lse2(pb, pnb));
+      } else {
+        const int e = idx - 64, p = e / kc, j = e - p * kc;
+        const float from = (b_len[p] > 0 && b_last[p] == c_id[j]) ? b_pb[p] : b_tot[p];
+        tot = ctcb_plus_zero(from + c_lp[j]);
+        pb = CTC_NEG_INF; pnb = tot; last = c_id[j]; len = b_len[p] + 1; par = b_node[p];
+        lms = ctcb_lm_add(lm, b_lm[p], ctcb_lm_step(lm, b_state[p], last, state));
+        node = ctcb_find_or_create(tab, slots, par, last);
+      }
+    } else {
+      pb = pnb = tot = CTC_NEG_INF; last = -1; len = 0; node = 0; par = -1; state = 0; lms = 0.f;
+    }
+    __syncthreads();
+  }
+  // the end of the string, then the survivors' ranks by total + lm: at most 64 keys, one per lane, each lane counts the greater
+  if (lm.end != 0 && lane < nb && (unsigned)state < (unsigned)lm.states)
+    lms = __fadd_rn(lms, __fmul_rn(lm.alpha, lm.end_lp[state]));
+  const float ranked = lane < nb ? __fadd_rn(tot, lms) : CTC_NEG_INF;
+  keys[lane] = ctc_key(ranked, (unsigned)lane, CTCB_MERGE_ZEROS);
+  __syncthreads();
+  int rank = 0, alive = 0;
+  for (int i = 0; i < 64; ++i) {
+    rank += keys[i] > keys[lane] ? 1 : 0;
+    alive += keys[i] != 0ull ? 1 : 0;
+  }
+  const bool have = keys[lane] != 0ull && rank < K;
+  __syncthreads();   // b_len is read as the ranks' lengths below, the keys are done with
+  if (lane < K) b_len[lane] = 0;
+  __syncthreads();
+  if (have) b_len[rank] = len;
+  if (lane < K && lane >= min(alive, K)) {
+    lengths[(long long)n * K + lane] = 0;
+    scores[(long long)n * K + lane] = CTC_NEG_INF;
+    ctc_scores[(long long)n * K + lane] = CTC_NEG_INF;
+    lm_scores[(long long)n * K + lane] = CTC_NEG_INF;
+  }
+  if (have) {
+    lengths[(long long)n * K + rank] = len;
+    scores[(long long)n * K + rank] = ranked;
+    ctc_scores[(long long)n * K + rank] = tot;
+    lm_scores[(long long)n * K + rank] = lms;
+  }
+  if (lane == 0) count[n] = min(alive, K);
+  __syncthreads();
+  int* out = ids + (long long)n * K * T;
+  for (long long i = lane; i < (long long)K * T; i += 64) {
+    const int k = (int)(i / T), tt = (int)(i - (long long)k * T);
+    if (tt >= b_len[k]) out[i] = blank;
+  }
+  if (have) {
+    int nd = node;
+    for (int i = len - 1; i >= 0 && nd > 0; --i) {
+      const u64 entry = __hip_atomic_load(tab + (nd - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      out[(long long)rank * T + i] = (int)(unsigned)(entry & 0xffffffffull) - 1;
+      nd = (int)(unsigned)(entry >> 32);
+    }
+  }
+}
+
 // nodes a row can create are at most T * beam; the table is kept under half full
 static inline long long ctcb_slots(int T, int beam) { return 2ll * T * beam + 64; }
 
@@ -238,6 +458,18 @@ static long long ctcb_ws_bytes(long long N, int T, int beam, int top_classes) {
   const long long lists = N * T * top_classes * (long long)(sizeof(int) + sizeof(float));
   const long long tables = N * ctcb_slots(T, beam) * (long long)sizeof(u64);
   return lists + tables <= INT_MAX ? lists + tables : 0;
+}
+
+// what both entry points check of the search itself, in the order they report it
+static int ctcb_check_sizes(const char* who, int N, int C, int T, int blank, int beam, int nbest, int top_classes) {
+  MR_CHECK_ARG(N >= 0, "%s: N=%d rows", who, N);
+  MR_CTC_TRY(ctc_check_columns(who, T, MR_SEQ_MEASURE_MAX));
+  MR_CTC_TRY(ctc_check_classes(who, C, blank));
+  MR_CHECK_ARG(beam >= 1 && beam <= MR_CTC_BEAM_MAX, "%s: beam=%d (1..MR_CTC_BEAM_MAX=%d)", who, beam, MR_CTC_BEAM_MAX);
+  MR_CHECK_ARG(nbest >= 1 && nbest <= beam, "%s: nbest=%d (1..beam=%d)", who, nbest, beam);
+  MR_CHECK_ARG(top_classes >= 1 && top_classes <= MR_CTC_BEAM_TOP_MAX, "%s: top_classes=%d (1..MR_CTC_BEAM_TOP_MAX=%d)", who,
+               top_classes, MR_CTC_BEAM_TOP_MAX);
+  return MR_OK;
 }
 
 }  // namespace mr
@@ -251,14 +483,7 @@ int mr_ctc_beam_ws_bytes(int N, int T, int beam, int top_classes) { return (int)
 int mr_ctc_beam_search(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T, int log_probs,
                        int blank, int unknown, int beam, int nbest, int top_classes, int* ids, int* lengths, float* scores,
                        int* count, void* ws, long long ws_bytes, hipStream_t stream) {
-  MR_CHECK_ARG(N >= 0, "mr_ctc_beam_search: N=%d rows", N);
-  MR_CTC_TRY(ctc_check_columns("mr_ctc_beam_search", T, MR_SEQ_MEASURE_MAX));
-  MR_CTC_TRY(ctc_check_classes("mr_ctc_beam_search", C, blank));
-  MR_CHECK_ARG(beam >= 1 && beam <= MR_CTC_BEAM_MAX, "mr_ctc_beam_search: beam=%d (1..MR_CTC_BEAM_MAX=%d)", beam,
-               MR_CTC_BEAM_MAX);
-  MR_CHECK_ARG(nbest >= 1 && nbest <= beam, "mr_ctc_beam_search: nbest=%d (1..beam=%d)", nbest, beam);
-  MR_CHECK_ARG(top_classes >= 1 && top_classes <= MR_CTC_BEAM_TOP_MAX,
-               "mr_ctc_beam_search: top_classes=%d (1..MR_CTC_BEAM_TOP_MAX=%d)", top_classes, MR_CTC_BEAM_TOP_MAX);
+  MR_CTC_TRY(ctcb_check_sizes("mr_ctc_beam_search", N, C, T, blank, beam, nbest, top_classes));
   MR_CTC_TRY(ctc_check_dtype("mr_ctc_beam_search", dtype));
   if (N == 0) return MR_OK;
   MR_CTC_TRY(ctc_check_workspace("mr_ctc_beam_search", "mr_ctc_beam_ws_bytes", ws, ws_bytes,
@@ -279,6 +504,49 @@ int mr_ctc_beam_search(int dtype, const void* pred, long long sn, long long sc, 
                   hipLaunchKernelGGL(ctc_beam_kernel<PT>, dim3(N), dim3(64), 0, stream, (const PT*)pred, sn, sc, st, C, T,
                                      log_probs, blank, beam, nbest, Kc, sym_id, sym_lp, tables, slots, ids, lengths, scores,
                                      count));
+  MR_CHECK_LAUNCH();
+  return MR_OK;
+}
+
+int mr_ctc_beam_search_lm(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T, int log_probs,
+                          int blank, int unknown, int beam, int nbest, int top_classes, const unsigned long long* lm_keys,
+                          const float* lm_arc_lp, const int* lm_arc_next, const float* lm_bow, const int* lm_backoff,
+                          const float* lm_end_lp, int states, int slots, int max_probe, int start_state, int order, float alpha,
+                          float beta, int end, int* ids, int* lengths, float* scores, float* ctc_scores, float* lm_scores,
+                          int* count, void* ws, long long ws_bytes, hipStream_t stream) {
+  MR_CTC_TRY(ctcb_check_sizes("mr_ctc_beam_search_lm", N, C, T, blank, beam, nbest, top_classes));
+  MR_CHECK_ARG(order >= 1 && order <= MR_NGRAM_ORDER_MAX, "mr_ctc_beam_search_lm: order=%d (1..MR_NGRAM_ORDER_MAX=%d)", order,
+               MR_NGRAM_ORDER_MAX);
+  MR_CHECK_ARG(states >= 1 && slots >= 1 && max_probe >= 1, "mr_ctc_beam_search_lm: states=%d slots=%d max_probe=%d (each >= 1)",
+               states, slots, max_probe);
+  MR_CHECK_ARG(start_state >= 0 && start_state < states, "mr_ctc_beam_search_lm: start_state=%d is not one of %d states",
+               start_state, states);
+  MR_CHECK_ARG(alpha - alpha == 0.f && beta - beta == 0.f, "mr_ctc_beam_search_lm: alpha=%g beta=%g must be finite", (double)alpha,
+               (double)beta);
+  MR_CHECK_ARG(lm_keys && lm_arc_lp && lm_arc_next && lm_bow && lm_backoff && lm_end_lp,
+               "mr_ctc_beam_search_lm: null model pointer");
+  MR_CTC_TRY(ctc_check_dtype("mr_ctc_beam_search_lm", dtype));
+  if (N == 0) return MR_OK;
+  MR_CTC_TRY(ctc_check_workspace("mr_ctc_beam_search_lm", "mr_ctc_beam_ws_bytes", ws, ws_bytes,
+                                 ctcb_ws_bytes(N, T, beam, top_classes)));
+  MR_CHECK_ARG(pred && ids && lengths && scores && ctc_scores && lm_scores && count, "mr_ctc_beam_search_lm: null pointer");
+  MR_CHECK_ARG((long long)N * T <= INT_MAX, "mr_ctc_beam_search_lm: N=%d rows x T=%d columns exceed the grid", N, T);
+  const long long cells = (long long)N * T * top_classes;
+  int* sym_id = (int*)ws;
+  float* sym_lp = (float*)(sym_id + cells);
+  u64* tables = (u64*)(sym_lp + cells);
+  const unsigned table_slots = (unsigned)ctcb_slots(T, beam);
+  const int staged = C <= CTCB_STAGE_MAX;
+  const size_t lds = staged ? (size_t)C * sizeof(float) : 0;
+  const int Kc = top_classes;
+  const CtcbModel lm = {lm_keys, lm_arc_lp, lm_arc_next, lm_bow, lm_backoff, lm_end_lp, states, (unsigned)slots, max_probe,
+                        start_state, order, alpha, beta, end};
+  MR_CTC_DISPATCH(dtype, PT,
+                  hipLaunchKernelGGL(ctc_beam_columns_kernel<PT>, dim3((unsigned)(N * T)), dim3(64), lds, stream, (const PT*)pred,
+                                     sn, sc, st, C, T, log_probs, blank, unknown, Kc, staged, sym_id, sym_lp);
+                  hipLaunchKernelGGL(ctc_beam_lm_kernel<PT>, dim3(N), dim3(64), 0, stream, (const PT*)pred, sn, sc, st, C, T,
+                                     log_probs, blank, beam, nbest, Kc, sym_id, sym_lp, tables, table_slots, lm, ids, lengths,
+                                     scores, ctc_scores, lm_scores, count));
   MR_CHECK_LAUNCH();
   return MR_OK;
 }

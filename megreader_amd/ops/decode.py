@@ -2,6 +2,8 @@
 sample and time step on the host (structure/representers/ctc_representer.py:20-34, ctc_representer2d.py:27-51,
 structure/measurers/sequence_recognition_measurer.py:66-112).  Same rules, bit-exact results
 (tests/test_decode_gpu.py against oracle/decode.py, which is pinned to the reference)."""
+import math
+
 import torch
 
 from .._lib import _DEFINES, call, load, ptr, require_cuda
@@ -47,7 +49,8 @@ def ctc_greedy_decode(pred, blank=0, unknown=1):
     return out, lengths
 
 
-def ctc_beam_search_decode(pred, beam=8, nbest=1, top_classes=16, blank=0, unknown=1, log_probs=False):
+def ctc_beam_search_decode(pred, beam=8, nbest=1, top_classes=16, blank=0, unknown=1, log_probs=False, lm=None, lm_weight=1.0,
+                           lm_bonus=0.0, lm_end=True):
     """CTC prefix beam search (mr_ctc_beam_search, include/megreader_hip.h): the `nbest` most probable STRINGS of every row with
     their log-probabilities, where `ctc_greedy_decode` returns the most probable path.  pred: [N, C, 1, T] or [N, C, T] on the GPU,
     any strides; probabilities (the eval head's softmax) or, with log_probs=True, their logs; f32 and bf16 are read as they are,
@@ -56,7 +59,14 @@ def ctc_beam_search_decode(pred, beam=8, nbest=1, top_classes=16, blank=0, unkno
     Returns a dict of device tensors: ids i32 [N, nbest, T] blank padded, lengths i32 [N, nbest], scores f32 [N, nbest]
     (descending; a lower bound of log p(string | pred), exact when nothing was pruned), count i32 [N] (hypotheses returned; slots
     past it: length 0, score -inf).  One call, no host work that depends on device data (capturable in a graph after one call
-    outside); the workspace is a fresh tensor per call."""
+    outside); the workspace is a fresh tensor per call.
+    With `lm`, a `CharNgramLM` (ops/language_model.py) over the same classes, the search is mr_ctc_beam_search_lm: the strings are
+    ranked by log p_ctc + lm_weight * log p_lm + lm_bonus * (symbols), with lm_end=True the model's end of string included.  The
+    dict gains ctc_scores f32 [N, nbest], the pure CTC log-probability (the lower bound above), and lm_scores f32 [N, nbest], the
+    model's weighted part; scores = ctc_scores + lm_scores is what the strings are ordered by.  The model may cover fewer classes
+    than C (the others take its floor), not more, and its blank and unknown are the call's: ValueError otherwise.  The model's
+    device image is uploaded on the first call per device and C (do that call outside a capture).  lm=None is the call above,
+    unchanged."""
     who = "ctc_beam_search_decode"
     beam, nbest, top_classes, blank = int(beam), int(nbest), int(top_classes), int(blank)
     if not 1 <= beam <= _DEFINES["MR_CTC_BEAM_MAX"]:
@@ -73,10 +83,28 @@ def ctc_beam_search_decode(pred, beam=8, nbest=1, top_classes=16, blank=0, unkno
     scores = torch.empty((N, nbest), dtype=torch.float32, device=dev)
     count = torch.empty((N,), dtype=torch.int32, device=dev)
     out = {'ids': ids, 'lengths': lengths, 'scores': scores, 'count': count}
+    if lm is not None:
+        lm_weight, lm_bonus = float(lm_weight), float(lm_bonus)
+        if lm.classes > C or lm.blank != blank or lm.unknown != int(unknown):
+            raise ValueError("%s: the model is over %d classes with blank=%d unknown=%d, the call has C=%d blank=%d unknown=%d"
+                             % (who, lm.classes, lm.blank, lm.unknown, C, blank, int(unknown)))
+        if not (math.isfinite(lm_weight) and math.isfinite(lm_bonus)):
+            raise ValueError("%s: lm_weight=%r and lm_bonus=%r must be finite" % (who, lm_weight, lm_bonus))
+        out['ctc_scores'] = torch.empty((N, nbest), dtype=torch.float32, device=dev)
+        out['lm_scores'] = torch.empty((N, nbest), dtype=torch.float32, device=dev)
     if N == 0:
         return out
     ws = _workspace(load().mr_ctc_beam_ws_bytes(N, T, beam, top_classes), who,
                     "N=%d T=%d beam=%d top_classes=%d" % (N, T, beam, top_classes), dev)
+    if lm is not None:
+        m = lm._tensors(dev, C)
+        with torch.cuda.device(dev):
+            call("mr_ctc_beam_search_lm", code, ptr(pred), sn, sc, st, N, C, T, int(bool(log_probs)), blank, int(unknown), beam,
+                 nbest, top_classes, ptr(m['keys']), ptr(m['arc_lp']), ptr(m['arc_next']), ptr(m['bow']), ptr(m['backoff']),
+                 ptr(m['end_lp']), m['states'], m['slots'], m['max_probe'], m['start_state'], m['order'], lm_weight, lm_bonus,
+                 int(bool(lm_end)), ptr(ids), ptr(lengths), ptr(scores), ptr(out['ctc_scores']), ptr(out['lm_scores']), ptr(count),
+                 ptr(ws), ws.numel() * 8)
+        return out
     with torch.cuda.device(dev):
         call("mr_ctc_beam_search", code, ptr(pred), sn, sc, st, N, C, T, int(bool(log_probs)), blank, int(unknown), beam, nbest,
              top_classes, ptr(ids), ptr(lengths), ptr(scores), ptr(count), ptr(ws), ws.numel() * 8)

@@ -53,7 +53,8 @@ class TextReader(object):
     def __init__(self, detector, recognizer, charset, representer=None, det_size=(576, 1024), rec_size=(32, 128),
                  rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
                  lexicon_max_distance=None, lexicon_rule='nearest', beam_width=None, nbest=1, beam_top_classes=16, chars=False,
-                 column_geometry=None, row_geometry=None, attention_extent=1.5, encoded=False):
+                 column_geometry=None, row_geometry=None, attention_extent=1.5, encoded=False, lm=None, lm_weight=1.0,
+                 lm_bonus=0.0):
         if lexicon_rule not in ('nearest', 'likelihood'):
             raise ValueError("lexicon_rule must be 'nearest' or 'likelihood', got %r" % (lexicon_rule,))
         if lexicon_rule == 'likelihood' and decode != 'ctc':
@@ -66,6 +67,8 @@ class TextReader(object):
         if decode == 'beam' and not (1 <= int(nbest) <= int(beam_width) <= 64 and 1 <= int(beam_top_classes) <= 64):
             raise ValueError("decode='beam' needs 1 <= nbest <= beam_width <= 64 and 1 <= beam_top_classes <= 64, got nbest=%r "
                              "beam_width=%r beam_top_classes=%r" % (nbest, beam_width, beam_top_classes))
+        if lm is not None and decode != 'beam':
+            raise ValueError("lm is fused into the CTC prefix beam search: it needs decode='beam', got %r" % (decode,))
         if int(max_crops) < 1:
             raise ValueError("max_crops must be at least 1, got %r" % (max_crops,))
         if decode == 'attention':
@@ -99,6 +102,7 @@ class TextReader(object):
         self.representer = representer if representer is not None else SegDetectorRepresenter(resize=True)
         self.decode = decode
         self.beam_width, self.nbest, self.beam_top_classes = int(beam_width), int(nbest), int(beam_top_classes)
+        self.lm, self.lm_weight, self.lm_bonus = lm, float(lm_weight), float(lm_bonus)
         self.max_crops = int(max_crops)
         self.scores = bool(scores)
         self.chars = bool(chars)
@@ -165,7 +169,8 @@ class TextReader(object):
         """One chunk by prefix beam search: (top-1 ids [M, T] and lengths [M] on the device, per crop {'text_score'} and, with
         nbest > 1, {'alternatives'}).  The ids, lengths and scores of the hypotheses are all that crosses to the host."""
         out = ctc_beam_search_decode(pred, beam=self.beam_width, nbest=self.nbest, top_classes=self.beam_top_classes,
-                                     blank=self.blank, unknown=self.unknown)
+                                     blank=self.blank, unknown=self.unknown, lm=self.lm, lm_weight=self.lm_weight,
+                                     lm_bonus=self.lm_bonus)
         return out['ids'][:, 0], out['lengths'][:, 0], self._hypotheses(out)
 
     def _align(self, pred, ids, lengths, found, head2d=None):
@@ -307,11 +312,15 @@ class TextReader(object):
         {'text_score'} and, with nbest > 1, {'alternatives'}.  The ids, lengths and scores are all that crosses to the host."""
         scores, count = out['scores'].cpu().tolist(), out['count'].cpu().tolist()
         extras = [{'text_score': float(row[0]) if k > 0 else float('-inf')} for row, k in zip(scores, count)]
+        parts = [out[key].cpu().tolist() for key in ('lm_scores', 'ctc_scores') if key in out]       # with a language model
+        if parts:
+            for m, extra in enumerate(extras):
+                extra['lm_score'], extra['ctc_score'] = (float(part[m][0]) for part in parts)    # (-inf past count: a dead beam)
         if self.nbest > 1:
             ids, lengths = out['ids'].cpu().numpy(), out['lengths'].cpu().numpy()
-            for extra, rows, lens, row_scores, k in zip(extras, ids, lengths, scores, count):
+            for m, (extra, rows, lens, row_scores, k) in enumerate(zip(extras, ids, lengths, scores, count)):
                 extra['alternatives'] = [(self.charset.label_to_string(rows[j][:int(lens[j])]), float(row_scores[j]))
-                                         for j in range(k)]
+                                         + tuple(float(part[m][j]) for part in parts) for j in range(k)]
         return extras
 
     def _read_attention(self, crops):
@@ -395,7 +404,11 @@ class TextReader(object):
         with a lexicon and the `nearest` rule as 'raw_text' and as what the nearest word is searched for -- and every item also
         has 'text_score', a float: its log-probability under the posterior (a lower bound: pruned alignments are missing); with
         `nbest > 1` also 'alternatives', the list of (text, score) of all hypotheses returned, the first one included, in
-        descending order.  A crop whose beam died (no string has a non-zero probability) gets '', -inf and [].  With `chars=True`
+        descending order.  A crop whose beam died (no string has a non-zero probability) gets '', -inf and [].  With `lm`, a
+        `CharNgramLM` over the reader's charset (`decode='beam'` only), the beam ranks its strings by log p_ctc + lm_weight *
+        log p_lm + lm_bonus * (symbols) (`ctc_beam_search_decode(lm=...)`): 'text_score' is that fused value, every item also
+        has 'lm_score' and 'ctc_score', its two parts (the latter the log-probability under the posterior), and the
+        'alternatives' are (text, score, lm_score, ctc_score).  With `chars=True`
         (`decode='ctc'` or `'beam'`) every item also has 'chars', one {'char', 'quad', 'score'} per character of 'text': the final
         string -- the greedy ids, the beam's first hypothesis, or the lexicon word where one was taken -- is aligned to the crop's
         posterior by `ctc_forced_align` (a lexicon word to the posterior over the folded alphabet), 'score' is the geometric mean
