@@ -996,6 +996,113 @@ int mr_sizeof_crop_desc(void);
 int mr_quad_crop(const unsigned char* src, const void* images /* [I] */, int I, const void* crops /* [M] */, int M,
                  int H, int W, double mean0, double mean1, double mean2, float* dst /* [M][3][H][W] */, hipStream_t stream);
 
+/* ---- Synthetic text (csrc/synth_text.hip): labelled word crops and scenes rendered on the device, from glyph atlases and tables
+ * the host plans in float64 (megreader_amd/data/synth_text.py).  One launch renders N canvases of H x W pixels: a background, the
+ * words ("items") of the canvas warped onto it with a drop shadow, a 5 x 5 separable blur, noise, and the quantised result as
+ * uint8 HWC (B, G, R like a decoded photo) and / or as the recogniser's normalised f32 planes.
+ *
+ * Tables.  All live in memory the device reads.  `base` is the address every byte offset below is relative to (offsets may be
+ * negative: an atlas or a photo resident in another allocation).
+ *   fonts [F]: a font is a uint8 coverage image ("atlas") of gh rows and aw columns, row j at base + atlas_off + j*pitch, and the
+ *     pairs glyphs[2*(glyph_first + id)] = x0, glyphs[2*(glyph_first + id) + 1] = w for class ids 0 <= id < n_classes: the glyph's
+ *     first column in the atlas and its advance box (bearings are inside the box).  `glyphs` holds G pairs in all.  A pair is
+ *     VALID when 0 <= glyph_first + id < G, x0 >= 0, 0 < w <= MR_SYNTH_MAX_GLYPH_W and x0 + w <= aw; every other pair, w = 0
+ *     (a class without a glyph) included, and every id outside [0, n_classes), counts as w = 0.
+ *   items [I]: a word: its canvas, its font, n_glyphs <= MR_SYNTH_MAX_GLYPHS class ids, the projective map h[9] canvas -> line
+ *     (float64, row major), the integer box [x0, x1) x [y0, y1) of canvas pixels outside which it contributes nothing, the colours
+ *     fg[3] and shadow[3] (float, in the order of the output channels), shadow_alpha, and the shadow's offset (shadow_dx,
+ *     shadow_dy) in line pixels.  An item whose font is outside [0, F), whose font has gh < 1, whose n_glyphs is outside
+ *     [0, MR_SYNTH_MAX_GLYPHS] or whose `canvas` is not the index of the canvas that lists it contributes nothing.
+ *   canvases [N]: items first_item .. first_item + n_items - 1 in table order (n_items <= MR_SYNTH_MAX_ITEMS: a larger count is
+ *     cut to it, a negative one is 0; indices outside [0, I) name no item); the background (photo == 0: two colours bg0, bg1 and a gradient gx, gy, g0; photo != 0: a resident uint8 HWC
+ *     photo of at least H rows and W columns, row y at base + photo_off + y*photo_pitch); blur != 0: the taps w0, w1, w2 of the
+ *     symmetric kernel (w2, w1, w0, w1, w2); the noise amplitude and a 32-bit seed (the int's bits).
+ *
+ * The virtual line image of an item.  start[0] = 0, start[g + 1] = start[g] + w of glyph g (0 for a pair that is not valid); the
+ * line has Lw = start[n_glyphs] columns and gh rows.  Column i, 0 <= i < Lw, belongs to the one glyph g with
+ * start[g] <= i < start[g + 1], and L(i, j) = atlas[j][x0[g] + i - start[g]]; L is 0 outside [0, Lw) x [0, gh).  Only bytes
+ * atlas[j][k], 0 <= j < gh, 0 <= k < aw, are ever read, whatever the tables hold.
+ *
+ * Canvas pixel (x, y), channel c.  Every product and sum is rounded on its own, no fma, in the precision named; fmin / fmax
+ * return the other operand for a NaN.
+ *   comp(x, y), float32 unless marked:
+ *     background: t = fminf(fmaxf(gx*(x + 0.5f) + gy*(y + 0.5f) + g0, 0), 1)           (left to right)
+ *                 col[c] = bg0[c] + (bg1[c] - bg0[c]) * t;      with a photo: col[c] = (float)photo[y][x][c]
+ *     for each item of the canvas in table order with x0 <= x < x1 and y0 <= y < y1:
+ *       float64, left to right as mr_quad_crop:  px = x + 0.5, py = y + 0.5
+ *         X = h[0]*px + h[1]*py + h[2], Y = h[3]*px + h[4]*py + h[5], D = h[6]*px + h[7]*py + h[8]
+ *         u = X / D - 0.5, v = Y / D - 0.5
+ *       cov(u, v): 0 when D <= 0 (or NaN) or not (-1 < u < Lw and -1 < v < gh) (which a NaN or an infinity fails); otherwise
+ *         iu = floor(u), fu = (float)(u - iu); iv = floor(v), fv = (float)(v - iv); the four taps L(iu, iv), L(iu + 1, iv),
+ *         L(iu, iv + 1), L(iu + 1, iv + 1) as float and the float32 blend top, bot, val of mr_warp_normalize; cov = val / 255.f
+ *       a = cov(u, v);  if shadow_alpha != 0: s = cov(u - shadow_dx, v - shadow_dy) (float64 differences), ts = s * shadow_alpha,
+ *         col[c] = col[c]*(1.f - ts) + shadow[c]*ts.   Then col[c] = col[c]*(1.f - a) + fg[c]*a.
+ *   blur != 0:  with xi = min(max(x + i, 0), W - 1), yj = min(max(y + j, 0), H - 1) and k[-2..2] = (w2, w1, w0, w1, w2):
+ *       row(x, yj)[c] = k[-2]*comp(x-2, yj)[c] + k[-1]*comp(x-1, yj)[c] + k[0]*comp(x, yj)[c] + k[1]*comp(x+1, yj)[c] + k[2]*comp(x+2, yj)[c]
+ *       col[c] = k[-2]*row(x, y-2)[c] + k[-1]*row(x, y-1)[c] + k[0]*row(x, y)[c] + k[1]*row(x, y+1)[c] + k[2]*row(x, y+2)[c]
+ *     (each sum left to right, starting from its first product; the x +- i and y +- j above stand for the clamped xi, yj).
+ *     blur == 0: col = comp(x, y).
+ *   noise, uint32 arithmetic modulo 2^32:  k = (y*W + x)*3 + c;  r = seed + k * 0x9E3779B9;
+ *       r ^= r >> 16;  r *= 0x7FEB352D;  r ^= r >> 15;  r *= 0x846CA68B;  r ^= r >> 16;                          ("lowbias32")
+ *       col[c] = col[c] + noise_amp * ((float)(r >> 8) * 0x1p-24f - 0.5f)
+ *   q[c] = fminf(fmaxf(floorf(col[c] + 0.5f), 0), 255)
+ *   out_u8[n][y][x][c] = (unsigned char)q[c];   out_f32[n][c][y][x] = (float)((double)q[c] - mean[c]) / 255.f
+ * The f32 output is the normalising store of mr_resize_normalize: bit-equal to mr_resize_normalize of out_u8 at identity scale.
+ * Either output may be NULL (not both); every element of a given output is written.  A canvas's pixels are a function of its
+ * own table entries alone: they do not depend on N, on the canvas's position in the call or on the launch geometry.
+ *
+ * One launch on `stream` (a workgroup per MR_SYNTH_TILE_H x MR_SYNTH_TILE_W tile of a canvas), no allocation, no
+ * synchronisation; N == 0 returns MR_OK without a launch.  MR_ERR_ARG, nothing written: H or W < 1, N, F, G or I < 0, more than
+ * INT_MAX tiles, a NULL table that has elements (canvases; items when I > 0; fonts when F > 0; glyphs when G > 0), both outputs
+ * NULL.  When `canvases` / `items` / `fonts` are pinned host memory (and `stream` is not being captured) the entry point also
+ * refuses, before the launch, a canvas
+ * whose items are not inside [0, I) or more than MR_SYNTH_MAX_ITEMS, an item whose n_glyphs, font or canvas is out of range or
+ * not listed by its canvas, and a font whose glyph pairs are not inside [0, G).  Tables it cannot read are the kernel's to
+ * guard: every loop of the kernel is bounded by the limits above whatever the tables hold. */
+#define MR_SYNTH_MAX_GLYPHS 32
+#define MR_SYNTH_MAX_ITEMS 32
+#define MR_SYNTH_MAX_GLYPH_W 65536
+#define MR_SYNTH_TILE_H 16
+#define MR_SYNTH_TILE_W 64
+typedef struct mr_synth_font {
+  long long atlas_off;          /* byte offset of atlas row 0 from base */
+  int pitch;                    /* bytes per atlas row (>= aw) */
+  int gh, aw;                   /* rows and columns of the atlas */
+  int glyph_first, n_classes;   /* this font's pairs are glyphs[2*glyph_first .. 2*(glyph_first + n_classes)) */
+  int reserved;                 /* 0 (pads the entry to 32 bytes) */
+} mr_synth_font;
+typedef struct mr_synth_item {
+  int canvas, font, n_glyphs;
+  int reserved;                 /* 0 */
+  int x0, x1, y0, y1;           /* the item's box of canvas pixels */
+  float fg[3], shadow[3];
+  float shadow_alpha;
+  float reserved1;              /* 0 (keeps the doubles 8-byte aligned) */
+  double shadow_dx, shadow_dy;  /* line pixels */
+  double h[9];                  /* canvas -> line, row major, projective */
+  int glyph[32];                /* class ids (MR_SYNTH_MAX_GLYPHS entries) */
+} mr_synth_item;
+typedef struct mr_synth_canvas {
+  int first_item, n_items;
+  int photo;                    /* 0: gradient background, otherwise the photo at photo_off */
+  int blur;                     /* 0: no blur */
+  float bg0[3], bg1[3];
+  float gx, gy, g0;
+  float w0, w1, w2;             /* blur taps: (w2, w1, w0, w1, w2) */
+  float noise_amp;
+  int seed;                     /* the 32 bits of the noise seed */
+  long long photo_off;          /* byte offset of the photo's first pixel from base */
+  int photo_pitch;              /* bytes per photo row (>= 3 * W) */
+  int reserved;                 /* 0 */
+} mr_synth_canvas;
+int mr_sizeof_synth_font(void);
+int mr_sizeof_synth_item(void);
+int mr_sizeof_synth_canvas(void);
+int mr_synth_render(const unsigned char* base, const void* fonts /* [F] */, int F, const int* glyphs /* [G][2] */, int G,
+                    const void* items /* [I] */, int I, const void* canvases /* [N] */, int N, int H, int W, double mean0,
+                    double mean1, double mean2, unsigned char* out_u8 /* [N][H][W][3] or NULL */,
+                    float* out_f32 /* [N][3][H][W] or NULL */, hipStream_t stream);
+
 /* ---- Lexicon-constrained reading (csrc/lexicon.hip): the nearest lexicon word of every predicted id sequence, the rule of the
  * recognition benchmarks that are reported with lexicons (50 words per image, 1 k per set, "full"), and the membership test of
  * structure/measurers/sequence_recognition_measurer.py:59-64 (`in_lexicon`: distance 0).

@@ -2,7 +2,7 @@
 // mr_warp_normalize (the DB detector's training augmentation) and mr_quad_crop (text-line crops for the recogniser).  Each reads
 // packed uint8 HWC pixels along its own coordinate map and writes normalised f32 planes; they promise bit-equal results where
 // their maps coincide (include/megreader_hip.h), so what they share -- the canvas index split, the zero-border tap, the guarded
-// bilinear blend and the normalising store -- is written once below.
+// bilinear blend and the normalising store -- is written once, here and in image_sample.h (which csrc/synth_text.hip shares).
 //
 // DB detector augmentation, the image half (include/megreader_hip.h: mr_warp_normalize).  The reference resamples three
 // times per sample on the host -- imgaug Affine (rotate), imgaug Resize, cv2.resize of the crop in
@@ -25,6 +25,7 @@
 // photo stays in L2 across the hundreds of crops that read it.
 #include "common.h"
 #include "../../include/megreader_hip.h"
+#include "image_sample.h"
 
 // Bit-exactness against the numpy restatements (oracle/pipeline.py, tests/_db_augment_ref.py, tests/_quad_crop_ref.py): every
 // product and sum of this file is rounded on its own (hipcc contracts a*b + c*d into an fma by default, and HIP's __fmul_rn /
@@ -45,54 +46,6 @@ __device__ __forceinline__ void canvas_split(unsigned gid, int Hd, int Wd, int& 
   u = (int)(gid - row * Wd);
   n = (int)(row / Hd);
   v = (int)(row - (unsigned)n * Hd);
-}
-
-// One source pixel (3 bytes) as floats: row r, column k of `base`, or 0 where the caller found it outside.  No byte is
-// addressed unless `inside`.
-__device__ __forceinline__ void tap3(bool inside, const unsigned char* base, int pitch, int r, int k, float p[3]) {
-  p[0] = p[1] = p[2] = 0.f;
-  if (inside) {
-    const unsigned char* s = base + (long long)r * pitch + 3 * k;
-    p[0] = (float)s[0];
-    p[1] = (float)s[1];
-    p[2] = (float)s[2];
-  }
-}
-
-// val = the bilinear sample at (x, y) of a source of w columns and h rows whose pixels `tap(xx, yy, p)` reads (0 outside):
-// floor, float32 fractions, four taps, horizontal pass then vertical pass.  Outside (-1, w) x (-1, h) all four taps are
-// outside and val keeps its zeros; the test also keeps a NaN, an infinity or a huge coordinate away from the int cast.
-// `ok`: a condition of the caller's map that joins the test (one branch for both: the form the crop kernel was measured in).
-template <typename Tap>
-__device__ __forceinline__ void bilinear3(bool ok, double x, double y, int w, int h, Tap tap, float val[3]) {
-  if (ok && x > -1.0 && x < (double)w && y > -1.0 && y < (double)h) {
-    const double xf = floor(x), yf = floor(y);
-    const float fx = (float)(x - xf), fy = (float)(y - yf);
-    const int ix = (int)xf, iy = (int)yf;
-    float p00[3], p01[3], p10[3], p11[3];
-    tap(ix, iy, p00);
-    tap(ix + 1, iy, p01);
-    tap(ix, iy + 1, p10);
-    tap(ix + 1, iy + 1, p11);
-    const float gx = 1.f - fx, gy = 1.f - fy;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float top = p00[c] * gx + p01[c] * fx;
-      const float bot = p10[c] * gx + p11[c] * fx;
-      val[c] = top * gy + bot * fy;
-    }
-  }
-}
-
-// dst[n][c][y][x] = (float)((double)val[c] - mean[c]) / 255.f: normalize_image.py:8-17 (-= RGB_MEAN in double, /= 255 in f32,
-// HWC -> CHW).
-__device__ __forceinline__ void store_normalized(float* dst, int n, int y, int x, int Hd, int Wd, const float val[3],
-                                                 double m0, double m1, double m2) {
-  const double mean[3] = {m0, m1, m2};
-  const long long per = (long long)Hd * Wd;
-  float* o = dst + (long long)n * 3 * per + (long long)y * Wd + x;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) o[c * per] = (float)((double)val[c] - mean[c]) / 255.f;
 }
 
 // dst[n, c, y, x] = ((double)resize(src_n)[y, x, c] - mean[c]) -> f32, / 255.f ; canvas columns >= dst_w hold the

@@ -107,15 +107,22 @@ def rect_corners(quad):
     return _from_top_edge(corners)
 
 
+def homographies(src, dst):
+    """The projective maps (3 x 3, h[8] = 1) that take the four points src[k] to dst[k]: src, dst [n, 4, 2] -> [n, 3, 3], n 8 x 8
+    float64 systems in one batched solve."""
+    src, dst = np.asarray(src, dtype=np.float64).reshape(-1, 4, 2), np.asarray(dst, dtype=np.float64).reshape(-1, 4, 2)
+    n = len(src)
+    (xs, ys), (xd, yd) = (src[..., 0], src[..., 1]), (dst[..., 0], dst[..., 1])
+    A = np.zeros((n, 8, 8), dtype=np.float64)
+    A[:, 0::2, 0], A[:, 0::2, 1], A[:, 0::2, 2], A[:, 0::2, 6], A[:, 0::2, 7] = xs, ys, 1.0, -xs * xd, -ys * xd
+    A[:, 1::2, 3], A[:, 1::2, 4], A[:, 1::2, 5], A[:, 1::2, 6], A[:, 1::2, 7] = xs, ys, 1.0, -xs * yd, -ys * yd
+    b = np.stack([xd, yd], axis=-1).reshape(n, 8, 1)
+    return np.concatenate([np.linalg.solve(A, b)[..., 0], np.ones((n, 1))], axis=1).reshape(n, 3, 3)
+
+
 def _homography(src, dst):
-    """The projective map (3 x 3, h[8] = 1) that takes the four points src [4, 2] to dst [4, 2]: an 8 x 8 float64 solve."""
-    A = np.zeros((8, 8), dtype=np.float64)
-    b = np.zeros(8, dtype=np.float64)
-    for k, ((xs, ys), (xd, yd)) in enumerate(zip(src, dst)):
-        A[2 * k] = [xs, ys, 1.0, 0.0, 0.0, 0.0, -xs * xd, -ys * xd]
-        A[2 * k + 1] = [0.0, 0.0, 0.0, xs, ys, 1.0, -xs * yd, -ys * yd]
-        b[2 * k], b[2 * k + 1] = xd, yd
-    return np.append(np.linalg.solve(A, b), 1.0).reshape(3, 3)
+    """The projective map (3 x 3, h[8] = 1) that takes the four points src [4, 2] to dst [4, 2]."""
+    return homographies(np.asarray(src, dtype=np.float64)[None], np.asarray(dst, dtype=np.float64)[None])[0]
 
 
 def crop_frame(quad, rectify='min_area_rect'):
