@@ -996,6 +996,90 @@ int mr_sizeof_crop_desc(void);
 int mr_quad_crop(const unsigned char* src, const void* images /* [I] */, int I, const void* crops /* [M] */, int M,
                  int H, int W, double mean0, double mean1, double mean2, float* dst /* [M][3][H][W] */, hipStream_t stream);
 
+/* ---- Tiled multi-scale detection (csrc/det_tiles.hip): a photo too large for one detector input is resized to a CANVAS at its
+ * own scale (several canvases: several "levels"), the canvas is covered by overlapping detector-sized tiles, and the tiles'
+ * probability maps are fused into one map per photo BEFORE the boxes are read, so that a word cut by a tile border comes back
+ * as one box.  The host plans canvases and tiles from shapes only (megreader_amd/data/detection_tiles.py).
+ *
+ * The 1-D cover, applied to each axis on its own: a canvas side L, tiles of side t with halo h (t > 2h), stride s = t - 2h.
+ *   L <= t: K = 1, the tile starts at 0.  Otherwise K = ceil((L - t) / s) + 1 tiles start at o_k = k*s (the last may overhang L).
+ *   owner(p) of canvas coordinate p, 0 <= p < L:  0 if p < t - h, else min(K - 1, (p - h) / s)      (integer division)
+ *   Every p has exactly one owner, and p - o_owner lies in [0, t): in the owner's "core", at least h from the tile's inner borders.
+ *   Tile (ky, kx) of a level is entry first + ky*Kx + kx of the tile arrays.
+ *
+ * mr_tile_sample: ONE launch draws all T tiles of all photos and levels from the resident uint8 HWC photos (the photo table of
+ * mr_quad_crop: `offset` relative to src, may be negative).  Pixel (u, v) of tile t, 0 <= u < tw, 0 <= v < th, is canvas pixel
+ * (X, Y) = (x0 + u, y0 + v).  For 0 <= X < wc and 0 <= Y < hc its value is the value of mr_resize_normalize at (X, Y) of a
+ * resize of photo `image` (h rows, w columns) to hc rows and wc columns, bit for bit:
+ *   h == hc and w == wc:  val[c] = (float)src(X, Y)[c]                                    (cv2.resize returns a copy)
+ *   otherwise  fx = (float)((X + 0.5)*scale_x - 0.5)   (the product and the sum in float64, each rounded, then one rounding to f32)
+ *              sx = (int)floorf(fx), fx = fx - sx;  sx < 0: sx = 0, fx = 0;  sx >= w - 1: sx = w - 1, fx = 0;  sx1 = min(sx + 1, w - 1)
+ *              fy, sy, sy1 likewise from Y, scale_y and h
+ *              top = src(sx, sy)*(1 - fx) + src(sx1, sy)*fx, bot = src(sx, sy1)*(1 - fx) + src(sx1, sy1)*fx
+ *              val = top*(1 - fy) + bot*fy                                                (float32, no fma)
+ *   dst[t][c][v][u] = (float)((double)val[c] - mean[c]) / 255.f
+ * with scale_x = 1. / ((double)wc / w) and scale_y = 1. / ((double)hc / h) evaluated by the host.  Every other pixel -- outside
+ * the canvas, or of a tile whose `image` is not in [0, I) or whose wc or hc is < 1 -- is 0.0f: NOT the normalised zero pixel of
+ * mode "pad", but what a detector's own zero padding supplies beyond a whole canvas, which is what makes a tiled detector
+ * equal the untiled one.  Every element of dst f32 [T][3][th][tw] is written; only bytes src[offset + r*pitch + 3*k + c],
+ * 0 <= r < h, 0 <= k < w, of photos in the table are read.  MR_ERR_ARG, nothing written: a null pointer with T > 0, T or I < 0,
+ * th or tw < 1, T*th*tw*3 >= 2^31.  T == 0 returns MR_OK without a launch.
+ *
+ * mr_tile_stitch: a gather; every pixel of every fused map is written exactly once by the one thread that owns it (no atomics:
+ * the bits are the same on every run).  maps: [T][th][tw], dtype MR_F32 or MR_BF16 (read as (float)).  levels: one
+ * mr_stitch_level per (photo, level); photos: one mr_stitch_photo per photo, whose `levels` entries start at `first_level` and
+ * are fused in that order; `base` (0 <= base < levels) names the level whose canvas is the fused map: hb x wb is its hc x wc.
+ * Fused pixel (X, Y) of photo p, value v_l of level l:
+ *   tile_value(l, x, y) = maps[first + owner(y)*kx + owner(x)][y - o_owner(y)][x - o_owner(x)]  with the cover of hc (halo_y) and
+ *                         of wc (halo_x); 0.0f when that tile index is not in [0, T) or a table whose ky, kx are not the
+ *                         cover's puts the local coordinate outside [0, th) x [0, tw): no element outside maps is read
+ *   l == base:  v_l = tile_value(l, X, Y)
+ *   otherwise   x = (X + 0.5)*ratio_x - 0.5  (float64, the product and the sum each rounded; ratio_x = (double)wc / (double)wb, one
+ *               correctly rounded division, evaluated by the host), clamped to [0, wc - 1];  ix = floor(x), fx = (float)(x - ix),
+ *               ix1 = min(ix + 1, wc - 1);  y, iy, fy, iy1 likewise from Y, ratio_y = (double)hc / (double)hb and hc;  each of the
+ *               four taps is tile_value at its OWN owner tile (taps may straddle a core border)
+ *               top = tap(ix, iy)*(1 - fx) + tap(ix1, iy)*fx, bot = tap(ix, iy1)*(1 - fx) + tap(ix1, iy1)*fx
+ *               v_l = top*(1 - fy) + bot*fy                                               (float32, no fma)
+ *   fuse 0 (max):   out = fmaxf(...fmaxf(fmaxf(v_0, v_1), v_2)...)                        (listed order)
+ *   fuse 1 (mean):  out = ((v_0 + v_1) + ...) / (float)levels                             (float32, listed order)
+ *   out[offset + Y*wb + X] = out                                                          (offset in ELEMENTS of the packed f32 buffer)
+ * A photo whose map does not lie inside [0, out_elems), whose levels do not lie inside the level table, or whose hb, wb, levels
+ * or base are out of range is skipped (nothing of it is written).  max_pixels: the largest hb*wb of the table (the launch is
+ * sized by it; pixels beyond it are not written).  MR_ERR_ARG, nothing written: a null pointer with P > 0, T, L or P < 0, th or
+ * tw < 1, a halo < 0 or th <= 2*halo_y or tw <= 2*halo_x, T*th*tw >= 2^31, max_pixels < 1 or >= 2^31, out_elems < 0, P > 65535, fuse outside {0, 1};
+ * MR_ERR_DTYPE: another dtype.  P == 0 returns MR_OK without a launch. */
+#define MR_TILE_FUSE_MAX 0
+#define MR_TILE_FUSE_MEAN 1
+typedef struct mr_tile_desc {
+  int image;                    /* index into the mr_crop_image table */
+  int x0, y0;                   /* canvas coordinates of the tile's first pixel */
+  int wc, hc;                   /* the canvas: columns and rows of the resized photo */
+  int reserved;                 /* 0 (keeps the doubles 8-byte aligned) */
+  double scale_x, scale_y;      /* cv2.resize scales: 1. / ((double)wc / w), 1. / ((double)hc / h) */
+} mr_tile_desc;
+typedef struct mr_stitch_level {
+  int hc, wc;                   /* the level's canvas: rows and columns */
+  int ky, kx;                   /* its tile grid (the cover's K of hc and of wc) */
+  int first;                    /* index of its tile (0, 0) in the tile maps */
+  int reserved;                 /* 0 (keeps the doubles 8-byte aligned) */
+  double ratio_x, ratio_y;      /* (double)wc / (double)wb and (double)hc / (double)hb of its photo; not read for the base level */
+} mr_stitch_level;
+typedef struct mr_stitch_photo {
+  long long offset;             /* first element of the photo's fused map in the packed f32 output */
+  int hb, wb;                   /* rows and columns of the fused map: the base level's canvas */
+  int levels, first_level;      /* its entries of the level table: first_level .. first_level + levels - 1 */
+  int base;                     /* which of them (0 .. levels - 1) is the base level */
+  int reserved;                 /* 0 */
+} mr_stitch_photo;
+int mr_sizeof_tile_desc(void);
+int mr_sizeof_stitch_level(void);
+int mr_sizeof_stitch_photo(void);
+int mr_tile_sample(const unsigned char* src, const void* images /* [I] */, int I, const void* tiles /* [T] */, int T, int th,
+                   int tw, double mean0, double mean1, double mean2, float* dst /* [T][3][th][tw] */, hipStream_t stream);
+int mr_tile_stitch(int dtype, const void* maps /* [T][th][tw] */, int T, int th, int tw, int halo_y, int halo_x,
+                   const void* levels /* [L] */, int L, const void* photos /* [P] */, int P, long long max_pixels, int fuse,
+                   float* out, long long out_elems, hipStream_t stream);
+
 /* ---- Synthetic text (csrc/synth_text.hip): labelled word crops and scenes rendered on the device, from glyph atlases and tables
  * the host plans in float64 (megreader_amd/data/synth_text.py).  One launch renders N canvases of H x W pixels: a background, the
  * words ("items") of the canvas warped onto it with a drop shadow, a 5 x 5 separable blur, noise, and the quantised result as

@@ -33,12 +33,21 @@ lowest and the highest height of every character cross to the host as well).
 An attention recogniser (a backbone and an `AttentionDecoder`) has no posterior to read; `decode='attention'` goes through
 `AttentionDecoder.read` instead: the probability of the string and of every character under the decoder, n-best strings by beam
 search, and character boxes from the mean and spread of each step's attention map (per chunk the words' log-probabilities
-and four moments per character cross to the host)."""
+and four moments per character cross to the host).
+
+`det_scales` (None: step 1 and 2 as above, one `det_size` canvas per photo whatever its size) reads large photos at their own
+scale: `det_size` becomes the size of a TILE, every photo is resized to one canvas per entry of `det_scales` ('fit': `det_size`
+itself; a float s: the photo times s, rounded to multiples of `det_align`), the canvases are covered by tiles that overlap by
+twice `det_halo`, the detector runs on the tiles in chunks of `det_batch`, and the tiles' maps of all levels are fused
+(`det_fuse`: 'max' or 'mean') into ONE map per photo, on which the representer runs once with the photo's own shape
+(data/detection_tiles.py: `DetectionTiler`; a word cut by a tile border comes back as one box).  The tiles are sampled from the
+photos the pipeline uploaded, decoded ones with `encoded=True`; everything behind the boxes is as above."""
 import math
 
 import numpy as np
 import torch
 
+from .data.detection_tiles import DetectionTiler
 from .data.device_pipeline import DevicePipeline, EncodedDevicePipeline
 from .data.jpeg_decode import SPLIT_ABOVE
 from .data.quad_crop import QuadCropper
@@ -54,7 +63,13 @@ class TextReader(object):
                  rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
                  lexicon_max_distance=None, lexicon_rule='nearest', beam_width=None, nbest=1, beam_top_classes=16, chars=False,
                  column_geometry=None, row_geometry=None, attention_extent=1.5, encoded=False, lm=None, lm_weight=1.0,
-                 lm_bonus=0.0):
+                 lm_bonus=0.0, det_scales=None, det_halo=(64, 64), det_fuse='max', det_batch=8, det_align=32):
+        self.det_tiler = None
+        if det_scales is not None:      # tiles of `det_size` at the photo's own scale, fused per photo (data/detection_tiles.py)
+            if int(det_batch) < 1:
+                raise ValueError("det_batch must be at least 1, got %r" % (det_batch,))
+            self.det_tiler = DetectionTiler(tile=det_size, halo=det_halo, scales=det_scales, fuse=det_fuse, align=det_align)
+        self.det_batch = int(det_batch)
         if lexicon_rule not in ('nearest', 'likelihood'):
             raise ValueError("lexicon_rule must be 'nearest' or 'likelihood', got %r" % (lexicon_rule,))
         if lexicon_rule == 'likelihood' and decode != 'ctc':
@@ -127,6 +142,24 @@ class TextReader(object):
         staged, layout = self.det_pipeline.pack(images, [''] * len(images))
         batch = self.det_pipeline.upload(staged, layout)
         return batch, self.det_pipeline.photos(batch, layout)
+
+    def _detect_tiled(self, photos):
+        """With `det_scales`: the detector on tiles of the resident photos at their own scale (`DetectionTiler.detect_maps`), every
+        map the representer reads -- 'binary', and `representer.dest` when it differs -- fused per photo, and the representer
+        once per photo on the fused map with the photo's own shape: (boxes per photo, scores per photo or None)."""
+        keys = ('binary',) + ((self.representer.dest,) if getattr(self.representer, 'dest', 'binary') != 'binary' else ())
+        fused = self.det_tiler.detect_maps(self.detector, photos, batch=self.det_batch, keys=keys)
+        boxes, box_scores = [], ([] if self.scores else None)
+        for i, photo in enumerate(photos):
+            det_batch = {'image': None, 'shape': [tuple(photo.shape[:2])]}
+            pred = {key: fused[key][i] for key in keys}
+            if self.scores:
+                found, scored, _ = self.representer.represent_scored(det_batch, pred)
+                box_scores.extend(scored)
+            else:
+                found, _ = self.representer.represent(det_batch, pred)
+            boxes.extend(found)
+        return boxes, box_scores
 
     @staticmethod
     def _head2d(pred):
@@ -444,14 +477,17 @@ class TextReader(object):
         if not images:
             return results
         batch, photos = self._upload(images)
-        pred = self._eval(self.detector, batch['image'])
-        if not isinstance(pred, dict):
-            pred = {'binary': pred}
-        det_batch = {'image': batch['image'], 'shape': [tuple(p.shape[:2]) for p in photos]}
-        if self.scores:
-            boxes, box_scores, _ = self.representer.represent_scored(det_batch, pred)
+        if self.det_tiler is not None:          # (the pipeline's one-canvas batch is not looked at: the tiles read the photos)
+            boxes, box_scores = self._detect_tiled(photos)
         else:
-            boxes, _ = self.representer.represent(det_batch, pred)
+            pred = self._eval(self.detector, batch['image'])
+            if not isinstance(pred, dict):
+                pred = {'binary': pred}
+            det_batch = {'image': batch['image'], 'shape': [tuple(p.shape[:2]) for p in photos]}
+            if self.scores:
+                boxes, box_scores, _ = self.representer.represent_scored(det_batch, pred)
+            else:
+                boxes, _ = self.representer.represent(det_batch, pred)
         staged, layout = self.cropper.pack(photos, boxes)
         if layout.M == 0:
             return results
