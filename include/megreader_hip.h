@@ -1187,6 +1187,80 @@ int mr_synth_render(const unsigned char* base, const void* fonts /* [F] */, int 
                     double mean1, double mean2, unsigned char* out_u8 /* [N][H][W][3] or NULL */,
                     float* out_f32 /* [N][3][H][W] or NULL */, hipStream_t stream);
 
+/* ---- Recognition augmentation (csrc/rec_augment.hip): the recogniser's training augmentation -- geometric jitter, a wavy
+ * baseline, a colour map, a 5 x 5 blur, noise, pixelation and erased rectangles, per sample -- in ONE bilinear pass from the
+ * resident uint8 HWC photos (stored crops, or scenes that hold the words) to the recogniser's normalised f32 planes.  The host
+ * plans every sample in float64 from shapes alone (megreader_amd/data/recognition_augment.py); the device reads each source
+ * pixel once.  `images` is the photo table of mr_quad_crop (`offset` relative to src, may be negative).
+ *
+ * The call writes the whole rows dst[row] of its M descriptors and NOTHING else: rows that no descriptor names keep their bytes,
+ * so a pipeline runs its plain kernel over the batch and this one over the augmented rows, and the other samples keep their bits.
+ *
+ * Every product and sum is rounded on its own, no fma, in the precision named; fmin / fmax (min / max below) return the other
+ * operand for a NaN.  With Wv = min(max(dst_w, 0), W), canvas pixel (u, v) of a descriptor, u < Wv:
+ *   comp(u, v):
+ *     q = max(quant, 1);  bu = (u / q)*q, bv = (v / q)*q                                  (integer division)
+ *     U = (double)bu + 0.5*(double)q, V = (double)bv + 0.5*(double)q                      (float64 from here)
+ *     t = U*8.0 / (double)Wv;  j = (int)min(max(floor(t), 0), 7);  f = t - (double)j
+ *     U' = U + ((double)dx[j] + ((double)dx[j+1] - (double)dx[j])*f),  V' = V + ((double)dy[j] + ((double)dy[j+1] - (double)dy[j])*f)
+ *     cx = U'*sx - 0.5, cy = V'*sy - 0.5                                                  (cv2.resize's sampling point, displaced)
+ *     X = g[0]*cx + g[1]*cy + g[2], Y = g[3]*cx + g[4]*cy + g[5], D = g[6]*cx + g[7]*cy + g[8]     (left to right, as mr_quad_crop)
+ *     D <= 0 (or NaN): val = 0.  Otherwise px = min(max(X / D, cu0), cu1), py = min(max(Y / D, cv0), cv1), and (px, py) goes
+ *     through h[9] as mr_quad_crop's (cx, cy) does: X2 = h[0]*px + h[1]*py + h[2], Y2, D2 likewise, x = X2 / D2, y = Y2 / D2;
+ *     D2 <= 0 (or NaN), or x or y not finite: val = 0; otherwise floor, (float) fractions, the four taps (0 outside
+ *     [0, w) x [0, h) of the photo) and the float32 blend top, bot, val of mr_warp_normalize
+ *     col[c] = fminf(fmaxf(m[3c]*val[0] + m[3c+1]*val[1] + m[3c+2]*val[2] + b[c], 0), 255)     (float32, left to right)
+ *   blur != 0:  col[c] = the sum over j = -2..2 (outer) and i = -2..2 (inner), left to right starting from its first product, of
+ *                        k[(j+2)*5 + (i+2)] * comp(min(max(u + i, 0), Wv - 1), min(max(v + j, 0), H - 1))[c]              (float32)
+ *   blur == 0:  col = comp(u, v)
+ *   erase:  for e = 0 .. min(max(n_erase, 0), MR_AUG_MAX_ERASE) - 1 in order, with (x0, x1, y0, y1) = erase[4e .. 4e + 3]:
+ *           x0 <= u < x1 and y0 <= v < y1  ->  col[c] = erase_col[3e + c]
+ *   noise:  the rule of mr_synth_render, uint32 arithmetic modulo 2^32:  kk = (v*W + u)*3 + c;  r = lowbias32(seed + kk * 0x9E3779B9)
+ *           col[c] = col[c] + noise_amp * ((float)(r >> 8) * 0x1p-24f - 0.5f);  col[c] = fminf(fmaxf(col[c], 0), 255)
+ *   dst[row][c][v][u] = (float)((double)col[c] - mean[c]) / 255.f                         (as mr_resize_normalize ends)
+ * Columns u >= Wv get the normalised zero pixel, and so does every pixel of a descriptor whose `image` is not in [0, I).  A
+ * descriptor whose `row` is not in [0, N) writes nothing.  Only bytes src[offset + r*pitch + 3*k + c], 0 <= r < h, 0 <= k < w, of
+ * photos in the table are read, whatever the tables hold, and every loop is bounded by the limits above.  A row's pixels are a
+ * function of its own descriptor alone: not of M, of the descriptor's position in the call or of the launch geometry.
+ *
+ * Consequence: the IDENTITY descriptor -- g = identity, dx = dy = 0, m = identity, b = 0, blur = 0, n_erase = 0, noise_amp = 0,
+ * quant = 1, cu0 = cv0 = 0 -- writes the row that mr_quad_crop writes for the mr_crop_desc with the same image, dst_w, sx, sy,
+ * cu1, cv1 and h, bit for bit (X = cx, D = 1 and col = val are exact).
+ *
+ * One launch on `stream` (a workgroup per MR_SYNTH_TILE_H x MR_SYNTH_TILE_W tile of a descriptor's canvas; comp is evaluated once
+ * per pixel of the tile and its halo of 2), no allocation on the device, no synchronisation; capturable.  M == 0 returns MR_OK
+ * without a launch.  MR_ERR_ARG, nothing written: a NULL src, images, descs or dst with M > 0, I, M or N < 0, H or W < 1, more
+ * than INT_MAX tiles.  When `descs` is pinned host memory and `stream` is not being captured the entry point also refuses, before
+ * the launch, a `row` that two descriptors name, a `row` outside [0, N), an `image` outside [0, I), an `n_erase` outside
+ * [0, MR_AUG_MAX_ERASE] and a `dst_w` outside [1, W].  A table it cannot read is the kernel's to guard, as above; two descriptors
+ * of such a table that name one row leave that row as either of them. */
+#define MR_AUG_KNOTS 9
+#define MR_AUG_MAX_ERASE 4
+typedef struct mr_aug_desc {
+  int image;                    /* index into the mr_crop_image table */
+  int row;                      /* destination row of dst */
+  int dst_w;                    /* valid canvas columns; the rest is the zero canvas */
+  int quant;                    /* pixelation block in canvas pixels; 1 (or less) = off */
+  int blur;                     /* 0: k is not applied */
+  int n_erase;                  /* rectangles of `erase` in use, 0 .. MR_AUG_MAX_ERASE */
+  int seed;                     /* the 32 bits of the noise seed */
+  int reserved;                 /* 0 (keeps the doubles 8-byte aligned) */
+  double sx, sy;                /* cv2.resize scales of the frame, as mr_crop_desc */
+  double cu0, cu1, cv0, cv1;    /* the frame coordinate is clamped to [cu0, cu1] x [cv0, cv1] */
+  double g[9];                  /* jitter: output frame -> source frame, row major, projective */
+  double h[9];                  /* frame -> photo, row major, projective: identity for a stored crop, mr_crop_desc.h for a quad crop */
+  float dx[9], dy[9];           /* displacement of the sampling point in canvas pixels at MR_AUG_KNOTS knots over [0, dst_w] */
+  float m[9], b[3];             /* colour: col = m * val + b, row major */
+  float k[25];                  /* 5 x 5 blur kernel, row major (rows are v) */
+  float noise_amp;
+  int erase[16];                /* [MR_AUG_MAX_ERASE][4]: x0, x1, y0, y1 of [x0, x1) x [y0, y1) in canvas pixels */
+  float erase_col[12];          /* [MR_AUG_MAX_ERASE][3]: the fill colour of each rectangle */
+} mr_aug_desc;
+int mr_sizeof_aug_desc(void);
+int mr_rec_augment(const unsigned char* src, const void* images /* [I] mr_crop_image */, int I,
+                   const void* descs /* [M] mr_aug_desc */, int M, int N, int H, int W,
+                   double mean0, double mean1, double mean2, float* dst /* [N][3][H][W] */, hipStream_t stream);
+
 /* ---- Lexicon-constrained reading (csrc/lexicon.hip): the nearest lexicon word of every predicted id sequence, the rule of the
  * recognition benchmarks that are reported with lexicons (50 words per image, 1 k per set, "full"), and the membership test of
  * structure/measurers/sequence_recognition_measurer.py:59-64 (`in_lexicon`: distance 0).

@@ -93,7 +93,12 @@ def target_width(mode, image_size, shape):
 
 
 class DevicePipeline(object):
-    def __init__(self, image_size=(32, 128), mode='resize', charset=None, max_size=32, device=None):
+    """augmenter: a `RecognitionAugmenter` (data/recognition_augment.py), or None: the batch is the bare resize.  With one,
+    `pack` draws the batch's descriptor table (batch index: a counter of this pipeline, or `pack(..., index=)`) and stages it
+    with an `mr_crop_image` table of the samples; `_kernels` runs mr_resize_normalize over the batch as before and then
+    mr_rec_augment over the augmented rows, so the other rows keep their bits.  Labels and lengths are untouched."""
+
+    def __init__(self, image_size=(32, 128), mode='resize', charset=None, max_size=32, device=None, augmenter=None):
         if mode not in ('resize', 'pad'):
             raise NotImplementedError("DevicePipeline supports the batched modes 'resize' and 'pad' "
                                       "(keep_size / keep_ratio produce per-sample shapes)")
@@ -108,6 +113,9 @@ class DevicePipeline(object):
         self.tab_id = torch.from_numpy(ids).to(self.device)
         self.unknown = getattr(self.charset, "unknown", 1)
         self._staging = Staging()
+        self.augmenter = augmenter
+        self.index = 0                          # the next batch's number in the augmenter's stream
+        self._copied = {}                       # slot -> the event behind the last H2D copy of its staging buffer
 
     def _describe(self, shapes):
         """The `ImgDesc` table of images of the given (h, w); the offsets are the caller's to fill."""
@@ -129,22 +137,56 @@ class DevicePipeline(object):
         offs[1:] = np.cumsum([len(c) for c in cp])
         return [np.concatenate(cp + [np.zeros(0, dtype=np.int32)]), offs]
 
-    def pack(self, images, texts, slot=0):
+    def _draw(self, shapes, slot, index):
+        """With an augmenter: (the two further sections -- an `mr_crop_image` table, still to be filled from the `ImgDesc`
+        entries, and the batch's descriptor table --, the rows it augments).  Also waits until the slot's last copy has run:
+        the tables are drawn ahead of the device, and a slot must not be rewritten while its bytes are still to be copied."""
+        from .quad_crop import CropImage
+        if index is None:
+            index, self.index = self.index, self.index + 1
+        table, rows = self.augmenter.sample([s[:2] for s in shapes], self.image_size, self.mode, index)
+        if self._copied.get(slot) is not None:
+            self._copied[slot].synchronize()
+        return [(CropImage * max(len(shapes), 1))(), table], rows
+
+    @staticmethod
+    def _fill_crop_images(table, descs):
+        for t, d in zip(table, descs):
+            t.offset, t.pitch, t.h, t.w, t.reserved = d.offset, d.pitch, d.h, d.w, 0
+
+    def pack(self, images, texts, slot=0, index=None):
         """Host side: lay the decoded uint8 HWC images, their descriptors and the UTF-32 text out in ONE pinned
-        staging buffer (per prefetch slot).  Returns (pinned uint8 tensor, layout tuple); the layout's last element is the
-        `ImgDesc` array that was staged (`photos` reads it)."""
+        staging buffer (per prefetch slot).  Returns (pinned uint8 tensor, layout tuple); element 4 of the layout is the
+        `ImgDesc` array that was staged (`photos` reads it).  With an augmenter two further sections follow the text and the
+        layout ends with (slot, M, offset of the crop-image table, offset of the descriptor table, rows)."""
         n = len(images)
         check_images(images)
         descs = self._describe([im.shape for im in images])
-        lay = Sections(list(images) + [descs] + self._text(texts))
+        if self.augmenter is None:
+            lay = Sections(list(images) + [descs] + self._text(texts))
+            for d, off in zip(descs, lay.offsets):
+                d.offset = off
+            staged, _ = self._staging.stage(slot, lay)
+            return staged, (n,) + tuple(lay.offsets[n:]) + (descs,)
+        extra, rows = self._draw([im.shape for im in images], slot, index)
+        lay = Sections(list(images) + [descs] + self._text(texts) + extra)
         for d, off in zip(descs, lay.offsets):
             d.offset = off
+        self._fill_crop_images(extra[0], descs)
         staged, _ = self._staging.stage(slot, lay)
-        return staged, (n,) + tuple(lay.offsets[n:]) + (descs,)
+        return staged, (n,) + tuple(lay.offsets[n:n + 3]) + (descs, (slot, len(rows)) + tuple(lay.offsets[n + 3:]) + (rows,))
 
     def upload(self, staged, layout):
         """One async H2D copy of the staging buffer, then the two kernels, on the CURRENT stream."""
-        return self._kernels(upload(staged, self.device), layout)
+        dbuf = upload(staged, self.device)
+        self._mark_copied(layout)
+        return self._kernels(dbuf, layout)
+
+    def _mark_copied(self, layout):
+        """With an augmenter: record the event `pack` waits for before it stages the same slot again."""
+        if self.augmenter is not None:
+            ev = self._copied[layout[-1][0]] = torch.cuda.Event()
+            ev.record()
 
     def _kernels(self, dbuf, layout):
         """mr_resize_normalize and mr_encode_labels over the uploaded buffer."""
@@ -153,6 +195,10 @@ class DevicePipeline(object):
         image = torch.empty((n, 3, H, W), dtype=torch.float32, device=self.device)
         call("mr_resize_normalize", ptr(dbuf), dbuf.data_ptr() + desc_off, n, H, W, RGB_MEAN[0], RGB_MEAN[1],
              RGB_MEAN[2], ptr(image))
+        if self.augmenter is not None:
+            _, M, table_off, aug_off, _ = layout[-1]
+            call("mr_rec_augment", ptr(dbuf), dbuf.data_ptr() + table_off, n, dbuf.data_ptr() + aug_off, M, n, H, W,
+                 RGB_MEAN[0], RGB_MEAN[1], RGB_MEAN[2], ptr(image))
         label = torch.empty((n, self.max_size), dtype=torch.int32, device=self.device)
         length = torch.empty((n,), dtype=torch.int32, device=self.device)
         call("mr_encode_labels", dbuf.data_ptr() + text_off, dbuf.data_ptr() + offs_off, n, self.max_size,
@@ -181,14 +227,15 @@ class EncodedDevicePipeline(DevicePipeline):
     (csrc/jpeg_split.hip) and `host_above` applies to the others only; None: every item is one wavefront's, as before."""
 
     def __init__(self, image_size=(32, 128), mode='resize', charset=None, max_size=32, device=None, host_above=None,
-                 split_above=None):
-        super().__init__(image_size, mode, charset, max_size, device)
+                 split_above=None, augmenter=None):
+        super().__init__(image_size, mode, charset, max_size, device, augmenter)
         from .jpeg_decode import HOST_ABOVE, JpegDecoder
         self.decoder = JpegDecoder(self.device, 'BGR', HOST_ABOVE if host_above is None else host_above, split_above)
 
-    def pack(self, blobs, texts, slot=0):
-        """Host side: ONE staging buffer [blobs | plan | host-decoded pixels | descriptors | text].  The device buffer of
-        `upload` is [staged bytes | workspace | decoded pixels]; the `ImgDesc` offsets point into its decoded region for the
+    def pack(self, blobs, texts, slot=0, index=None):
+        """Host side: ONE staging buffer [blobs | plan | host-decoded pixels | descriptors | text], with an augmenter
+        [... | crop-image table | augmentation descriptors] (the layout then ends as `DevicePipeline.pack`'s does).  The
+        device buffer of `upload` is [staged bytes | workspace | decoded pixels]; the `ImgDesc` offsets point into its decoded region for the
         images the device decodes and at the staged pixels for the others.  Raises ValueError for blobs whose headers are
         corrupt."""
         from .jpeg_decode import plan_layout, stage_plan
@@ -197,18 +244,28 @@ class EncodedDevicePipeline(DevicePipeline):
             raise ValueError("corrupt JPEG data at batch indices %s" % plan.corrupt())
         n = plan.n
         descs = self._describe([plan.shape(i) for i in range(n)])
-        lay, jpeg = plan_layout(plan, [descs] + self._text(texts))
+        if self.augmenter is None:
+            lay, jpeg = plan_layout(plan, [descs] + self._text(texts))
+            at = dict(zip(sorted(plan.host), lay.offsets[lay.first:]))
+            for i, d in enumerate(descs):
+                d.offset = at[i] if i in at else jpeg[4] + plan.images[i].out_off
+            staged, _ = stage_plan(plan, lay, self._staging, slot)
+            return staged, (n,) + tuple(lay.offsets[-3:]) + (descs, jpeg)
+        extra, rows = self._draw([plan.shape(i) for i in range(n)], slot, index)
+        lay, jpeg = plan_layout(plan, [descs] + self._text(texts) + extra)
         at = dict(zip(sorted(plan.host), lay.offsets[lay.first:]))
         for i, d in enumerate(descs):
             d.offset = at[i] if i in at else jpeg[4] + plan.images[i].out_off
+        self._fill_crop_images(extra[0], descs)
         staged, _ = stage_plan(plan, lay, self._staging, slot)
-        return staged, (n,) + tuple(lay.offsets[-3:]) + (descs, jpeg)
+        return staged, (n,) + tuple(lay.offsets[-5:-2]) + (descs, jpeg, (slot, len(rows)) + tuple(lay.offsets[-2:]) + (rows,))
 
     def upload(self, staged, layout):
         """One device buffer, one async H2D copy of the staged part, then mr_jpeg_decode and the two kernels of
         `DevicePipeline`, on the CURRENT stream."""
         from .jpeg_decode import upload_and_launch
         dbuf, status = upload_and_launch(staged, layout[5], self.device)
+        self._mark_copied(layout)
         batch = self._kernels(dbuf, layout)
         batch['jpeg_status'] = status
         return batch

@@ -207,13 +207,17 @@ def plan_crop(shape, quad, image_size=(64, 512), mode='resize', rectify='min_are
                     cu1=float(Wr - 1), cv1=float(Hr - 1), h9=m.reshape(9).copy(), crop_map=crop_map)
 
 
-CropLayout = namedtuple("CropLayout", "M I table_off desc_off index_off quad_off resident plans dropped")
+# aug: None, or with an augmenter (slot, number of augmented crops, offset of their mr_aug_desc table, their rows)
+CropLayout = namedtuple("CropLayout", "M I table_off desc_off index_off quad_off resident plans dropped aug", defaults=(None,))
 
 
 class QuadCropper(object):
-    """`ImageCropper` on the GPU (the defaults are its defaults); see the module docstring."""
+    """`ImageCropper` on the GPU (the defaults are its defaults); see the module docstring.  augmenter: a
+    `RecognitionAugmenter` (data/recognition_augment.py), or None.  With one, `pack` draws a descriptor per planned crop whose
+    frame -> photo map is the plan's `h9` (batch index: a counter of this cropper, or `pack(..., index=)`), and `upload` runs
+    mr_rec_augment over the augmented rows behind mr_quad_crop: augmented word crops straight from annotated scenes."""
 
-    def __init__(self, image_size=(64, 512), mode='resize', rectify='min_area_rect', device=None):
+    def __init__(self, image_size=(64, 512), mode='resize', rectify='min_area_rect', device=None, augmenter=None):
         if mode not in ('resize', 'pad'):
             raise NotImplementedError("QuadCropper supports the batched modes 'resize' and 'pad' "
                                       "(keep_size / keep_ratio produce per-sample shapes)")
@@ -225,8 +229,11 @@ class QuadCropper(object):
         self.device = torch.device(device if device is not None else "cuda")
         load()
         self._staging = Staging()
+        self.augmenter = augmenter
+        self.index = 0                          # the next batch's number in the augmenter's stream
+        self._copied = {}                       # slot -> the event behind the last H2D copy of its staging buffer
 
-    def pack(self, images, quads, slot=0, plans=None):
+    def pack(self, images, quads, slot=0, plans=None, index=None):
         """Host side: plan every quadrilateral and lay the numpy photos, the photo table, the crop descriptors, the source
         indices (int32 [M]) and the quads (float64 [M][4][2]) out in ONE pinned staging buffer (per prefetch slot).  Photos that
         are CUDA tensors are not copied: their table entries are completed by `upload`.  `plans`: ready-made
@@ -270,15 +277,27 @@ class QuadCropper(object):
         descs = (CropDesc * max(M, 1))()
         for m, (i, plan, _) in enumerate(kept):
             plan.fill(descs[m], i)
-        lay = Sections([im for _, im in staged_photos] + [
+        sections = [im for _, im in staged_photos] + [
             table, descs, np.array([i for i, _, _ in kept], dtype=np.int32),
-            np.asarray([q for _, _, q in kept], dtype=np.float64).reshape(-1)], pad_end=True)
+            np.asarray([q for _, _, q in kept], dtype=np.float64).reshape(-1)]
+        aug = None
+        if self.augmenter is not None:
+            if index is None:
+                index, self.index = self.index, self.index + 1
+            aug_table, rows = self.augmenter.sample([plan for _, plan, _ in kept], self.image_size, self.mode, index,
+                                                    images=[i for i, _, _ in kept])
+            sections.append(aug_table)
+            if self._copied.get(slot) is not None:      # drawn ahead of the device: the slot's last copy must have run
+                self._copied[slot].synchronize()
+        lay = Sections(sections, pad_end=True)
         for (i, _), off in zip(staged_photos, lay.offsets):
             table[i].offset = off
         staged, _ = self._staging.stage(slot, lay)
-        table_off, desc_off, index_off, quad_off = lay.offsets[len(staged_photos):]
+        table_off, desc_off, index_off, quad_off = lay.offsets[len(staged_photos):len(staged_photos) + 4]
+        if self.augmenter is not None:
+            aug = (slot, len(rows), lay.offsets[-1], rows)
         return staged, CropLayout(M, n, table_off, desc_off, index_off, quad_off, resident,
-                                  [plan for _, plan, _ in kept], dropped)
+                                  [plan for _, plan, _ in kept], dropped, aug)
 
     def upload(self, staged, layout):
         """One async H2D copy of the staging buffer, then the one launch, on the CURRENT stream (resident photos must be
@@ -292,9 +311,15 @@ class QuadCropper(object):
             for i, im in layout.resident:
                 offsets[i] = im.data_ptr() - dbuf.data_ptr()
         dbuf = upload(staged, self.device, place_resident if layout.resident else None)
+        if layout.aug is not None:
+            ev = self._copied[layout.aug[0]] = torch.cuda.Event()
+            ev.record()
         image = torch.empty((M, 3, H, W), dtype=torch.float32, device=self.device)
         call("mr_quad_crop", ptr(dbuf), dbuf.data_ptr() + layout.table_off, layout.I, dbuf.data_ptr() + layout.desc_off, M,
              H, W, RGB_MEAN[0], RGB_MEAN[1], RGB_MEAN[2], ptr(image))
+        if layout.aug is not None:
+            call("mr_rec_augment", ptr(dbuf), dbuf.data_ptr() + layout.table_off, layout.I, dbuf.data_ptr() + layout.aug[2],
+                 layout.aug[1], M, H, W, RGB_MEAN[0], RGB_MEAN[1], RGB_MEAN[2], ptr(image))
         index = dbuf[layout.index_off:layout.index_off + 4 * M].view(torch.int32)
         quad = dbuf[layout.quad_off:layout.quad_off + 64 * M].view(torch.float64).view(M, 4, 2)
         return {'image': image, 'index': index, 'quad': quad, 'dropped': list(layout.dropped),

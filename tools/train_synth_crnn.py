@@ -3,6 +3,8 @@
 Prints the loss curve (mean of every 100 steps), the greedy word accuracy on held-out rendered words (batches the training never
 drew: another seed), and what `TextReader` reads on a rendered scene with the trained recogniser and a stub detector that returns
 the ground-truth quads.  A report, not a test: nothing here is asserted.
+  python tools/train_synth_crnn.py --augment [--steps 3000] [--batch 256] [--out FILE]
+is another report in the place of that one: the A/B of the recognition augmentation (`augment_ab` below).
 The word list is built into this file (no dataset, no download); the font is Pillow's built-in one."""
 import argparse
 import os
@@ -73,11 +75,52 @@ def accuracy(model, charset, gen, batches, n):
     return right, total, wrong
 
 
+def augment_ab(args, charset, atlas, say):
+    """--augment: train twice on crops rendered in a PLAIN style -- no rotation, shear, perspective, shadow, blur or noise -- once
+    as rendered and once through `RecognitionAugmenter` + `augment_crops`, and read held-out crops in the default `SynthStyle`
+    with both.  What the augmentation is for, on the only labelled data this repository can make: a recogniser that has seen
+    upright clean words only meets slanted, blurred, noisy ones."""
+    from megreader_amd.data import RecognitionAugmenter, augment_crops
+    plain = SynthStyle(rotation=(0.0, 0.0), shear=(0.0, 0.0), perspective=0.0, shadow_prob=0.0, blur_sigma=(0.0, 0.0),
+                       noise=(0.0, 0.0))
+    size = (32, 128)
+    say("%s; CRNN, bf16, FusedAdam lr %g, %d steps of %d crops at 32 x 128 rendered in a plain style, %d words; held-out crops in "
+        "the default style" % (torch.cuda.get_device_name(0), args.lr, args.steps, args.batch, len(WORDS)))
+    for name, aug in (("without the augmenter", None), ("with the augmenter", RecognitionAugmenter(seed=1, p=0.8))):
+        torch.manual_seed(0)
+        model = Model().cuda().train()
+        opt = FusedAdam(model.parameters(), lr=args.lr)
+        train = SynthText(charset, [atlas], WORDS, image_size=size, style=plain, seed=0)
+        held_out = SynthText(charset, [atlas], WORDS, image_size=size, seed=12345)
+        t0 = time.perf_counter()
+        window = []
+        for step in range(args.steps):
+            batch = train.batch(args.batch, photos=aug is not None)
+            image = batch['image']
+            if aug is not None:
+                table, _ = aug.sample([size] * args.batch, size, 'resize', step)
+                image = augment_crops(batch['photos'], table, size, out=image)
+            opt.zero_grad()
+            loss, _ = model(image, targets=batch['label'], lengths=batch['length'].long(), train=True)
+            loss.mean().backward()
+            opt.step()
+            window.append(loss.mean().detach())
+            if (step + 1) % 500 == 0 or step + 1 == args.steps:
+                say("  %s: steps %5d-%5d  mean loss %.4f   (%.0f s)" % (name, step + 1 - len(window), step,
+                                                                       float(torch.stack(window).mean()), time.perf_counter() - t0))
+                window = []
+        right, total, _ = accuracy(model, charset, held_out, 8, 256)
+        say("%s: greedy word accuracy on %d held-out crops in the default style: %d right = %.2f %%"
+            % (name, total, right, 100.0 * right / total))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3000)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--augment", action="store_true", help="the A/B report of the recognition augmentation in the place of the "
+                    "default run")
     ap.add_argument("--out")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -91,6 +134,13 @@ def main():
     charset = EnglishCharset()
     atlas = GlyphAtlas.from_font(charset, size=48)
     mr.set_compute_dtype(torch.bfloat16)
+    if args.augment:
+        augment_ab(args, charset, atlas, say)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     torch.manual_seed(0)
     model = Model().cuda().train()
     opt = FusedAdam(model.parameters(), lr=args.lr)
