@@ -1,6 +1,7 @@
 // CTC prefix beam search (Graves; Hannun et al., "First-pass large vocabulary continuous speech recognition using bi-directional
-// recurrent DNNs", Algorithm 1, without the language model): the n most probable strings of a CTC posterior with their
-// log-probabilities.  The rule is written out in include/megreader_hip.h (mr_ctc_beam_search); this file is two kernels.
+// recurrent DNNs", Algorithm 1): the n most probable strings of a CTC posterior with their log-probabilities, by the posterior
+// alone (mr_ctc_beam_search) or ranked with a character n-gram model (mr_ctc_beam_search_lm).  The rules are written out in
+// include/megreader_hip.h; this file is two kernels, the second with a compile-time flag for the model.
 //
 //   ctc_beam_columns_kernel   one wave per column (n, t): the top_classes symbols of the column by (lp descending, id ascending)
 //                             into the workspace lists sym_id / sym_lp [N, T, Kc] (-1 / -inf past the eligible ones).  A lane keeps
@@ -8,11 +9,15 @@
 //                             that owned it looks for its next one.  The column's logs are taken once and kept in LDS (one f32 per
 //                             class, a lane rescans only what it wrote) up to CTCB_STAGE_MAX classes; a wider alphabet
 //                             takes them again from global memory on a rescan: slow, exact.
-//   ctc_beam_kernel           one wave per row, sequential in t.  Lane i holds beam entry i (pb, pnb, total, last, length, node,
+//   ctc_beam_rows_kernel<LM>  one wave per row, sequential in t.  Lane i holds beam entry i (pb, pnb, total, last, length, node,
 //                             parent node) in registers, mirrored in LDS for the other lanes.  Per column: the stay candidates by
 //                             their own lanes, the B * Kc extensions spread over the lanes, one 64-bit key (ordered total << 32 |
 //                             ~index) per candidate in LDS; B rounds of wave maximum pick the survivors in descending order (the
 //                             same descent as above), so the beam is always sorted and there is no barrier between waves anywhere.
+//                             LM = true adds, and LM = false compiles none of: a model state and an f32 sum lm per beam entry,
+//                             total + lm as what a key orders, one lookup in the model (a read-only automaton) per extension, the
+//                             end-of-string term and a last ranking of the survivors by total + lm, the two outputs more.  The
+//                             masses, the columns and the trie are the same either way.
 // Strings are a persistent parent-pointer trie per row in the caller's workspace: an open-addressing table keyed by the exact pair
 // (parent node, symbol), whose slot index IS the node id.  A prefix that left the beam and comes back finds its old node, so "the
 // extension p + c is beam entry q" is `q.parent == p.node && q.last == c` -- exact, no string hash.  An extension can only meet a
@@ -20,9 +25,6 @@
 // and for its last symbol among the column's, adds that extension's mass to its own pnb' and strikes the extension's key out.
 // Only the <= B survivors that are new are looked up or created (64-bit compare-and-swap, probes read past the L1); node ids depend
 // on the probing order and never reach an output.  The strings are unwound once at the end.
-//   ctc_beam_lm_kernel        the row kernel WITH the language model (mr_ctc_beam_search_lm): a sibling, so that the one above stays
-//                             the code it was.  Same columns, same trie; a model state and an f32 sum per beam entry, the candidate
-//                             keys order total + lm, the model is a read-only automaton looked up once per extension.
 #include <limits.h>
 #include "device.h"
 #include "ctc_posterior.h"
@@ -110,128 +112,7 @@ __device__ __forceinline__ int ctcb_find_or_create(u64* tab, unsigned slots, int
   return 0;
 }
 
-template <typename PT>
-__global__ __launch_bounds__(64) void ctc_beam_kernel(const PT* pred, long long sn, long long sc, long long st, int C, int T,
-                                                      int log_probs, int blank, int B, int K, int Kc, const int* sym_id,
-                                                      const float* sym_lp, u64* tables, unsigned slots, int* ids, int* lengths,
-                                                      float* scores, int* count) {
-  // candidate keys: [0, 64) the stay of beam entry q; 64 + p * kc + j the extension of entry p by the column's j-th symbol
-  __shared__ u64 keys[MR_CTC_BEAM_MAX + MR_CTC_BEAM_MAX * MR_CTC_BEAM_TOP_MAX];
-  __shared__ float b_pb[64], b_pnb[64], b_tot[64], s_pb[64], s_pnb[64], c_lp[64];
-  __shared__ int b_last[64], b_len[64], b_node[64], b_par[64], c_id[64];
-  const int lane = threadIdx.x, n = blockIdx.x;
-  u64* tab = tables + (long long)n * slots;
-  for (unsigned i = lane; i < slots; i += 64) tab[i] = 0ull;
-  // beam entry `lane`: the start state is the empty prefix alone
-  float pb = lane == 0 ? 0.f : CTC_NEG_INF, pnb = CTC_NEG_INF, tot = pb;
-  int last = -1, len = 0, node = 0, par = -1, nb = 1;
-  __syncthreads();   // the zeroed table has landed before the first compare-and-swap
-  for (int t = 0; t < T; ++t) {
-    const PT* col = pred + (long long)n * sn + (long long)t * st;
-    const long long list = ((long long)n * T + t) * Kc;
-    const int cid = lane < Kc ? sym_id[list + lane] : -1;
-    const float clp = lane < Kc ? sym_lp[list + lane] : CTC_NEG_INF;
-    const float lpb = ctc_lp_at(col, sc, blank, log_probs != 0);
-    const int kc = __popcll(__ballot(cid >= 0));   // the eligible ones come first
-    b_pb[lane] = pb; b_pnb[lane] = pnb; b_tot[lane] = tot;
-    b_last[lane] = last; b_len[lane] = len; b_node[lane] = node; b_par[lane] = par;
-    c_id[lane] = cid; c_lp[lane] = clp;
-    __syncthreads();
-    // stay: lane q, with the one extension that spells the same string
-    u64 key = 0ull;
-    int merged = -1;
-    if (lane < nb) {
-      const float npb = tot + lpb;
-      float npnb = CTC_NEG_INF;
-      if (len > 0) {
-        int jl = -1;
-        for (int j = 0; j < kc; ++j)
-          if (c_id[j] == last) jl = j;
-        npnb = pnb + (jl >= 0 ? c_lp[jl] : ctc_lp_at(col, sc, last, log_probs != 0));   // the same bits either way
-        if (jl >= 0) {
-          int p = -1;
-          for (int i = 0; i < nb; ++i)
-            if (b_node[i] == par) p = i;
-          if (p >= 0) {
-            const float from = (b_len[p] > 0 && b_last[p] == last) ? b_pb[p] : b_tot[p];
-            npnb = ctc_lse2(npnb, from + c_lp[jl]);
-            merged = p * kc + jl;
-          }
-        }
-      }
-      s_pb[lane] = npb; s_pnb[lane] = npnb;
-      key = ctc_key(ctc_lse2(npb, npnb), (unsigned)lane, CTCB_MERGE_ZEROS);
-    }
-    keys[lane] = key;
-    const int ne = nb * kc;
-    for (int e = lane; e < ne; e += 64) {
-      const int p = e / kc, j = e - p * kc;
-      const float from = (b_len[p] > 0 && b_last[p] == c_id[j]) ? b_pb[p] : b_tot[p];
-      keys[64 + e] = ctc_key(from + c_lp[j], (unsigned)(64 + e), CTCB_MERGE_ZEROS);
-    }
-    __syncthreads();
-    if (merged >= 0) keys[64 + merged] = 0ull;
-    __syncthreads();
-    // keep: the B greatest in descending order; lane r takes the r-th
-    u64 mine = keys[lane];
-    for (int e = lane; e < ne; e += 64) mine = keys[64 + e] > mine ? keys[64 + e] : mine;
-    u64 got = 0ull;
-    int kept = 0;
-    for (int r = 0; r < B; ++r) {
-      const u64 w = ctc_wave_max(mine);
-      if (w == 0ull) break;   // (wave-uniform) nothing finite is left
-      if (lane == r) got = w;
-      ++kept;
-      if (mine == w) {
-        u64 m = keys[lane] < w ? keys[lane] : 0ull;
-        for (int e = lane; e < ne; e += 64) {
-          const u64 k = keys[64 + e];
-          if (k < w && k > m) m = k;
-        }
-        mine = m;
-      }
-    }
-    nb = kept;
-    if (lane < nb) {
-      const int idx = (int)(0xffffffffu - (unsigned)(got & 0xffffffffull));
-      tot = ctc_unordered((unsigned)(got >> 32));
-      if (idx < 64) {
-        pb = s_pb[idx]; pnb = s_pnb[idx]; last = b_last[idx]; len = b_len[idx]; node = b_node[idx]; par = b_par[idx];
-      } else {
-        const int e = idx - 64, p = e / kc, j = e - p * kc;
-        pb = CTC_NEG_INF; pnb = tot; last = c_id[j]; len = b_len[p] + 1; par = b_node[p];
-        node = ctcb_find_or_create(tab, slots, par, last);
-      }
-    } else {
-      pb = pnb = tot = CTC_NEG_INF; last = -1; len = 0; node = 0; par = -1;
-    }
-    __syncthreads();   // every read of the old beam is done before the next column overwrites it
-  }
-  // the K best are lanes 0 .. K-1 already
-  const bool have = lane < nb && lane < K;
-  b_len[lane] = have ? len : 0;
-  if (lane < K) {
-    lengths[(long long)n * K + lane] = have ? len : 0;
-    scores[(long long)n * K + lane] = have ? tot : CTC_NEG_INF;
-  }
-  if (lane == 0) count[n] = min(nb, K);
-  __syncthreads();
-  int* out = ids + (long long)n * K * T;
-  for (long long i = lane; i < (long long)K * T; i += 64) {
-    const int k = (int)(i / T), tt = (int)(i - (long long)k * T);
-    if (tt >= b_len[k]) out[i] = blank;
-  }
-  if (have) {
-    int nd = node;
-    for (int i = len - 1; i >= 0 && nd > 0; --i) {
-      const u64 entry = __hip_atomic_load(tab + (nd - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      out[(long long)lane * T + i] = (int)(unsigned)(entry & 0xffffffffull) - 1;
-      nd = (int)(unsigned)(entry >> 32);
-    }
-  }
-}
-
-// ---- with a character n-gram model (mr_ctc_beam_search_lm): the same search, ranked by total + lm ----
+// ---- the character n-gram model of mr_ctc_beam_search_lm ----
 
 // the model as the header lays it out: a finite automaton, its arcs in an open-addressing table keyed by (state, symbol)
 struct CtcbModel {
@@ -296,38 +177,45 @@ __device__ __forceinline__ float ctcb_lm_add(const CtcbModel& lm, float sum, flo
 // a total as mr_ctc_beam_search takes it back out of a key: -0 is +0
 __device__ __forceinline__ float ctcb_plus_zero(float v) { return v == 0.f ? 0.f : v; }
 
-// ctc_beam_kernel with two more registers per beam entry, the model state and the f32 sum lm, mirrored in LDS like the others.
-// The masses are computed exactly as there; only the candidate keys order total + lm, so a survivor's total is taken again from
-// its masses (the same operations, the same bits) where ctc_beam_kernel reads it back out of the key.  The lanes that build the
-// extension keys look the model up, one lookup per (p, j), independent of each other; the <= B lanes whose survivor is an
-// extension repeat theirs for the new state instead of keeping 4 096 states in LDS.
-template <typename PT>
-__global__ __launch_bounds__(64) void ctc_beam_lm_kernel(const PT* pred, long long sn, long long sc, long long st, int C, int T,
-                                                         int log_probs, int blank, int B, int K, int Kc, const int* sym_id,
-                                                         const float* sym_lp, u64* tables, unsigned slots, CtcbModel lm, int* ids,
-                                                         int* lengths, float* scores, float* ctc_scores, float* lm_scores,
-                                                         int* count) {
+// The row kernel.  LM: with the model -- two more values per beam entry, the model state and the f32 sum lm, mirrored in LDS like
+// the others.  The masses are computed the same either way; with the model the candidate keys order total + lm, so a survivor's
+// total is taken again from its masses (the same operations, the same bits) where the plain search reads it back out of the key.
+// The lanes that build the extension keys look the model up, one lookup per (p, j), independent of each other; the <= B lanes whose
+// survivor is an extension repeat theirs for the new state instead of keeping 4 096 states in LDS.
+template <typename PT, bool LM>
+__global__ __launch_bounds__(64) void ctc_beam_rows_kernel(const PT* pred, long long sn, long long sc, long long st, int C, int T,
+                                                           int log_probs, int blank, int B, int K, int Kc, const int* sym_id,
+                                                           const float* sym_lp, u64* tables, unsigned slots, CtcbModel lm, int* ids,
+                                                           int* lengths, float* scores, float* ctc_scores, float* lm_scores,
+                                                           int* count) {
+  // candidate keys: [0, 64) the stay of beam entry q; 64 + p * kc + j the extension of entry p by the column's j-th symbol
   __shared__ u64 keys[MR_CTC_BEAM_MAX + MR_CTC_BEAM_MAX * MR_CTC_BEAM_TOP_MAX];
-  __shared__ float b_pb[64], b_pnb[64], b_tot[64], b_lm[64], s_pb[64], s_pnb[64], c_lp[64];
-  __shared__ int b_last[64], b_len[64], b_node[64], b_par[64], b_state[64], c_id[64];
+  __shared__ float b_pb[64], b_pnb[64], b_tot[64], s_pb[64], s_pnb[64], c_lp[64];
+  __shared__ int b_last[64], b_len[64], b_node[64], b_par[64], c_id[64];
+  __shared__ float b_lm[LM ? 64 : 1];   // without the model nothing refers to these two: they take no LDS
+  __shared__ int b_state[LM ? 64 : 1];
   const int lane = threadIdx.x, n = blockIdx.x;
   u64* tab = tables + (long long)n * slots;
   for (unsigned i = lane; i < slots; i += 64) tab[i] = 0ull;
+  // beam entry `lane`: the start state is the empty prefix alone
   float pb = lane == 0 ? 0.f : CTC_NEG_INF, pnb = CTC_NEG_INF, tot = pb, lms = 0.f;
-  int last = -1, len = 0, node = 0, par = -1, nb = 1, state = lm.start_state;
-  __syncthreads();
+  int last = -1, len = 0, node = 0, par = -1, nb = 1, state = LM ? lm.start_state : 0;
+  // what the extension of entry p by symbol c grows out of: a repeat of p's last symbol only out of the paths that end in a blank
+  const auto from = [&](int p, int c) { return (b_len[p] > 0 && b_last[p] == c) ? b_pb[p] : b_tot[p]; };
+  __syncthreads();   // the zeroed table has landed before the first compare-and-swap
   for (int t = 0; t < T; ++t) {
     const PT* col = pred + (long long)n * sn + (long long)t * st;
     const long long list = ((long long)n * T + t) * Kc;
     const int cid = lane < Kc ? sym_id[list + lane] : -1;
     const float clp = lane < Kc ? sym_lp[list + lane] : CTC_NEG_INF;
     const float lpb = ctc_lp_at(col, sc, blank, log_probs != 0);
-    const int kc = __popcll(__ballot(cid >= 0));
-    b_pb[lane] = pb; b_pnb[lane] = pnb; b_tot[lane] = tot; b_lm[lane] = lms;
-    b_last[lane] = last; b_len[lane] = len; b_node[lane] = node; b_par[lane] = par; b_state[lane] = state;
+    const int kc = __popcll(__ballot(cid >= 0));   // the eligible ones come first
+    b_pb[lane] = pb; b_pnb[lane] = pnb; b_tot[lane] = tot;
+    b_last[lane] = last; b_len[lane] = len; b_node[lane] = node; b_par[lane] = par;
+    if constexpr (LM) { b_lm[lane] = lms; b_state[lane] = state; }
     c_id[lane] = cid; c_lp[lane] = clp;
     __syncthreads();
-    // stay: the masses of ctc_beam_kernel; the string is the same one, so are its state and lm
+    // stay: lane q, with the one extension that spells the same string (so its state and lm are the same too)
     u64 key = 0ull;
     int merged = -1;
     if (lane < nb) {
@@ -337,41 +225,45 @@ __global__ __launch_bounds__(64) void ctc_beam_lm_kernel(const PT* pred, long lo
         int jl = -1;
         for (int j = 0; j < kc; ++j)
           if (c_id[j] == last) jl = j;
-        npnb = pnb + (jl >= 0 ? c_lp[jl] : ctc_lp_at(col, sc, last, log_probs != 0));
+        npnb = pnb + (jl >= 0 ? c_lp[jl] : ctc_lp_at(col, sc, last, log_probs != 0));   // the same bits either way
         if (jl >= 0) {
           int p = -1;
           for (int i = 0; i < nb; ++i)
             if (b_node[i] == par) p = i;
           if (p >= 0) {
-            const float from = (b_len[p] > 0 && b_last[p] == last) ? b_pb[p] : b_tot[p];
-            npnb = ctc_lse2(npnb, from + c_lp[jl]);
+            npnb = ctc_lse2(npnb, from(p, last) + c_lp[jl]);
             merged = p * kc + jl;
           }
         }
       }
       s_pb[lane] = npb; s_pnb[lane] = npnb;
-      key = ctc_key(__fadd_rn(ctc_lse2(npb, npnb), lms), (unsigned)lane, CTCB_MERGE_ZEROS);
+      float ranked = ctc_lse2(npb, npnb);
+      if constexpr (LM) ranked = __fadd_rn(ranked, lms);
+      key = ctc_key(ranked, (unsigned)lane, CTCB_MERGE_ZEROS);
     }
     keys[lane] = key;
     const int ne = nb * kc;
     for (int e = lane; e < ne; e += 64) {
       const int p = e / kc, j = e - p * kc;
-      const float from = (b_len[p] > 0 && b_last[p] == c_id[j]) ? b_pb[p] : b_tot[p];
-      int next;
-      const float g = ctcb_lm_step(lm, b_state[p], c_id[j], next);
-      const float ranked = g > CTC_NEG_INF ? __fadd_rn(from + c_lp[j], ctcb_lm_add(lm, b_lm[p], g)) : CTC_NEG_INF;
+      float ranked = from(p, c_id[j]) + c_lp[j];
+      if constexpr (LM) {
+        int next;
+        const float g = ctcb_lm_step(lm, b_state[p], c_id[j], next);
+        ranked = g > CTC_NEG_INF ? __fadd_rn(ranked, ctcb_lm_add(lm, b_lm[p], g)) : CTC_NEG_INF;
+      }
       keys[64 + e] = ctc_key(ranked, (unsigned)(64 + e), CTCB_MERGE_ZEROS);
     }
     __syncthreads();
     if (merged >= 0) keys[64 + merged] = 0ull;
     __syncthreads();
+    // keep: the B greatest in descending order; lane r takes the r-th
     u64 mine = keys[lane];
     for (int e = lane; e < ne; e += 64) mine = keys[64 + e] > mine ? keys[64 + e] : mine;
     u64 got = 0ull;
     int kept = 0;
     for (int r = 0; r < B; ++r) {
       const u64 w = ctc_wave_max(mine);
-      if (w == 0ull) break;
+      if (w == 0ull) break;   // (wave-uniform) nothing finite is left
       if (lane == r) got = w;
       ++kept;
       if (mine == w) {
@@ -386,52 +278,66 @@ __global__ __launch_bounds__(64) void ctc_beam_lm_kernel(const PT* pred, long lo
     nb = kept;
     if (lane < nb) {
       const int idx = (int)(0xffffffffu - (unsigned)(got & 0xffffffffull));
+      if constexpr (!LM) tot = ctc_unordered((unsigned)(got >> 32));   // the key holds the total itself (-0 as +0)
       if (idx < 64) {
         pb = s_pb[idx]; pnb = s_pnb[idx]; last = b_last[idx]; len = b_len[idx]; node = b_node[idx]; par = b_par[idx];
-        state = b_state[idx]; lms = b_lm[idx];
-        tot = ctcb_plus_zero(ctc_lse2(pb, pnb));
+        if constexpr (LM) {
+          state = b_state[idx]; lms = b_lm[idx];
+          tot = ctcb_plus_zero(ctc_lse2(pb, pnb));
+        }
       } else {
         const int e = idx - 64, p = e / kc, j = e - p * kc;
-        const float from = (b_len[p] > 0 && b_last[p] == c_id[j]) ? b_pb[p] : b_tot[p];
-        tot = ctcb_plus_zero(from + c_lp[j]);
+        if constexpr (LM) tot = ctcb_plus_zero(from(p, c_id[j]) + c_lp[j]);
         pb = CTC_NEG_INF; pnb = tot; last = c_id[j]; len = b_len[p] + 1; par = b_node[p];
-        lms = ctcb_lm_add(lm, b_lm[p], ctcb_lm_step(lm, b_state[p], last, state));
+        if constexpr (LM) lms = ctcb_lm_add(lm, b_lm[p], ctcb_lm_step(lm, b_state[p], last, state));
         node = ctcb_find_or_create(tab, slots, par, last);
       }
     } else {
-      pb = pnb = tot = CTC_NEG_INF; last = -1; len = 0; node = 0; par = -1; state = 0; lms = 0.f;
+      pb = pnb = tot = CTC_NEG_INF; last = -1; len = 0; node = 0; par = -1;
+      if constexpr (LM) { state = 0; lms = 0.f; }
     }
+    __syncthreads();   // every read of the old beam is done before the next column overwrites it
+  }
+  // entry `lane` is returned in place `rank` if `have`; `alive` entries are left.  Without the model the beam is in order already
+  int rank = lane, alive = nb;
+  bool have = lane < nb && lane < K;
+  float score = tot;
+  if constexpr (LM) {
+    // the end of the string, then the survivors' ranks by total + lm: at most 64 keys, one per lane, each lane counts the greater
+    if (lm.end != 0 && lane < nb && (unsigned)state < (unsigned)lm.states)
+      lms = __fadd_rn(lms, __fmul_rn(lm.alpha, lm.end_lp[state]));
+    score = lane < nb ? __fadd_rn(tot, lms) : CTC_NEG_INF;
+    keys[lane] = ctc_key(score, (unsigned)lane, CTCB_MERGE_ZEROS);
     __syncthreads();
+    rank = alive = 0;
+    for (int i = 0; i < 64; ++i) {
+      rank += keys[i] > keys[lane] ? 1 : 0;
+      alive += keys[i] != 0ull ? 1 : 0;
+    }
+    have = keys[lane] != 0ull && rank < K;
+    __syncthreads();   // b_len is read as the ranks' lengths below, the keys are done with
   }
-  // the end of the string, then the survivors' ranks by total + lm: at most 64 keys, one per lane, each lane counts the greater
-  if (lm.end != 0 && lane < nb && (unsigned)state < (unsigned)lm.states)
-    lms = __fadd_rn(lms, __fmul_rn(lm.alpha, lm.end_lp[state]));
-  const float ranked = lane < nb ? __fadd_rn(tot, lms) : CTC_NEG_INF;
-  keys[lane] = ctc_key(ranked, (unsigned)lane, CTCB_MERGE_ZEROS);
-  __syncthreads();
-  int rank = 0, alive = 0;
-  for (int i = 0; i < 64; ++i) {
-    rank += keys[i] > keys[lane] ? 1 : 0;
-    alive += keys[i] != 0ull ? 1 : 0;
-  }
-  const bool have = keys[lane] != 0ull && rank < K;
-  __syncthreads();   // b_len is read as the ranks' lengths below, the keys are done with
+  const int returned = min(alive, K);
   if (lane < K) b_len[lane] = 0;
   __syncthreads();
   if (have) b_len[rank] = len;
-  if (lane < K && lane >= min(alive, K)) {
+  if (lane < K && lane >= returned) {
     lengths[(long long)n * K + lane] = 0;
     scores[(long long)n * K + lane] = CTC_NEG_INF;
-    ctc_scores[(long long)n * K + lane] = CTC_NEG_INF;
-    lm_scores[(long long)n * K + lane] = CTC_NEG_INF;
+    if constexpr (LM) {
+      ctc_scores[(long long)n * K + lane] = CTC_NEG_INF;
+      lm_scores[(long long)n * K + lane] = CTC_NEG_INF;
+    }
   }
   if (have) {
     lengths[(long long)n * K + rank] = len;
-    scores[(long long)n * K + rank] = ranked;
-    ctc_scores[(long long)n * K + rank] = tot;
-    lm_scores[(long long)n * K + rank] = lms;
+    scores[(long long)n * K + rank] = score;
+    if constexpr (LM) {
+      ctc_scores[(long long)n * K + rank] = tot;
+      lm_scores[(long long)n * K + rank] = lms;
+    }
   }
-  if (lane == 0) count[n] = min(alive, K);
+  if (lane == 0) count[n] = returned;
   __syncthreads();
   int* out = ids + (long long)n * K * T;
   for (long long i = lane; i < (long long)K * T; i += 64) {
@@ -460,8 +366,12 @@ static long long ctcb_ws_bytes(long long N, int T, int beam, int top_classes) {
   return lists + tables <= INT_MAX ? lists + tables : 0;
 }
 
-// what both entry points check of the search itself, in the order they report it
-static int ctcb_check_sizes(const char* who, int N, int C, int T, int blank, int beam, int nbest, int top_classes) {
+// Both entry points: the checks in the order they are reported, the workspace, the two launches.  lm: the model, or null for the
+// search by the posterior alone, which neither looks at ctc_scores and lm_scores nor writes them
+static int ctcb_search(const char* who, int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T,
+                       int log_probs, int blank, int unknown, int beam, int nbest, int top_classes, const CtcbModel* lm, int* ids,
+                       int* lengths, float* scores, float* ctc_scores, float* lm_scores, int* count, void* ws, long long ws_bytes,
+                       hipStream_t stream) {
   MR_CHECK_ARG(N >= 0, "%s: N=%d rows", who, N);
   MR_CTC_TRY(ctc_check_columns(who, T, MR_SEQ_MEASURE_MAX));
   MR_CTC_TRY(ctc_check_classes(who, C, blank));
@@ -469,6 +379,42 @@ static int ctcb_check_sizes(const char* who, int N, int C, int T, int blank, int
   MR_CHECK_ARG(nbest >= 1 && nbest <= beam, "%s: nbest=%d (1..beam=%d)", who, nbest, beam);
   MR_CHECK_ARG(top_classes >= 1 && top_classes <= MR_CTC_BEAM_TOP_MAX, "%s: top_classes=%d (1..MR_CTC_BEAM_TOP_MAX=%d)", who,
                top_classes, MR_CTC_BEAM_TOP_MAX);
+  if (lm) {
+    MR_CHECK_ARG(lm->order >= 1 && lm->order <= MR_NGRAM_ORDER_MAX, "%s: order=%d (1..MR_NGRAM_ORDER_MAX=%d)", who, lm->order,
+                 MR_NGRAM_ORDER_MAX);
+    MR_CHECK_ARG(lm->states >= 1 && (int)lm->slots >= 1 && lm->max_probe >= 1, "%s: states=%d slots=%d max_probe=%d (each >= 1)",
+                 who, lm->states, (int)lm->slots, lm->max_probe);
+    MR_CHECK_ARG(lm->start_state >= 0 && lm->start_state < lm->states, "%s: start_state=%d is not one of %d states", who,
+                 lm->start_state, lm->states);
+    MR_CHECK_ARG(lm->alpha - lm->alpha == 0.f && lm->beta - lm->beta == 0.f, "%s: alpha=%g beta=%g must be finite", who,
+                 (double)lm->alpha, (double)lm->beta);
+    MR_CHECK_ARG(lm->keys && lm->arc_lp && lm->arc_next && lm->bow && lm->backoff && lm->end_lp, "%s: null model pointer", who);
+  }
+  MR_CTC_TRY(ctc_check_dtype(who, dtype));
+  if (N == 0) return MR_OK;
+  MR_CTC_TRY(ctc_check_workspace(who, "mr_ctc_beam_ws_bytes", ws, ws_bytes, ctcb_ws_bytes(N, T, beam, top_classes)));
+  MR_CHECK_ARG(pred && ids && lengths && scores && count && (!lm || (ctc_scores && lm_scores)), "%s: null pointer", who);
+  MR_CHECK_ARG((long long)N * T <= INT_MAX, "%s: N=%d rows x T=%d columns exceed the grid", who, N, T);
+  const long long cells = (long long)N * T * top_classes;
+  int* sym_id = (int*)ws;
+  float* sym_lp = (float*)(sym_id + cells);
+  u64* tables = (u64*)(sym_lp + cells);
+  const unsigned slots = (unsigned)ctcb_slots(T, beam);
+  const int staged = C <= CTCB_STAGE_MAX;
+  const size_t lds = staged ? (size_t)C * sizeof(float) : 0;
+  const int Kc = top_classes;
+  MR_CTC_DISPATCH(dtype, PT,
+                  hipLaunchKernelGGL(ctc_beam_columns_kernel<PT>, dim3((unsigned)(N * T)), dim3(64), lds, stream, (const PT*)pred,
+                                     sn, sc, st, C, T, log_probs, blank, unknown, Kc, staged, sym_id, sym_lp);
+                  if (lm)
+                    hipLaunchKernelGGL((ctc_beam_rows_kernel<PT, true>), dim3(N), dim3(64), 0, stream, (const PT*)pred, sn, sc, st,
+                                       C, T, log_probs, blank, beam, nbest, Kc, sym_id, sym_lp, tables, slots, *lm, ids, lengths,
+                                       scores, ctc_scores, lm_scores, count);
+                  else
+                    hipLaunchKernelGGL((ctc_beam_rows_kernel<PT, false>), dim3(N), dim3(64), 0, stream, (const PT*)pred, sn, sc, st,
+                                       C, T, log_probs, blank, beam, nbest, Kc, sym_id, sym_lp, tables, slots, CtcbModel{}, ids,
+                                       lengths, scores, nullptr, nullptr, count));
+  MR_CHECK_LAUNCH();
   return MR_OK;
 }
 
@@ -483,29 +429,8 @@ int mr_ctc_beam_ws_bytes(int N, int T, int beam, int top_classes) { return (int)
 int mr_ctc_beam_search(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T, int log_probs,
                        int blank, int unknown, int beam, int nbest, int top_classes, int* ids, int* lengths, float* scores,
                        int* count, void* ws, long long ws_bytes, hipStream_t stream) {
-  MR_CTC_TRY(ctcb_check_sizes("mr_ctc_beam_search", N, C, T, blank, beam, nbest, top_classes));
-  MR_CTC_TRY(ctc_check_dtype("mr_ctc_beam_search", dtype));
-  if (N == 0) return MR_OK;
-  MR_CTC_TRY(ctc_check_workspace("mr_ctc_beam_search", "mr_ctc_beam_ws_bytes", ws, ws_bytes,
-                                 ctcb_ws_bytes(N, T, beam, top_classes)));
-  MR_CHECK_ARG(pred && ids && lengths && scores && count, "mr_ctc_beam_search: null pointer");
-  MR_CHECK_ARG((long long)N * T <= INT_MAX, "mr_ctc_beam_search: N=%d rows x T=%d columns exceed the grid", N, T);
-  const long long cells = (long long)N * T * top_classes;
-  int* sym_id = (int*)ws;
-  float* sym_lp = (float*)(sym_id + cells);
-  u64* tables = (u64*)(sym_lp + cells);
-  const unsigned slots = (unsigned)ctcb_slots(T, beam);
-  const int staged = C <= CTCB_STAGE_MAX;
-  const size_t lds = staged ? (size_t)C * sizeof(float) : 0;
-  const int Kc = top_classes;
-  MR_CTC_DISPATCH(dtype, PT,
-                  hipLaunchKernelGGL(ctc_beam_columns_kernel<PT>, dim3((unsigned)(N * T)), dim3(64), lds, stream, (const PT*)pred,
-                                     sn, sc, st, C, T, log_probs, blank, unknown, Kc, staged, sym_id, sym_lp);
-                  hipLaunchKernelGGL(ctc_beam_kernel<PT>, dim3(N), dim3(64), 0, stream, (const PT*)pred, sn, sc, st, C, T,
-                                     log_probs, blank, beam, nbest, Kc, sym_id, sym_lp, tables, slots, ids, lengths, scores,
-                                     count));
-  MR_CHECK_LAUNCH();
-  return MR_OK;
+  return ctcb_search("mr_ctc_beam_search", dtype, pred, sn, sc, st, N, C, T, log_probs, blank, unknown, beam, nbest, top_classes,
+                     nullptr, ids, lengths, scores, nullptr, nullptr, count, ws, ws_bytes, stream);
 }
 
 int mr_ctc_beam_search_lm(int dtype, const void* pred, long long sn, long long sc, long long st, int N, int C, int T, int log_probs,
@@ -514,41 +439,10 @@ int mr_ctc_beam_search_lm(int dtype, const void* pred, long long sn, long long s
                           const float* lm_end_lp, int states, int slots, int max_probe, int start_state, int order, float alpha,
                           float beta, int end, int* ids, int* lengths, float* scores, float* ctc_scores, float* lm_scores,
                           int* count, void* ws, long long ws_bytes, hipStream_t stream) {
-  MR_CTC_TRY(ctcb_check_sizes("mr_ctc_beam_search_lm", N, C, T, blank, beam, nbest, top_classes));
-  MR_CHECK_ARG(order >= 1 && order <= MR_NGRAM_ORDER_MAX, "mr_ctc_beam_search_lm: order=%d (1..MR_NGRAM_ORDER_MAX=%d)", order,
-               MR_NGRAM_ORDER_MAX);
-  MR_CHECK_ARG(states >= 1 && slots >= 1 && max_probe >= 1, "mr_ctc_beam_search_lm: states=%d slots=%d max_probe=%d (each >= 1)",
-               states, slots, max_probe);
-  MR_CHECK_ARG(start_state >= 0 && start_state < states, "mr_ctc_beam_search_lm: start_state=%d is not one of %d states",
-               start_state, states);
-  MR_CHECK_ARG(alpha - alpha == 0.f && beta - beta == 0.f, "mr_ctc_beam_search_lm: alpha=%g beta=%g must be finite", (double)alpha,
-               (double)beta);
-  MR_CHECK_ARG(lm_keys && lm_arc_lp && lm_arc_next && lm_bow && lm_backoff && lm_end_lp,
-               "mr_ctc_beam_search_lm: null model pointer");
-  MR_CTC_TRY(ctc_check_dtype("mr_ctc_beam_search_lm", dtype));
-  if (N == 0) return MR_OK;
-  MR_CTC_TRY(ctc_check_workspace("mr_ctc_beam_search_lm", "mr_ctc_beam_ws_bytes", ws, ws_bytes,
-                                 ctcb_ws_bytes(N, T, beam, top_classes)));
-  MR_CHECK_ARG(pred && ids && lengths && scores && ctc_scores && lm_scores && count, "mr_ctc_beam_search_lm: null pointer");
-  MR_CHECK_ARG((long long)N * T <= INT_MAX, "mr_ctc_beam_search_lm: N=%d rows x T=%d columns exceed the grid", N, T);
-  const long long cells = (long long)N * T * top_classes;
-  int* sym_id = (int*)ws;
-  float* sym_lp = (float*)(sym_id + cells);
-  u64* tables = (u64*)(sym_lp + cells);
-  const unsigned table_slots = (unsigned)ctcb_slots(T, beam);
-  const int staged = C <= CTCB_STAGE_MAX;
-  const size_t lds = staged ? (size_t)C * sizeof(float) : 0;
-  const int Kc = top_classes;
   const CtcbModel lm = {lm_keys, lm_arc_lp, lm_arc_next, lm_bow, lm_backoff, lm_end_lp, states, (unsigned)slots, max_probe,
                         start_state, order, alpha, beta, end};
-  MR_CTC_DISPATCH(dtype, PT,
-                  hipLaunchKernelGGL(ctc_beam_columns_kernel<PT>, dim3((unsigned)(N * T)), dim3(64), lds, stream, (const PT*)pred,
-                                     sn, sc, st, C, T, log_probs, blank, unknown, Kc, staged, sym_id, sym_lp);
-                  hipLaunchKernelGGL(ctc_beam_lm_kernel<PT>, dim3(N), dim3(64), 0, stream, (const PT*)pred, sn, sc, st, C, T,
-                                     log_probs, blank, beam, nbest, Kc, sym_id, sym_lp, tables, table_slots, lm, ids, lengths,
-                                     scores, ctc_scores, lm_scores, count));
-  MR_CHECK_LAUNCH();
-  return MR_OK;
+  return ctcb_search("mr_ctc_beam_search_lm", dtype, pred, sn, sc, st, N, C, T, log_probs, blank, unknown, beam, nbest,
+                     top_classes, &lm, ids, lengths, scores, ctc_scores, lm_scores, count, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

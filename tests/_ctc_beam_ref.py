@@ -1,5 +1,5 @@
-"""Pure numpy restatement of CTC prefix beam search, written from the description of mr_ctc_beam_search
-(include/megreader_hip.h) -- not from the kernel.  Hypotheses are keyed by their CONTENT (a tuple of class ids in a dict), every
+"""Pure numpy restatement of CTC prefix beam search, written from the descriptions of mr_ctc_beam_search and, with a character
+n-gram model, mr_ctc_beam_search_lm (include/megreader_hip.h) -- not from the kernel.  Hypotheses are keyed by their CONTENT (a tuple of class ids in a dict), every
 log mass is held in the dtype asked for: float64 is the truth the tests hold the device to, float32 shows how much of a
 difference is rounding.  `lp` is the table of log-probabilities as given -- for the device the f32 table the header defines
 (`logs`) -- and is taken to `dtype` for the arithmetic; the symbols of a column are chosen on the table as given.  Besides the
@@ -31,13 +31,35 @@ def column_symbols(col, top_classes, blank, unknown):
     return taken, gap
 
 
-def beam_search(lp, beam, nbest, top_classes, blank=0, unknown=1, dtype=np.float64):
-    """One row.  lp: [T, C].  Returns dict(hyps=[(tuple of ids, score)] -- at most nbest, descending --, margin, reentries)."""
+def beam_search(lp, beam, nbest, top_classes, blank=0, unknown=1, dtype=np.float64, model=None, alpha=0.0, beta=0.0, end=False):
+    """One row.  lp: [T, C].  Returns dict(hyps=[(tuple of ids, score)] -- at most nbest, descending --, margin, reentries).
+    With `model` the search is mr_ctc_beam_search_lm's: a state and a sum lm per hypothesis, step 5 and the final order read total +
+    lm while the masses stay the pure CTC ones, and hyps are (tuple of ids, score, ctc_score, lm_score).  `model` is anything with
+    `start`, `terms(state, c) -> ([backoff weights in the order met], the n-gram's value or None, next state)` and `end(state)`
+    (_ngram_lm_ref.DictLM: the state is the history itself).  The model's part is held in `dtype` like the masses: float32 follows
+    the header's order -- acc = 0, acc += bow .., g = acc + value; lm += (alpha * g + beta), each operation rounded -- with the
+    model's values rounded to float32 first, as the device image holds them.  `margin` is then taken on the fused keys."""
+    f = dtype
     lp = np.asarray(lp)
     T, C = lp.shape
-    z = lp.astype(dtype)
-    prefixes = [()]                                   # the beam, in descending order of total
-    pb, pnb = np.zeros(1, dtype=dtype), np.full(1, NEG, dtype=dtype)
+    z = lp.astype(f)
+    alpha, beta = f(alpha), f(beta)
+
+    def grown(state, lm, c):
+        """(lm(p + c), or -inf where g is: no such n-gram down to the empty context, dropped in step 5; state(p + c))"""
+        bows, value, nxt = model.terms(state, c)
+        if value is None:
+            return NEG, nxt
+        acc = f(0)
+        for b in bows:
+            acc = f(acc + f(b))
+        g = f(acc + f(value))
+        return f(lm + f(f(alpha * g) + beta)), nxt
+
+    prefixes = [()]                                   # the beam, in descending order of what it is ranked by
+    pb, pnb = np.zeros(1, dtype=f), np.full(1, NEG, dtype=f)
+    if model is not None:
+        states, lms = [model.start], [f(0)]
     margin, reentries = np.inf, 0
     for t in range(T):
         syms, gap = column_symbols(lp[t], top_classes, blank, unknown)
@@ -49,50 +71,71 @@ def beam_search(lp, beam, nbest, top_classes, blank=0, unknown=1, dtype=np.float
         total = lse([pb, pnb])
         last = np.array([p[-1] if p else -1 for p in prefixes])
         # stay
-        new_pb = (total + z[t, blank]).astype(dtype)
-        new_pnb = np.where(last >= 0, pnb + z[t, np.maximum(last, 0)], np.asarray(NEG, dtype=dtype)).astype(dtype)
+        new_pb = (total + z[t, blank]).astype(f)
+        new_pnb = np.where(last >= 0, pnb + z[t, np.maximum(last, 0)], np.asarray(NEG, dtype=f)).astype(f)
         # extend: [nb, kc]
         if kc:
             sym = np.array(syms)
-            ext = (np.where(last[:, None] == sym[None, :], pb[:, None], total[:, None]) + z[t, sym][None, :]).astype(dtype)
+            ext = (np.where(last[:, None] == sym[None, :], pb[:, None], total[:, None]) + z[t, sym][None, :]).astype(f)
         else:
-            ext = np.zeros((nb, 0), dtype=dtype)
+            ext = np.zeros((nb, 0), dtype=f)
+        if model is not None:
+            ext_lm = np.zeros((nb, kc), dtype=f)
+            ext_state = [[None] * kc for _ in range(nb)]
+            for p in range(nb):
+                for j in range(kc):
+                    ext_lm[p, j], ext_state[p][j] = grown(states[p], lms[p], syms[j])
         # merge: an extension that spells a prefix of the beam joins its stay masses (one at most per prefix)
         for q, i in index.items():
             if q and q[:-1] in index and q[-1] in syms:
                 p, j = index[q[:-1]], syms.index(q[-1])
                 new_pnb[i] = lse([new_pnb[i:i + 1], ext[p:p + 1, j]])[0]
                 ext[p, j] = NEG
-        # keep
-        cand_total = np.concatenate([lse([new_pb, new_pnb]), ext.reshape(-1)])
-        order = np.argsort(-cand_total, kind='stable')
-        order = [int(k) for k in order if cand_total[k] > NEG]
+        # keep: by total, with a model by total + lm
+        ranked = np.concatenate([lse([new_pb, new_pnb]), ext.reshape(-1)])
+        if model is not None:
+            ranked = (ranked + np.concatenate([np.array(lms, dtype=f), ext_lm.reshape(-1)])).astype(f)
+        order = np.argsort(-ranked, kind='stable')
+        order = [int(k) for k in order if ranked[k] > NEG]
         if len(order) > beam:
-            margin = min(margin, float(cand_total[order[beam - 1]]) - float(cand_total[order[beam]]))
+            margin = min(margin, float(ranked[order[beam - 1]]) - float(ranked[order[beam]]))
         order = order[:beam]
-        kept, kept_pb, kept_pnb = [], [], []
+        kept, kept_pb, kept_pnb, kept_state, kept_lm = [], [], [], [], []
         for k in order:
             if k < nb:
                 kept.append(prefixes[k]); kept_pb.append(new_pb[k]); kept_pnb.append(new_pnb[k])
+                if model is not None:
+                    kept_state.append(states[k]); kept_lm.append(lms[k])
             else:
                 p, j = divmod(k - nb, kc)
                 kept.append(prefixes[p] + (syms[j],)); kept_pb.append(NEG); kept_pnb.append(ext[p, j])
+                if model is not None:
+                    kept_state.append(ext_state[p][j]); kept_lm.append(ext_lm[p, j])
         # a prefix that was not in the beam comes in beside a child of it that was and stays: it has been there before (the child
         # was made from it), and a decoder that does not give it its old identity back will not merge the two again
         was, now = set(prefixes), set(kept)
         reentries += sum(1 for s in kept if s not in was and any(q in was and q[:-1] == s for q in now if q))
-        prefixes = kept
-        pb, pnb = np.array(kept_pb, dtype=dtype), np.array(kept_pnb, dtype=dtype)
-    total = lse([pb, pnb]) if prefixes else np.zeros(0, dtype=dtype)
-    hyps = [(p, total[i]) for i, p in enumerate(prefixes)][:nbest]
-    for a, b in zip(hyps, hyps[1:]):
-        margin = min(margin, float(a[1]) - float(b[1]))
+        prefixes, states, lms = kept, kept_state, kept_lm
+        pb, pnb = np.array(kept_pb, dtype=f), np.array(kept_pnb, dtype=f)
+    total = lse([pb, pnb]) if prefixes else np.zeros(0, dtype=f)
+    if model is None:
+        hyps = [(p, total[i]) for i, p in enumerate(prefixes)][:nbest]
+        decided = [h[1] for h in hyps]
+    else:
+        if end:
+            lms = [f(lm + f(alpha * f(model.end(s)))) for lm, s in zip(lms, states)]
+        ranked = [f(total[i] + lms[i]) for i in range(len(prefixes))]
+        order = sorted(range(len(prefixes)), key=lambda i: -ranked[i])       # (stable: the beam's order among equal values)
+        hyps = [(prefixes[i], ranked[i], total[i], lms[i]) for i in order[:nbest]]
+        decided = [ranked[i] for i in order[:nbest + 1]]                     # the re-ranking also decides who is left out
+    for a, b in zip(decided, decided[1:]):
+        margin = min(margin, float(a) - float(b))
     return dict(hyps=hyps, margin=float(margin), reentries=reentries)
 
 
-def decode(lp, beam, nbest, top_classes, blank=0, unknown=1, dtype=np.float64):
+def decode(lp, beam, nbest, top_classes, blank=0, unknown=1, dtype=np.float64, model=None, alpha=0.0, beta=0.0, end=False):
     """All rows: lp f32 [N, T, C] -> a list of beam_search results."""
-    return [beam_search(row, beam, nbest, top_classes, blank, unknown, dtype) for row in lp]
+    return [beam_search(row, beam, nbest, top_classes, blank, unknown, dtype, model, alpha, beta, end) for row in lp]
 
 
 def true_score(lp, string, blank=0, unknown=1):

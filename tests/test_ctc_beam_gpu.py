@@ -29,13 +29,13 @@ def eval_layout(y, dtype=torch.float32):
     return torch.from_numpy(np.ascontiguousarray(np.transpose(y, (0, 2, 1)))).to(DEV).to(dtype).unsqueeze(2)
 
 
-def host(out):
-    return {k: out[k].cpu().numpy() for k in KEYS}
+def host(out, keys=KEYS):
+    return {k: out[k].cpu().numpy() for k in keys}
 
 
-def strings(out, n):
-    """[(tuple of ids, score)] of row n as returned."""
-    return [(tuple(int(s) for s in out['ids'][n, k, :out['lengths'][n, k]]), float(out['scores'][n, k]))
+def strings(out, n, scores=('scores',)):
+    """[(tuple of ids, score)] of row n as returned; with the model's `scores`, (tuple of ids, score, ctc_score, lm_score)."""
+    return [(tuple(int(s) for s in out['ids'][n, k, :out['lengths'][n, k]]),) + tuple(float(out[key][n, k]) for key in scores)
             for k in range(int(out['count'][n]))]
 
 

@@ -1,5 +1,5 @@
 """mr_ctc_beam_search_lm (csrc/ctc_beam.hip) and `ctc_beam_search_decode(lm=...)` against enumeration of every path plus the
-model's own float64 score, and against the numpy restatement (tests/_ctc_beam_lm_ref.py) over the dict scorer
+model's own float64 score, and against the numpy restatement (tests/_ctc_beam_ref.py, with a model) over the dict scorer
 (tests/_ngram_lm_ref.py) of the same n-grams.
 
 Tolerance: the convention of tests/test_ctc_beam_gpu.py.  Each case runs the restatement in float64 and in float32; e32 is the
@@ -19,7 +19,6 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-import _ctc_beam_lm_ref as BL  # noqa: E402
 import _ctc_beam_ref as B  # noqa: E402
 import _ngram_lm_ref as R  # noqa: E402
 import test_ctc_beam_gpu as G  # noqa: E402
@@ -41,13 +40,11 @@ SMALL = Charset("abeht", case_sensitive=True)                                   
 SMALL_WORDS = ["the", "the", "the", "the", "the", "hat", "tea", "bet", "beta", "that", "at"]
 
 
-def eval_layout(y, dtype=torch.float32):
-    """y [N, T, C] numpy -> the eval head's [N, C, 1, T] device tensor (a class's T values contiguous)."""
-    return torch.from_numpy(np.ascontiguousarray(np.transpose(y, (0, 2, 1)))).to(DEV).to(dtype).unsqueeze(2)
+eval_layout = G.eval_layout
 
 
 def host(out, keys=KEYS):
-    return {k: out[k].cpu().numpy() for k in keys}
+    return G.host(out, keys)
 
 
 def dict_model(lm, C=None):
@@ -57,8 +54,7 @@ def dict_model(lm, C=None):
 
 def strings(out, n):
     """[(tuple of ids, score, ctc_score, lm_score)] of row n as returned."""
-    return [(tuple(int(s) for s in out['ids'][n, k, :out['lengths'][n, k]]),) + tuple(float(out[key][n, k]) for key in SCORES)
-            for k in range(int(out['count'][n]))]
+    return G.strings(out, n, SCORES)
 
 
 class Reference(object):
@@ -68,8 +64,8 @@ class Reference(object):
         self.lp, self.lm, self.weights, self.args, self.blank, self.unknown = lp, lm, weights, (beam, nbest, top), blank, unknown
         alpha, beta, end = weights
         model = dict_model(lm, lp.shape[2])
-        self.r64 = BL.decode(lp, model, alpha, beta, end, beam, nbest, top, blank, unknown, np.float64)
-        self.r32 = BL.decode(lp, model, alpha, beta, end, beam, nbest, top, blank, unknown, np.float32)
+        self.r64 = B.decode(lp, beam, nbest, top, blank, unknown, np.float64, model, alpha, beta, end)
+        self.r32 = B.decode(lp, beam, nbest, top, blank, unknown, np.float32, model, alpha, beta, end)
         self.e32 = 0.0
         for a, b in zip(self.r64, self.r32):
             if [h[0] for h in a['hyps']] == [h[0] for h in b['hyps']]:

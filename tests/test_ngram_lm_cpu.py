@@ -1,6 +1,6 @@
 """`CharNgramLM` (megreader_amd/ops/language_model.py) on the host: the automaton against a dict-of-n-grams scorer written from the
 ARPA definition (tests/_ngram_lm_ref.py), the device image against a lookup that follows the header's hash rule, training, the
-ARPA round trip, the refusals -- and the restatement of mr_ctc_beam_search_lm (tests/_ctc_beam_lm_ref.py) against enumeration of
+ARPA round trip, the refusals -- and the restatement of mr_ctc_beam_search_lm (tests/_ctc_beam_ref.py, with a model) against enumeration of
 every path plus the model's own score.  No GPU."""
 import itertools
 import math
@@ -8,7 +8,6 @@ import math
 import numpy as np
 import pytest
 
-import _ctc_beam_lm_ref as BL
 import _ctc_beam_ref as B
 import _ngram_lm_ref as R
 from megreader_amd import _lib
@@ -255,7 +254,7 @@ def test_restatement_equals_enumeration_plus_model(C, T, alpha, beta, end):
     for row in y:
         lp = B.logs(row)
         truth = B.enumerate_strings(np.exp(lp.astype(np.float64)), 0, 1)
-        got = BL.beam_search(lp, ref, alpha, beta, end, 10 ** 6, 10 ** 6, C, 0, 1, np.float64)['hyps']
+        got = B.beam_search(lp, 10 ** 6, 10 ** 6, C, 0, 1, np.float64, ref, alpha, beta, end)['hyps']
         assert {p for p, _, _, _ in got} == set(truth)
         assert [s for _, s, _, _ in got] == sorted((s for _, s, _, _ in got), reverse=True)
         for p, score, ctc, part in got:

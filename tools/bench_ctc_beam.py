@@ -30,15 +30,17 @@ from megreader_amd.ops.decode import ctc_beam_search_decode, ctc_greedy_decode  
 
 
 def make_posteriors(rng, N, T, C, sharp):
-    """f32 [N, C, 1, T] (the eval head's layout) and the f32 [N, T, C] numpy copy of it."""
+    """f32 [N, C, 1, T] (the eval head's layout), the f32 [N, T, C] numpy copy of it and the strings the rows spell (class ids)."""
     logits = rng.randn(N, T, C).astype(np.float32)
+    texts = []
     for n in range(N):
         text = rng.randint(2, C, size=int(rng.randint(3, 13)))
         path = np.zeros(T, dtype=np.int64)
         path[1:2 * len(text):2] = text                                   # a blank between the symbols, blanks after them
         logits[n, np.arange(T), path] += sharp
+        texts.append(text.tolist())
     y = torch.softmax(torch.from_numpy(logits), dim=-1)
-    return y.permute(0, 2, 1).contiguous().unsqueeze(2), y.numpy()
+    return y.permute(0, 2, 1).contiguous().unsqueeze(2), y.numpy(), texts
 
 
 def main():
@@ -61,7 +63,7 @@ def main():
     results = []
     for C in args.classes:
         rng = np.random.RandomState(2025 + C)
-        pred, y = make_posteriors(rng, N, T, C, args.sharp)
+        pred, y, _ = make_posteriors(rng, N, T, C, args.sharp)
         pred = pred.to(dev)
         lp = B.logs(y[:args.sample])
         ms_greedy, (g_ids, g_len) = timed(lambda: ctc_greedy_decode(pred), args.warmup, args.iters)

@@ -10,7 +10,7 @@ Workload (seeded: nothing is downloaded): 256 posteriors [N, C, 1, 32], the soft
 string of 3..12 symbols with a blank between them (tools/bench_ctc_beam.py's), over C = 37 and 6 000 classes; beams of 1, 8 and 32
 hypotheses over the 16 best symbols of a column, one string returned; character models of order 3 and 5 trained on the strings the
 rows spell (`CharNgramLM.train`), so that the extensions along a row's path find long n-grams and the others back off to the
-unigrams.  Per case the tool also holds a sample of rows to the float64 restatement (tests/_ctc_beam_lm_ref.py) with the tolerance
+unigrams.  Per case the tool also holds a sample of rows to the float64 restatement (tests/_ctc_beam_ref.py, with a model) with the tolerance
 of tests/test_ctc_beam_lm_gpu.py.  The two kernels of a call are not timed apart here:
 `rocprofv3 --kernel-trace --stats -- python tools/bench_ctc_beam_lm.py --iters 20` names them."""
 import argparse
@@ -25,24 +25,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+from bench_ctc_beam import make_posteriors  # noqa: E402
 from bench_lexicon import timed  # noqa: E402
 from megreader_amd.charsets import Charset  # noqa: E402
 from megreader_amd.ops.decode import ctc_beam_search_decode  # noqa: E402
 from megreader_amd.ops.language_model import CharNgramLM  # noqa: E402
-
-
-def make_posteriors(rng, N, T, C, sharp):
-    """f32 [N, C, 1, T] (the eval head's layout), the f32 [N, T, C] numpy copy of it and the strings the rows spell (class ids)."""
-    logits = rng.randn(N, T, C).astype(np.float32)
-    texts = []
-    for n in range(N):
-        text = rng.randint(2, C, size=int(rng.randint(3, 13)))
-        path = np.zeros(T, dtype=np.int64)
-        path[1:2 * len(text):2] = text                                   # a blank between the symbols, blanks after them
-        logits[n, np.arange(T), path] += sharp
-        texts.append(text.tolist())
-    y = torch.softmax(torch.from_numpy(logits), dim=-1)
-    return y.permute(0, 2, 1).contiguous().unsqueeze(2), y.numpy(), texts
 
 
 def main():
@@ -62,7 +49,6 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_ctc_beam_lm.py measures on the GPU; there is none")
-    import _ctc_beam_lm_ref as BL
     import _ctc_beam_ref as B
     import _ngram_lm_ref as R
     dev = torch.device("cuda")
@@ -85,8 +71,8 @@ def main():
                 ms_plain, _ = timed(lambda: ctc_beam_search_decode(pred, **kw), args.warmup, args.iters)
                 ms_lm, out = timed(lambda: ctc_beam_search_decode(pred, lm=lm, lm_weight=weights[0], lm_bonus=weights[1], **kw),
                                    args.warmup, args.iters)
-                r64 = BL.decode(lp, model, *weights, beam, 1, top, dtype=np.float64)
-                r32 = BL.decode(lp, model, *weights, beam, 1, top, dtype=np.float32)
+                r64 = B.decode(lp, beam, 1, top, 0, 1, np.float64, model, *weights)
+                r32 = B.decode(lp, beam, 1, top, 0, 1, np.float32, model, *weights)
                 e32 = max([0.0] + [abs(float(a['hyps'][0][1]) - float(b['hyps'][0][1])) for a, b in zip(r64, r32)
                                    if a['hyps'] and b['hyps'] and a['hyps'][0][0] == b['hyps'][0][0]])
                 ids_h, len_h = out['ids'][:, 0].cpu().numpy(), out['lengths'][:, 0].cpu().numpy()
