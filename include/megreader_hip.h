@@ -625,12 +625,51 @@ int mr_db_box_scores(const float* prob, const float* boxes, float* out, int B, i
  * f32 [N][K][2] its (sum, count) (zeros when not scored), status i32 [N][K]: 0 no such component, 1 short side < min_size,
  * 2 below box_thresh, 3 too small after unclip, 4 kept.
  * ws: *bytes of mr_db_boxes_ws_bytes (labels, rank map, row counts, the table of row extremes i32 [N][K][H][2], uncompacted
- * results), 16-byte aligned, not initialised.  1 <= K <= 1024; H <= 2048 (a candidate's 2 H hull points are staged in LDS);
+ * results, the candidate rectangles f64 [N][K][4][2] that mr_db_ribbons reads), 16-byte aligned, not initialised.  1 <= K <= 1024; H <= 2048 (a candidate's 2 H hull points are staged in LDS);
  * H * W < 2^31; MR_ERR_ARG otherwise. */
 int mr_db_boxes_ws_bytes(int N, int H, int W, int K, long long* bytes);
 int mr_db_boxes(const float* prob, const float* seg, float thresh, const int* dest, int N, int H, int W, int K,
                 double box_thresh, double min_size, void* ws, double* boxes, float* scores, int* count, int* components,
                 double* cand, float* cand_sums, int* status, hipStream_t stream);
+/* mr_db_ribbons: a RIBBON beside every box of the preceding mr_db_boxes, for words that follow a curve.  A ribbon is k rulings, each
+ * a top point and a bottom point in dest coordinates, ordered along the reading direction; the word is the strip between the two
+ * polylines (mr_strip_crop rectifies it).  Called after mr_db_boxes on the same stream with the same N, H, W, K, dest and ws: it
+ * reads what that call left there (flattened labels, row extremes, statuses and candidate rectangles), one launch, no host
+ * synchronisation, capturable; float64 with every product and sum rounded on its own, integer atomics only, the same bits every
+ * run (tests/_db_ribbon_ref.py restates it).  For the j-th surviving box of image n (the order of `boxes`):
+ *   ribbons f64 [N][K][MR_RIBBON_MAX_KNOTS][2][2] (knot, top / bottom, x / y), zeros behind the used knots;
+ *   knots i32 [N][K]: 0 = no ribbon, the box stands; otherwise 5 .. MR_RIBBON_MAX_KNOTS;
+ *   why i32 [N][K]: 0 ribbon, 1 short, 2 empty slab, 3 steep, 4 folded.     Rows behind count[n]: zeros.
+ *   rws: *bytes of mr_db_ribbons_ws_bytes, 8-byte aligned, not initialised: i64 [N][K][MR_RIBBON_MAX_SLABS][6], per candidate SLOT
+ *   with a kept box that reached step 3 the sums of its Se slabs (the rest is not written).
+ * The rule, per candidate whose status is kept; p0..p3 = its ordered rectangle before unclip (`cand`), |v| = sqrt(v.x*v.x + v.y*v.y),
+ * S = slabs, expressions evaluated left to right:
+ *  1. axis   a = |p1 - p0|, b = |p3 - p0|.  max((int)b, 1) > 1.5 * max((int)a, 1):  o = p1, e = (p2 - p1) / b, L = b;  otherwise
+ *            o = p0, e = (p1 - p0) / a, L = a  (`plan_crop`'s `rotated` rule: a vertical word reads downwards).  L > 0, else short.
+ *  2. slabs  P = pixels of the component, tbar = P / (L + 1), Se = min(S, (int)((L + 1) / max(4.0, tbar))); Se < 3: short.
+ *            sw = (L + 1) / Se; pixel (x, y) lies in slab clamp((int)floor((u + 0.5) / sw), 0, Se - 1), u = (x - o.x)*e.x + (y - o.y)*e.y.
+ *  3. moments per slab, 64-bit integers: n, Sx, Sy, Sxx, Sxy, Syy.  Any n == 0: empty.  m = (Sx / n, Sy / n),
+ *            cxx = Sxx / n - m.x*m.x, cxy = Sxy / n - m.x*m.y, cyy = Syy / n - m.y*m.y.
+ *  4. tangents  t_j = m_{j+1} - m_{j-1}; t_0 = -3*m_0 + 4*m_1 - m_2; t_l = 3*m_l - 4*m_{l-1} + m_{l-2} (l = Se - 1); t = t / |t|;
+ *            cos_j = t.x*e.x + t.y*e.y; any cos_j not > 0.25 (NaN included): steep.  Normal n = (-t.y, t.x).
+ *  5. half thickness  var = n.x*n.x*cxx + 2*n.x*n.y*cxy + n.y*n.y*cyy, h = (sqrt(12*max(var, 0) + 1) - 1) / 2 (r full pixel rows
+ *            give (r - 1) / 2, the point extent `mini_box` measures); the end slabs are under-filled: h_0 = h_1, h_l = h_{l-1}.
+ *  6. knots 0 .. Se + 1: knot i, 1 <= i <= Se, is (m, t, n, h) of slab i - 1; the end knots take t, n, h of their neighbour and
+ *            c_0 = m_0 - t_0*((sw / 2) / cos_0), c_last = m_l + t_l*((sw / 2) / cos_l).
+ *  7. unclip  T_i = c_i - n_i*h_i, B_i = c_i + n_i*h_i; A2 = sum of x_i*y_{i+1} - x_{i+1}*y_i and Lp = sum of |q_{i+1} - q_i| around
+ *            T_0 .. T_last, B_last .. B_0 (from 0, in that order); d = |A2| / 2 * ratio / Lp; c_0 -= d*t_0, c_last += d*t_last,
+ *            every h_i += d; T and B again.
+ *  8. fold   every cell (T_i, T_{i+1}, B_{i+1}, B_i) strictly convex: with q0..q3 its corners, all four
+ *            (q_{j+1} - q_j).x*(q_{j+2} - q_{j+1}).y - (q_{j+1} - q_j).y*(q_{j+2} - q_{j+1}).x > 0 (y down); otherwise folded.  It is
+ *            the condition under which the bilinear cell map of mr_strip_crop is one-to-one.
+ *  9. scale  x / W * dest_w, y / H * dest_h; not rounded, not clamped.
+ * 3 <= slabs <= MR_RIBBON_MAX_SLABS, 0 <= ratio <= 1e6 (1.5 is the boxes' unclip ratio), the shapes mr_db_boxes takes; MR_ERR_ARG
+ * otherwise, nothing launched. */
+#define MR_RIBBON_MAX_SLABS 16
+#define MR_RIBBON_MAX_KNOTS 18
+int mr_db_ribbons_ws_bytes(int N, int K, long long* bytes);
+int mr_db_ribbons(const int* dest, int N, int H, int W, int K, int slabs, double ratio, const void* ws, void* rws,
+                  double* ribbons, int* knots, int* why, hipStream_t stream);
 
 /* ---- DB detector metrics (concern/icdar2015_eval/detection/iou.py:13-179 `evaluate_image` for quadrilaterals, the
  * evaluator of structure/measurers/quad_measurer.py).  All arithmetic float64.  gt f64 [N][G][4][2] / det f64 [N][D][4][2]
@@ -995,6 +1034,35 @@ int mr_sizeof_crop_image(void);
 int mr_sizeof_crop_desc(void);
 int mr_quad_crop(const unsigned char* src, const void* images /* [I] */, int I, const void* crops /* [M] */, int M,
                  int H, int W, double mean0, double mean1, double mean2, float* dst /* [M][3][H][W] */, hipStream_t stream);
+
+/* ---- Strip crops (csrc/image_sample.hip): mr_quad_crop with a piecewise-bilinear mesh in the place of the homography, for words
+ * that follow a curve.  A strip is `knots` rulings (top[i], bot[i]) in photo coordinates at the arc lengths s[i] of the crop frame
+ * (s ascending, s[0] = 0); the host plans it from points only (megreader_amd/data/strip_crop.py).  The same photo table, output,
+ * taps, blend and normalisation as mr_quad_crop.  Canvas pixel (u, v) of crop m, u < dst_w (float64, in this order, every product
+ * and sum rounded on its own):
+ *   cx = min(max((u + 0.5)*sx - 0.5, 0), cu1), cy = min(max((v + 0.5)*sy - 0.5, 0), cv1)         (as mr_quad_crop)
+ *   i = the last knot with s[i] <= cx, at most knots - 2 (0 when there is none);  a = (cx - s[i]) / (s[i+1] - s[i]);  b = cy / hgt
+ *   top = top[i]*(1 - a) + top[i+1]*a, bot = bot[i]*(1 - a) + bot[i+1]*a   (per coordinate);   (x, y) = top*(1 - b) + bot*b
+ *   x or y not finite: the pixel value is 0.  Otherwise the taps and the float32 blend of mr_quad_crop.
+ * Columns u >= dst_w, and crops whose `image` is not in [0, I) or whose `knots` is not in [2, 18], get the normalised zero pixel;
+ * every element of dst is written.  `top` and `bot` depend on the column alone: a workgroup computes them once per column.  When
+ * `strips` is pinned host memory the entry point checks `image` and `knots` of every strip before the launch (MR_ERR_ARG).
+ * M == 0 returns MR_OK without a launch. */
+typedef struct mr_strip_desc {
+  int image;                    /* index into the mr_crop_image table */
+  int dst_w;                    /* valid canvas columns (mode "pad"); the rest is the zero canvas */
+  int knots;                    /* 2 .. 18 rulings */
+  int reserved;                 /* 0 (keeps the doubles 8-byte aligned) */
+  double sx, sy;                /* cv2.resize scales of the strip's frame, as mr_crop_desc */
+  double cu1, cv1;              /* the frame coordinate is clamped to [0, cu1] x [0, cv1] */
+  double hgt;                   /* the frame's height: b = cy / hgt runs from the top polyline to the bottom one */
+  double s[18];                 /* arc length of the centre line at every knot */
+  double top[18][2], bot[18][2];   /* the rulings' end points (x, y) in the photo */
+} mr_strip_desc;
+int mr_sizeof_strip_desc(void);
+int mr_strip_crop(const unsigned char* src, const void* images /* [I] mr_crop_image */, int I, const void* strips /* [M] */,
+                  int M, int H, int W, double mean0, double mean1, double mean2, float* dst /* [M][3][H][W] */,
+                  hipStream_t stream);
 
 /* ---- Tiled multi-scale detection (csrc/det_tiles.hip): a photo too large for one detector input is resized to a CANVAS at its
  * own scale (several canvases: several "levels"), the canvas is covered by overlapping detector-sized tiles, and the tiles'

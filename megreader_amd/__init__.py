@@ -25,15 +25,22 @@ def get_compute_dtype():
 
 
 def __getattr__(name):
-    """`megreader_amd.TextReader` (reader.py), `megreader_amd.QuadCropper` (data/quad_crop.py), `megreader_amd.DetectionTiler`
-    (data/detection_tiles.py) and `megreader_amd.Lexicon` (ops/lexicon.py), imported on first use: they load the HIP library,
-    which `import megreader_amd` alone does not."""
+    """`megreader_amd.TextReader` (reader.py), `megreader_amd.QuadCropper` (data/quad_crop.py), `megreader_amd.StripCropper`
+    (data/strip_crop.py), `megreader_amd.Ribbon` (structure/ribbon.py), `megreader_amd.DetectionTiler` (data/detection_tiles.py)
+    and `megreader_amd.Lexicon` (ops/lexicon.py), imported on first use: they load the HIP library, which `import megreader_amd`
+    alone does not."""
     if name == "TextReader":
         from .reader import TextReader
         return TextReader
     if name == "QuadCropper":
         from .data.quad_crop import QuadCropper
         return QuadCropper
+    if name == "StripCropper":
+        from .data.strip_crop import StripCropper
+        return StripCropper
+    if name == "Ribbon":
+        from .structure.ribbon import Ribbon
+        return Ribbon
     if name == "DetectionTiler":
         from .data.detection_tiles import DetectionTiler
         return DetectionTiler
@@ -43,4 +50,5 @@ def __getattr__(name):
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
-__all__ = ["set_compute_dtype", "get_compute_dtype", "DetectionTiler", "Lexicon", "QuadCropper", "TextReader"]
+__all__ = ["set_compute_dtype", "get_compute_dtype", "DetectionTiler", "Lexicon", "QuadCropper", "Ribbon", "StripCropper",
+           "TextReader"]

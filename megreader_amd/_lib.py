@@ -25,13 +25,16 @@ _RETURN_TYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "const cha
 
 
 def _ctype(decl, context, array_ok=False):
-    """(name, ctypes type, is a hipStream_t) of one parameter `TYPE name` or struct field `TYPE name` / `TYPE name[N]`."""
-    m = re.fullmatch(r"(.*?)(\w+)(?:\[(\d+)\])?", decl.strip(), re.S)
+    """(name, ctypes type, is a hipStream_t) of one parameter `TYPE name` or struct field `TYPE name` / `TYPE name[N]` /
+    `TYPE name[N][M]`."""
+    m = re.fullmatch(r"(.*?)(\w+)((?:\[\d+\])*)", decl.strip(), re.S)
     base = " ".join(m.group(1).split()) if m else ""
     ctype = ctypes.c_void_p if "*" in base else _PARAM_TYPES.get(base)
     if ctype is None or (m.group(3) and not array_ok):
         raise TypeError("cannot bind %r in `%s`: no ctypes mapping for that type" % (decl.strip(), " ".join(context.split())))
-    return m.group(2), ctype * int(m.group(3)) if m.group(3) else ctype, base == "hipStream_t"
+    for n in reversed(re.findall(r"\d+", m.group(3))):             # double top[18][2]: 18 arrays of 2
+        ctype = ctype * int(n)
+    return m.group(2), ctype, base == "hipStream_t"
 
 
 def parse_header(text):

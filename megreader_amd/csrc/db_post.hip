@@ -520,7 +520,8 @@ __global__ __launch_bounds__(256) void db_boxes_kernel(const float* __restrict__
                                                         const int* __restrict__ dest, double box_thresh, double min_size,
                                                         double* __restrict__ sbox, float* __restrict__ sscore,
                                                         int* __restrict__ status, double* __restrict__ cand,
-                                                        float* __restrict__ cand_sums, int* __restrict__ status_out) {
+                                                        float* __restrict__ cand_sums, int* __restrict__ status_out,
+                                                        double* __restrict__ kept_cand) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   double* area = (double*)(lds + DBX_AREA);
   double* rect = (double*)(lds + DBX_RECT);
@@ -620,6 +621,7 @@ __global__ __launch_bounds__(256) void db_boxes_kernel(const float* __restrict__
   if (tid == 0) val[0] = dbx_mini_box(P1, h, rect, tmp, box);
   __syncthreads();
   if (tid < 8 && cand != nullptr) cand[slot * 8 + tid] = box[tid];
+  if (tid < 8) kept_cand[slot * 8 + tid] = box[tid];    // stays in ws for mr_db_ribbons (read where the status is kept)
   if (val[0] < min_size) {
     finish(DBX_SHORT);
     return;
@@ -698,9 +700,275 @@ __global__ __launch_bounds__(256) void db_boxes_compact_kernel(const int* __rest
   if (threadIdx.x == 0) count[blockIdx.x] = base;
 }
 
+// ---- Ribbons (mr_db_ribbons): the curve a kept candidate follows, from what mr_db_boxes left in its workspace -------------------
+// One workgroup per (image, candidate slot), as db_boxes_kernel: two scans of the candidate's pixels between its row extremes
+// (the count, then six exact integer sums per slab along the rectangle's long axis: LDS atomics on 64-bit integers, one table per
+// wavefront, a thread flushes its sums when the slab changes), then one lane per slab / knot restates the rule of
+// include/megreader_hip.h in float64.  No global atomics; the same bits every run.
+constexpr int RB_NONE = 0, RB_SHORT = 1, RB_EMPTY = 2, RB_STEEP = 3, RB_FOLDED = 4;
+constexpr int RB_S = MR_RIBBON_MAX_SLABS, RB_K = MR_RIBBON_MAX_KNOTS, RB_ROW = RB_K * 4;
+enum { RB_BEFORE = 0, RB_TOTAL, RB_YMIN, RB_YMAX, RB_XMIN, RB_XMAX, RB_PIX, RB_SE, RB_FLAG };
+
+__global__ __launch_bounds__(256) void db_ribbons_kernel(const int* __restrict__ labels, const int2* __restrict__ ext,
+                                                          const int* __restrict__ status, const double* __restrict__ cand,
+                                                          const int* __restrict__ dest, int H, int W, int K, int S, double ratio,
+                                                          long long* __restrict__ sums, double* __restrict__ ribbons,
+                                                          int* __restrict__ knots, int* __restrict__ why) {
+  __shared__ unsigned long long acc[4][RB_S][6];
+  __shared__ double mean[RB_S][2], cov[RB_S][3], tan_[RB_S][2], cosv[RB_S], half[RB_S];
+  __shared__ double kc[RB_K][2], kt[RB_K][2], kh[RB_K], top[RB_K][2], bot[RB_K][2];
+  __shared__ double geo[8];                             // o.x, o.y, e.x, e.y, sw, d
+  __shared__ int misc[12];
+  const int tid = threadIdx.x;
+  const long long slot = blockIdx.x;
+  const int n = (int)(slot / K), k = (int)(slot - (long long)n * K);
+  if (tid < 12) misc[tid] = tid == RB_YMIN || tid == RB_XMIN ? INT_MAX : (tid == RB_YMAX || tid == RB_XMAX ? -1 : 0);
+  for (int i = tid; i < 4 * RB_S * 6; i += 256) (&acc[0][0][0])[i] = 0ull;
+  __syncthreads();
+  // the row of this slot in the compacted order of db_boxes_compact_kernel, and how many rows the image has
+  {
+    int before = 0, total = 0;
+    for (int j = tid; j < K; j += 256) {
+      const int kept = status[(long long)n * K + j] == DBX_KEPT ? 1 : 0;
+      total += kept;
+      before += j < k ? kept : 0;
+    }
+    if (total) atomicAdd(&misc[RB_TOTAL], total);
+    if (before) atomicAdd(&misc[RB_BEFORE], before);
+  }
+  __syncthreads();
+  if (k >= misc[RB_TOTAL]) {                            // a row behind the last box: zeros
+    for (int i = tid; i < RB_ROW; i += 256) ribbons[slot * RB_ROW + i] = 0.0;
+    if (tid == 0) { knots[slot] = 0; why[slot] = RB_NONE; }
+  }
+  if (status[slot] != DBX_KEPT) return;
+  const long long row = (long long)n * K + misc[RB_BEFORE];
+  auto none = [&](int reason) {                         // (every thread of the workgroup comes here together)
+    for (int i = tid; i < RB_ROW; i += 256) ribbons[row * RB_ROW + i] = 0.0;
+    if (tid == 0) { knots[row] = 0; why[row] = reason; }
+  };
+  // rows and columns of the candidate; its label is its raster-first pixel: the left-most one of its first row
+  const int2* e = ext + slot * H;
+  {
+    int ylo = INT_MAX, yhi = -1, xlo = INT_MAX, xhi = -1;
+    for (int y = tid; y < H; y += 256) {
+      const int2 v = e[y];
+      if (v.y >= 0) {
+        ylo = min(ylo, y); yhi = max(yhi, y);
+        xlo = min(xlo, v.x); xhi = max(xhi, v.y);
+      }
+    }
+    if (yhi >= 0) {
+      atomicMin(&misc[RB_YMIN], ylo); atomicMax(&misc[RB_YMAX], yhi);
+      atomicMin(&misc[RB_XMIN], xlo); atomicMax(&misc[RB_XMAX], xhi);
+    }
+  }
+  __syncthreads();
+  const int ymin = misc[RB_YMIN], nrows = misc[RB_YMAX] - ymin + 1, xmin = misc[RB_XMIN];
+  if (nrows <= 0) {                                     // (a kept candidate has pixels)
+    none(RB_SHORT);
+    return;
+  }
+  const int root = ymin * W + e[ymin].x;
+  const int* L = labels + (long long)n * H * W;
+  const int chunks = (misc[RB_XMAX] - xmin) / 8 + 1;    // 8 pixels of one row per thread and step
+  const long long items = (long long)nrows * chunks;
+  {
+    int cnt = 0;
+    for (long long t = tid; t < items; t += 256) {
+      const int r = (int)(t / chunks), y = ymin + r, c0 = xmin + (int)(t - (long long)r * chunks) * 8;
+      const int2 v = e[y];                              // (a row without pixels holds (INT_MAX, -1): an empty range)
+      const int x0 = max(c0, v.x), xe = min(c0 + 7, v.y);
+      for (int x = x0; x <= xe; ++x) cnt += L[(long long)y * W + x] == root ? 1 : 0;
+    }
+    if (cnt) atomicAdd(&misc[RB_PIX], cnt);
+  }
+  __syncthreads();
+  if (tid == 0) {                                       // 1. axis, 2. slabs
+    const double* p = cand + slot * 8;
+    const double ax = p[2] - p[0], ay = p[3] - p[1], bx = p[6] - p[0], by = p[7] - p[1];
+    const double a = sqrt(ax * ax + ay * ay), b = sqrt(bx * bx + by * by);
+    double ox, oy, ex, ey, len;
+    if ((double)max((int)b, 1) > 1.5 * (double)max((int)a, 1)) {
+      ox = p[2]; oy = p[3]; ex = (p[4] - p[2]) / b; ey = (p[5] - p[3]) / b; len = b;
+    } else {
+      ox = p[0]; oy = p[1]; ex = ax / a; ey = ay / a; len = a;
+    }
+    int se = 0;
+    double sw = 0.0;
+    if (len > 0.0) {
+      const double tbar = (double)misc[RB_PIX] / (len + 1.0);
+      se = min(S, (int)((len + 1.0) / fmax(4.0, tbar)));
+      if (se >= 3) sw = (len + 1.0) / (double)se;
+    }
+    geo[0] = ox; geo[1] = oy; geo[2] = ex; geo[3] = ey; geo[4] = sw;
+    misc[RB_SE] = se;
+  }
+  __syncthreads();
+  const int se = misc[RB_SE];
+  if (se < 3) {
+    none(RB_SHORT);
+    return;
+  }
+  const double ox = geo[0], oy = geo[1], ex = geo[2], ey = geo[3], sw = geo[4];
+  // 3. moments
+  {
+    unsigned long long (*mine)[6] = acc[tid >> 6];
+    for (long long t = tid; t < items; t += 256) {
+      const int r = (int)(t / chunks), y = ymin + r, c0 = xmin + (int)(t - (long long)r * chunks) * 8;
+      const int2 v = e[y];
+      const int x0 = max(c0, v.x), xe = min(c0 + 7, v.y);
+      int cur = -1;
+      unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0;
+      auto flush = [&]() {
+        if (cur < 0) return;
+        atomicAdd(&mine[cur][0], s0); atomicAdd(&mine[cur][1], s1); atomicAdd(&mine[cur][2], s2);
+        atomicAdd(&mine[cur][3], s3); atomicAdd(&mine[cur][4], s4); atomicAdd(&mine[cur][5], s5);
+      };
+      for (int x = x0; x <= xe; ++x) {
+        if (L[(long long)y * W + x] != root) continue;
+        const double u = ((double)x - ox) * ex + ((double)y - oy) * ey;
+        const double f = floor((u + 0.5) / sw);
+        const int j = f >= (double)(se - 1) ? se - 1 : (f > 0.0 ? (int)f : 0);      // (a NaN falls to slab 0)
+        if (j != cur) {
+          flush();
+          cur = j;
+          s0 = s1 = s2 = s3 = s4 = s5 = 0;
+        }
+        const unsigned long long xx = (unsigned long long)x, yy = (unsigned long long)y;
+        s0 += 1; s1 += xx; s2 += yy; s3 += xx * xx; s4 += xx * yy; s5 += yy * yy;
+      }
+      flush();
+    }
+  }
+  __syncthreads();
+  if (tid < se * 6) {
+    const int j = tid / 6, q = tid - j * 6;
+    const unsigned long long v = acc[0][j][q] + acc[1][j][q] + acc[2][j][q] + acc[3][j][q];
+    acc[0][j][q] = v;
+    sums[(slot * RB_S + j) * 6 + q] = (long long)v;
+  }
+  __syncthreads();
+  if (tid < se) {
+    const double cnt = (double)(long long)acc[0][tid][0];
+    if (acc[0][tid][0] == 0ull) {
+      atomicOr(&misc[RB_FLAG], 1);
+    } else {
+      const double mx = (double)(long long)acc[0][tid][1] / cnt, my = (double)(long long)acc[0][tid][2] / cnt;
+      mean[tid][0] = mx; mean[tid][1] = my;
+      cov[tid][0] = (double)(long long)acc[0][tid][3] / cnt - mx * mx;
+      cov[tid][1] = (double)(long long)acc[0][tid][4] / cnt - mx * my;
+      cov[tid][2] = (double)(long long)acc[0][tid][5] / cnt - my * my;
+    }
+  }
+  __syncthreads();
+  if (misc[RB_FLAG]) {
+    none(RB_EMPTY);
+    return;
+  }
+  const int l = se - 1, kn = se + 2;
+  if (tid < se) {                                       // 4. tangents
+    double tx, ty;
+    if (tid == 0) {
+      tx = -3.0 * mean[0][0] + 4.0 * mean[1][0] - mean[2][0];
+      ty = -3.0 * mean[0][1] + 4.0 * mean[1][1] - mean[2][1];
+    } else if (tid == l) {
+      tx = 3.0 * mean[l][0] - 4.0 * mean[l - 1][0] + mean[l - 2][0];
+      ty = 3.0 * mean[l][1] - 4.0 * mean[l - 1][1] + mean[l - 2][1];
+    } else {
+      tx = mean[tid + 1][0] - mean[tid - 1][0];
+      ty = mean[tid + 1][1] - mean[tid - 1][1];
+    }
+    const double len = sqrt(tx * tx + ty * ty);
+    tx = tx / len; ty = ty / len;
+    const double c = tx * ex + ty * ey;
+    if (!(c > 0.25)) atomicOr(&misc[RB_FLAG], 1);
+    tan_[tid][0] = tx; tan_[tid][1] = ty; cosv[tid] = c;
+    const double nx = -ty, ny = tx;                     // 5. half thickness
+    const double var = nx * nx * cov[tid][0] + 2.0 * nx * ny * cov[tid][1] + ny * ny * cov[tid][2];
+    half[tid] = (sqrt(12.0 * fmax(var, 0.0) + 1.0) - 1.0) / 2.0;
+  }
+  __syncthreads();
+  if (misc[RB_FLAG]) {
+    none(RB_STEEP);
+    return;
+  }
+  if (tid < kn) {                                       // 6. knots
+    const int j = min(max(tid - 1, 0), l), jh = min(max(j, 1), l - 1);
+    const double tx = tan_[j][0], ty = tan_[j][1];
+    double cx = mean[j][0], cy = mean[j][1];
+    if (tid == 0) {
+      const double back = (sw / 2.0) / cosv[0];
+      cx = cx - tx * back; cy = cy - ty * back;
+    } else if (tid == kn - 1) {
+      const double on = (sw / 2.0) / cosv[l];
+      cx = cx + tx * on; cy = cy + ty * on;
+    }
+    const double h = half[jh], nx = -ty, ny = tx;
+    kc[tid][0] = cx; kc[tid][1] = cy; kt[tid][0] = tx; kt[tid][1] = ty; kh[tid] = h;
+    top[tid][0] = cx - nx * h; top[tid][1] = cy - ny * h;
+    bot[tid][0] = cx + nx * h; bot[tid][1] = cy + ny * h;
+  }
+  __syncthreads();
+  if (tid == 0) {                                       // 7. unclip distance: shoelace area and perimeter of the outline
+    double a2 = 0.0, per = 0.0;
+    const int m = 2 * kn;
+    for (int i = 0; i < m; ++i) {
+      const int i1 = i + 1 == m ? 0 : i + 1;
+      const double* p = i < kn ? top[i] : bot[m - 1 - i];
+      const double* q = i1 < kn ? top[i1] : bot[m - 1 - i1];
+      a2 = a2 + (p[0] * q[1] - q[0] * p[1]);
+      const double dx = q[0] - p[0], dy = q[1] - p[1];
+      per = per + sqrt(dx * dx + dy * dy);
+    }
+    geo[5] = fabs(a2) / 2.0 * ratio / per;
+  }
+  __syncthreads();
+  if (tid < kn) {
+    const double d = geo[5], tx = kt[tid][0], ty = kt[tid][1], nx = -ty, ny = tx;
+    double cx = kc[tid][0], cy = kc[tid][1];
+    if (tid == 0) {
+      cx = cx - d * tx; cy = cy - d * ty;
+    } else if (tid == kn - 1) {
+      cx = cx + d * tx; cy = cy + d * ty;
+    }
+    const double h = kh[tid] + d;
+    top[tid][0] = cx - nx * h; top[tid][1] = cy - ny * h;
+    bot[tid][0] = cx + nx * h; bot[tid][1] = cy + ny * h;
+  }
+  __syncthreads();
+  if (tid < kn - 1) {                                   // 8. fold: every cell strictly convex
+    const double qx[4] = {top[tid][0], top[tid + 1][0], bot[tid + 1][0], bot[tid][0]};
+    const double qy[4] = {top[tid][1], top[tid + 1][1], bot[tid + 1][1], bot[tid][1]};
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int j1 = (j + 1) & 3, j2 = (j + 2) & 3;
+      ok &= (qx[j1] - qx[j]) * (qy[j2] - qy[j1]) - (qy[j1] - qy[j]) * (qx[j2] - qx[j1]) > 0.0;
+    }
+    if (!ok) atomicOr(&misc[RB_FLAG], 1);
+  }
+  __syncthreads();
+  if (misc[RB_FLAG]) {
+    none(RB_FOLDED);
+    return;
+  }
+  if (tid < RB_K) {                                     // 9. scale
+    double* o = ribbons + row * RB_ROW + tid * 4;
+    if (tid < kn) {
+      const double dw = (double)dest[2 * n], dh = (double)dest[2 * n + 1];
+      o[0] = top[tid][0] / (double)W * dw; o[1] = top[tid][1] / (double)H * dh;
+      o[2] = bot[tid][0] / (double)W * dw; o[3] = bot[tid][1] / (double)H * dh;
+    } else {
+      o[0] = o[1] = o[2] = o[3] = 0.0;
+    }
+  }
+  if (tid == 0) { knots[row] = kn; why[row] = RB_NONE; }
+}
+
 // workspace of mr_db_boxes, every part 16-byte aligned
 struct DbxWorkspace {
-  long long sbox, labels, rank, ext, rowcnt, sscore, status, bytes;
+  long long sbox, labels, rank, ext, rowcnt, sscore, status, cand, bytes;
 };
 static inline DbxWorkspace dbx_workspace(int N, int H, int W, int K) {
   auto up = [](long long b) { return (b + 15) / 16 * 16; };
@@ -713,6 +981,7 @@ static inline DbxWorkspace dbx_workspace(int N, int H, int W, int K) {
   w.rowcnt = off; off += up((long long)N * H * 4);
   w.sscore = off; off += up((long long)N * K * 4);
   w.status = off; off += up((long long)N * K * 4);
+  w.cand = off;   off += up((long long)N * K * 8 * 8);    // the candidate rectangles, for mr_db_ribbons
   w.bytes = off;
   return w;
 }
@@ -756,7 +1025,8 @@ int mr_db_box_scores(const float* prob, const float* boxes, float* out, int B, i
   return MR_OK;
 }
 
-// bytes of workspace mr_db_boxes wants: labels, rank map, row counts, extremes table, the uncompacted boxes / scores / statuses
+// bytes of workspace mr_db_boxes wants: labels, rank map, row counts, extremes table, the uncompacted boxes / scores / statuses /
+// candidate rectangles
 int mr_db_boxes_ws_bytes(int N, int H, int W, int K, long long* bytes) {
   MR_CHECK_ARG(bytes != nullptr, "mr_db_boxes_ws_bytes: bytes is null");
   const char* bad = dbx_bad_shape(N, H, W, K);
@@ -793,8 +1063,36 @@ int mr_db_boxes(const float* prob, const float* seg, float thresh, const int* de
                      (long long)N * K * H);
   hipLaunchKernelGGL(db_extremes_kernel, dim3(grid_for(total, 256)), dim3(256), 0, stream, labels, rank, N, H, W, K, ext);
   hipLaunchKernelGGL(db_boxes_kernel, dim3(N * K), dim3(256), dbx_lds_bytes(H), stream, prob, H, W, K, components,
-                     (const int2*)ext, dest, box_thresh, min_size, sbox, sscore, st, cand, cand_sums, status);
+                     (const int2*)ext, dest, box_thresh, min_size, sbox, sscore, st, cand, cand_sums, status,
+                     (double*)(base + w.cand));
   hipLaunchKernelGGL(db_boxes_compact_kernel, dim3(N), dim3(256), 0, stream, st, sbox, sscore, K, boxes, scores, count);
+  MR_CHECK_LAUNCH();
+  return MR_OK;
+}
+
+// bytes of workspace mr_db_ribbons wants: the six integer sums of every slab, i64 [N][K][MR_RIBBON_MAX_SLABS][6]
+int mr_db_ribbons_ws_bytes(int N, int K, long long* bytes) {
+  MR_CHECK_ARG(bytes != nullptr, "mr_db_ribbons_ws_bytes: bytes is null");
+  MR_CHECK_ARG(N > 0 && K >= 1 && K <= DBX_MAX_K && (long long)N * K < (1ll << 31), "mr_db_ribbons_ws_bytes: bad shape");
+  *bytes = (long long)N * K * RB_S * 6 * 8;
+  return MR_OK;
+}
+
+// a ribbon beside every box of the preceding mr_db_boxes (same shapes, same ws, same stream): one launch (include/megreader_hip.h)
+int mr_db_ribbons(const int* dest, int N, int H, int W, int K, int slabs, double ratio, const void* ws, void* rws,
+                  double* ribbons, int* knots, int* why, hipStream_t stream) {
+  const char* bad = dbx_bad_shape(N, H, W, K);
+  MR_CHECK_ARG(bad == nullptr, "mr_db_ribbons: %s", bad);
+  MR_CHECK_ARG(slabs >= 3 && slabs <= RB_S, "mr_db_ribbons: slabs must be in [3, %d], got %d", RB_S, slabs);
+  MR_CHECK_ARG(ratio >= 0.0 && ratio <= 1e6, "mr_db_ribbons: ratio must be in [0, 1e6]");
+  MR_CHECK_ARG(dest && ws && rws && ribbons && knots && why, "mr_db_ribbons: null pointer");
+  MR_CHECK_ARG(((unsigned long long)ws & 15ull) == 0 && ((unsigned long long)rws & 7ull) == 0,
+               "mr_db_ribbons: ws must be 16-byte aligned, rws 8-byte aligned");
+  const DbxWorkspace w = dbx_workspace(N, H, W, K);
+  const char* base = (const char*)ws;
+  hipLaunchKernelGGL(db_ribbons_kernel, dim3(N * K), dim3(256), 0, stream, (const int*)(base + w.labels),
+                     (const int2*)(base + w.ext), (const int*)(base + w.status), (const double*)(base + w.cand), dest, H, W, K,
+                     slabs, ratio, (long long*)rws, ribbons, knots, why);
   MR_CHECK_LAUNCH();
   return MR_OK;
 }

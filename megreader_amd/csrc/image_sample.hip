@@ -39,6 +39,7 @@ static_assert(sizeof(mr_img_desc) == 40, "mr_img_desc is mirrored by ctypes (dat
 static_assert(sizeof(mr_warp_desc) == 128, "mr_warp_desc is mirrored by ctypes (data/detection_augment.py)");
 static_assert(sizeof(mr_crop_image) == 24, "mr_crop_image is mirrored by ctypes (data/quad_crop.py)");
 static_assert(sizeof(mr_crop_desc) == 112, "mr_crop_desc is mirrored by ctypes (data/quad_crop.py)");
+static_assert(sizeof(mr_strip_desc) == 776, "mr_strip_desc is mirrored by ctypes (data/strip_crop.py)");
 
 // Canvas pixel number gid of [N][Hd][Wd], threads along u: image n, row v, column u.
 __device__ __forceinline__ void canvas_split(unsigned gid, int Hd, int Wd, int& n, int& v, int& u) {
@@ -146,6 +147,51 @@ __global__ __launch_bounds__(256) void quad_crop_kernel(const unsigned char* src
   store_normalized(dst, m, v, u, Hd, Wd, val, m0, m1, m2);
 }
 
+// mr_strip_crop: mr_quad_crop's sampling point of the strip's frame, then the piecewise-bilinear mesh into the photo.  One
+// workgroup per (crop, 64 canvas columns): the descriptor is uniform, the first wavefront finds every column's cell and blends
+// its top and bottom point ONCE (the search over the knots, a division and four blends in float64), then each wavefront takes
+// every fourth row and a pixel costs two blends -- the order the restatement (tests/_strip_crop_ref.py) rounds in.  Lanes run
+// along u as in quad_crop_kernel: 256 consecutive bytes per plane and store.
+constexpr int STRIP_COLS = 64;
+__global__ __launch_bounds__(256) void strip_crop_kernel(const unsigned char* src, const mr_crop_image* images, int I,
+                                                         const mr_strip_desc* strips, int tiles, int Hd, int Wd, double m0,
+                                                         double m1, double m2, float* dst) {
+  __shared__ double col[STRIP_COLS][4];                 // top.x, top.y, bot.x, bot.y of the column
+  const int m = (int)(blockIdx.x / (unsigned)tiles);
+  const int lane = threadIdx.x & 63, u = (int)(blockIdx.x - (unsigned)m * tiles) * STRIP_COLS + lane;
+  const mr_strip_desc* d = strips + m;
+  const int image = d->image, dst_w = d->dst_w, knots = d->knots;
+  const bool sampled = image >= 0 && image < I && knots >= 2 && knots <= 18 && u < dst_w && u < Wd;
+  if (threadIdx.x < STRIP_COLS && sampled) {
+    const double cx = fmin(fmax(((double)u + 0.5) * d->sx - 0.5, 0.0), d->cu1);
+    int i = 0;
+    for (int j = 1; j <= knots - 2; ++j) i = d->s[j] <= cx ? j : i;
+    const double a = (cx - d->s[i]) / (d->s[i + 1] - d->s[i]), g = 1.0 - a;
+    col[lane][0] = d->top[i][0] * g + d->top[i + 1][0] * a;
+    col[lane][1] = d->top[i][1] * g + d->top[i + 1][1] * a;
+    col[lane][2] = d->bot[i][0] * g + d->bot[i + 1][0] * a;
+    col[lane][3] = d->bot[i][1] * g + d->bot[i + 1][1] * a;
+  }
+  __syncthreads();
+  if (u >= Wd) return;
+  mr_crop_image im = {0, 0, 0, 0, 0};
+  if (sampled) im = images[image];
+  const unsigned char* pix = src + im.offset;
+  const double sy = d->sy, cv1 = d->cv1, hgt = d->hgt;
+  for (int v = threadIdx.x >> 6; v < Hd; v += 4) {
+    float val[3] = {0.f, 0.f, 0.f};
+    if (sampled) {
+      const double cy = fmin(fmax(((double)v + 0.5) * sy - 0.5, 0.0), cv1);
+      const double b = cy / hgt, g = 1.0 - b;
+      const double x = col[lane][0] * g + col[lane][2] * b, y = col[lane][1] * g + col[lane][3] * b;
+      bilinear3(true, x, y, im.w, im.h, [&](int xx, int yy, float p[3]) {       // a NaN or an infinity fails the range test
+        tap3(xx >= 0 && xx < im.w && yy >= 0 && yy < im.h, pix, im.pitch, yy, xx, p);
+      }, val);
+    }
+    store_normalized(dst, m, v, u, Hd, Wd, val, m0, m1, m2);
+  }
+}
+
 }  // namespace mr
 
 using namespace mr;
@@ -200,6 +246,34 @@ int mr_quad_crop(const unsigned char* src, const void* images, int I, const void
   }
   hipLaunchKernelGGL(quad_crop_kernel, dim3((unsigned)cdivll(total, 256)), dim3(256), 0, stream, src,
                      (const mr_crop_image*)images, I, (const mr_crop_desc*)crops, M, H, W, mean0, mean1, mean2, dst);
+  MR_CHECK_LAUNCH();
+  return MR_OK;
+}
+
+int mr_sizeof_strip_desc(void) { return (int)sizeof(mr_strip_desc); }
+
+int mr_strip_crop(const unsigned char* src, const void* images, int I, const void* strips, int M, int H, int W, double mean0,
+                  double mean1, double mean2, float* dst, hipStream_t stream) {
+  MR_CHECK_ARG(I >= 0 && M >= 0 && H > 0 && W > 0, "mr_strip_crop: bad shape I=%d M=%d H=%d W=%d", I, M, H, W);
+  if (M == 0) return MR_OK;
+  MR_CHECK_ARG(src != nullptr && images != nullptr && strips != nullptr && dst != nullptr, "mr_strip_crop: null pointer");
+  MR_CHECK_ARG(I > 0, "mr_strip_crop: %d crops and no photo", M);
+  const long long tiles = cdivll(W, STRIP_COLS);
+  MR_CHECK_ARG((long long)M * H * W < 0x7fffff00LL && M * tiles < 0x7fffff00LL, "mr_strip_crop: M=%d H=%d W=%d exceed one launch",
+               M, H, W);
+  // A table in pinned host memory is readable on both sides: check it here.  Device memory is the kernel's to check.
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, strips) == hipSuccess && attr.type == hipMemoryTypeHost) {
+    const mr_strip_desc* c = (const mr_strip_desc*)strips;
+    for (int m = 0; m < M; ++m) {
+      MR_CHECK_ARG(c[m].image >= 0 && c[m].image < I, "mr_strip_crop: crop %d names photo %d of %d", m, c[m].image, I);
+      MR_CHECK_ARG(c[m].knots >= 2 && c[m].knots <= 18, "mr_strip_crop: crop %d has %d knots", m, c[m].knots);
+    }
+  } else {
+    (void)hipGetLastError();    // an address the runtime does not know is no error of this call
+  }
+  hipLaunchKernelGGL(strip_crop_kernel, dim3((unsigned)(M * tiles)), dim3(256), 0, stream, src, (const mr_crop_image*)images, I,
+                     (const mr_strip_desc*)strips, (int)tiles, H, W, mean0, mean1, mean2, dst);
   MR_CHECK_LAUNCH();
   return MR_OK;
 }

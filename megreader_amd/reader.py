@@ -41,7 +41,15 @@ itself; a float s: the photo times s, rounded to multiples of `det_align`), the 
 twice `det_halo`, the detector runs on the tiles in chunks of `det_batch`, and the tiles' maps of all levels are fused
 (`det_fuse`: 'max' or 'mean') into ONE map per photo, on which the representer runs once with the photo's own shape
 (data/detection_tiles.py: `DetectionTiler`; a word cut by a tile border comes back as one box).  The tiles are sampled from the
-photos the pipeline uploaded, decoded ones with `encoded=True`; everything behind the boxes is as above."""
+photos the pipeline uploaded, decoded ones with `encoded=True`; everything behind the boxes is as above.
+
+`curved=True` reads words that follow a curve.  The representer's `represent_ribbons` returns beside every box the RIBBON its
+component follows (structure/ribbon.py; `mr_db_ribbons` with `ribbon_slabs` slabs), or None where the word is short or straight
+enough for its box, and every crop goes through `StripCropper` (data/strip_crop.py, one launch of mr_strip_crop) -- a box without
+a ribbon as `Ribbon.from_box`, which is the quad crop's map.  Every item gains 'polygon', the ribbon's outline (top forward, bottom
+backward) or the box's four corners; 'quad' stays the box; character quads go through `StripPlan.canvas_to_photo` and follow the
+curve.  The representer scores a box by the mean of the map over the RECTANGLE, of which a curved word fills only a part: give the
+representer a lower `box_thresh` than the 0.7 that suits straight words."""
 import math
 
 import numpy as np
@@ -50,11 +58,13 @@ import torch
 from .data.detection_tiles import DetectionTiler
 from .data.device_pipeline import DevicePipeline, EncodedDevicePipeline
 from .data.jpeg_decode import SPLIT_ABOVE
-from .data.quad_crop import QuadCropper
+from .data.quad_crop import DegenerateQuad, QuadCropper
+from .data.strip_crop import StripCropper, plan_strip
 from .ops.decode import (ctc2d_char_rows, ctc2d_greedy_decode, ctc2d_marginal, ctc_beam_search_decode, ctc_forced_align,
                          ctc_greedy_decode)
 from .ops.lexicon import Lexicon
 from ._lib import _DEFINES
+from .structure.ribbon import Ribbon
 from .structure.seg_detector_representer import SegDetectorRepresenter
 
 
@@ -63,7 +73,8 @@ class TextReader(object):
                  rec_mode='resize', rectify='min_area_rect', decode='ctc', max_crops=256, scores=False, lexicon=None,
                  lexicon_max_distance=None, lexicon_rule='nearest', beam_width=None, nbest=1, beam_top_classes=16, chars=False,
                  column_geometry=None, row_geometry=None, attention_extent=1.5, encoded=False, lm=None, lm_weight=1.0,
-                 lm_bonus=0.0, det_scales=None, det_halo=(64, 64), det_fuse='max', det_batch=8, det_align=32):
+                 lm_bonus=0.0, det_scales=None, det_halo=(64, 64), det_fuse='max', det_batch=8, det_align=32, curved=False,
+                 ribbon_slabs=8):
         self.det_tiler = None
         if det_scales is not None:      # tiles of `det_size` at the photo's own scale, fused per photo (data/detection_tiles.py)
             if int(det_batch) < 1:
@@ -136,6 +147,18 @@ class TextReader(object):
         else:
             self.det_pipeline = DevicePipeline(image_size=det_size, mode='resize', charset=charset)
         self.cropper = QuadCropper(image_size=rec_size, mode=rec_mode, rectify=rectify)
+        self.curved = bool(curved)
+        self.ribbon_slabs = int(ribbon_slabs)
+        if self.curved:         # every crop through mr_strip_crop: a ribbon where the representer found one, else the box's
+            if not callable(getattr(self.representer, 'represent_ribbons', None)):
+                raise ValueError("curved=True needs a representer with represent_ribbons(batch, pred, slabs=) -> (boxes, scores, "
+                                 "ribbons), got %r" % (type(self.representer).__name__,))
+            if rectify != 'min_area_rect':
+                raise ValueError("curved=True crops boxes as `Ribbon.from_box` does: it needs rectify='min_area_rect', got %r"
+                                 % (rectify,))
+            if not 3 <= self.ribbon_slabs <= _DEFINES["MR_RIBBON_MAX_SLABS"]:
+                raise ValueError("ribbon_slabs must be in [3, %d], got %r" % (_DEFINES["MR_RIBBON_MAX_SLABS"], ribbon_slabs))
+            self.strip_cropper = StripCropper(image_size=rec_size, mode=rec_mode)
 
     def _upload(self, images):
         """The detector's input batch and the photos as uint8 HWC views of the device buffer the pipeline uploaded."""
@@ -146,20 +169,55 @@ class TextReader(object):
     def _detect_tiled(self, photos):
         """With `det_scales`: the detector on tiles of the resident photos at their own scale (`DetectionTiler.detect_maps`), every
         map the representer reads -- 'binary', and `representer.dest` when it differs -- fused per photo, and the representer
-        once per photo on the fused map with the photo's own shape: (boxes per photo, scores per photo or None)."""
+        once per photo on the fused map with the photo's own shape: (boxes per photo, scores per photo or None, with `curved`
+        ribbons per photo or None)."""
         keys = ('binary',) + ((self.representer.dest,) if getattr(self.representer, 'dest', 'binary') != 'binary' else ())
         fused = self.det_tiler.detect_maps(self.detector, photos, batch=self.det_batch, keys=keys)
         boxes, box_scores = [], ([] if self.scores else None)
+        ribbons = [] if self.curved else None
         for i, photo in enumerate(photos):
             det_batch = {'image': None, 'shape': [tuple(photo.shape[:2])]}
             pred = {key: fused[key][i] for key in keys}
-            if self.scores:
+            if self.curved:
+                found, scored, curves = self.representer.represent_ribbons(det_batch, pred, slabs=self.ribbon_slabs)
+                ribbons.extend(curves)
+                if self.scores:
+                    box_scores.extend(scored)
+            elif self.scores:
                 found, scored, _ = self.representer.represent_scored(det_batch, pred)
                 box_scores.extend(scored)
             else:
                 found, _ = self.representer.represent(det_batch, pred)
             boxes.extend(found)
-        return boxes, box_scores
+        return boxes, box_scores, ribbons
+
+    def _pack_strips(self, photos, boxes, ribbons):
+        """With `curved`: every box as a strip -- its ribbon, or `Ribbon.from_box` of the box where there is none -- planned and
+        staged by the `StripCropper`: (staged, layout, per crop its photo, its box and its outline).  A box with a zero side is
+        dropped, as the `QuadCropper` drops it."""
+        plans, index, quads, outlines, dropped = [], [], [], [], []
+        for i, (found, curves) in enumerate(zip(boxes, ribbons)):
+            for k, (box, ribbon) in enumerate(zip(found, curves)):
+                outline = box
+                try:
+                    if ribbon is not None:
+                        try:
+                            plan, outline = plan_strip(photos[i].shape, ribbon, self.strip_cropper.image_size,
+                                                       self.strip_cropper.mode), ribbon.polygon().tolist()
+                        except DegenerateQuad:
+                            ribbon = None
+                    if ribbon is None:
+                        plan = plan_strip(photos[i].shape, Ribbon.from_box(box), self.strip_cropper.image_size,
+                                          self.strip_cropper.mode)
+                except DegenerateQuad:
+                    dropped.append((i, k))
+                    continue
+                plans.append((i, plan))
+                index.append(i)
+                quads.append([[float(x), float(y)] for x, y in box])
+                outlines.append(outline)
+        staged, layout = self.strip_cropper.pack(photos, None, plans=plans)
+        return staged, layout._replace(dropped=dropped), index, quads, outlines
 
     @staticmethod
     def _head2d(pred):
@@ -471,34 +529,46 @@ class TextReader(object):
         (cx, cy) its mean and (sx, sy) its standard deviation in cells, the rectangle cx +- max(attention_extent * sx, 0.5) by
         cy +- max(attention_extent * sy, 0.5) cells, scaled by W_canvas / max_size and H_canvas / height, clamped to the valid
         canvas and carried to the photo by `CropPlan.canvas_to_photo`.  An attention map says where the decoder looked, which is
-        not a segmentation: `attention_extent` (1.5 standard deviations) is a choice, and half a cell the least box."""
+        not a segmentation: `attention_extent` (1.5 standard deviations) is a choice, and half a cell the least box.
+        With `curved=True` every item also has 'polygon' ([[x, y], ...]: the outline of the word's ribbon, or the four corners of
+        'quad' where the box stands) and the crops, and with them every character quad, follow the ribbon (module docstring)."""
         images = list(images)
         results = [[] for _ in images]
         if not images:
             return results
         batch, photos = self._upload(images)
+        ribbons = None
         if self.det_tiler is not None:          # (the pipeline's one-canvas batch is not looked at: the tiles read the photos)
-            boxes, box_scores = self._detect_tiled(photos)
+            boxes, box_scores, ribbons = self._detect_tiled(photos)
         else:
             pred = self._eval(self.detector, batch['image'])
             if not isinstance(pred, dict):
                 pred = {'binary': pred}
             det_batch = {'image': batch['image'], 'shape': [tuple(p.shape[:2]) for p in photos]}
-            if self.scores:
+            if self.curved:
+                boxes, box_scores, ribbons = self.representer.represent_ribbons(det_batch, pred, slabs=self.ribbon_slabs)
+            elif self.scores:
                 boxes, box_scores, _ = self.representer.represent_scored(det_batch, pred)
             else:
                 boxes, _ = self.representer.represent(det_batch, pred)
-        staged, layout = self.cropper.pack(photos, boxes)
+        outlines = None
+        if self.curved:
+            staged, layout, index, quads, outlines = self._pack_strips(photos, boxes, ribbons)
+        else:
+            staged, layout = self.cropper.pack(photos, boxes)
         if layout.M == 0:
             return results
-        crops = self.cropper.upload(staged, layout)
+        crops = (self.strip_cropper if self.curved else self.cropper).upload(staged, layout)
         records = self._recognize(crops['image'])
-        host = staged.numpy()
-        index = host[layout.index_off:layout.index_off + 4 * layout.M].view(np.int32)
-        quads = host[layout.quad_off:layout.quad_off + 64 * layout.M].view(np.float64).reshape(layout.M, 4, 2)
+        if not self.curved:
+            host = staged.numpy()
+            index = host[layout.index_off:layout.index_off + 4 * layout.M].view(np.int32).tolist()
+            quads = host[layout.quad_off:layout.quad_off + 64 * layout.M].view(np.float64).reshape(layout.M, 4, 2).tolist()
         # (boxes with a zero side were dropped by the cropper)
-        for i, quad, plan, rec in zip(index.tolist(), quads.tolist(), layout.plans, records):
+        for m, (i, quad, plan, rec) in enumerate(zip(index, quads, layout.plans, records)):
             item = {'quad': quad, 'text': rec['text']}
+            if outlines is not None:
+                item['polygon'] = outlines[m]
             item.update((key, rec[key]) for key in ('raw_text', 'lexicon_distance', 'lexicon_score') if key in rec)
             item.update(rec.get('extras', ()))
             if 'spans' in rec:

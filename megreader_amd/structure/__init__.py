@@ -3,6 +3,7 @@ from .representers import CTCRepresenter, CTCRepresenter2D  # noqa: F401,E402
 from .measurers import SequenceRecognitionMeasurer  # noqa: F401,E402
 from .quad_measurer import QuadMeasurer  # noqa: F401,E402
 from .seg_detector_representer import SegDetectorRepresenter  # noqa: F401,E402
+from .ribbon import Ribbon  # noqa: F401,E402
 
 
 def member_from_config(obj, cmd=None):

@@ -75,6 +75,11 @@ class SegDetectorRepresenter(object):
         {'boxes': f64 [N, K, 4, 2] the boxes of image n in its first count[n] slots (zeros behind), 'scores': f32 [N, K],
         'count': i32 [N], 'components': i32 [N] connected components of the image (more than K = max_candidates: the rest was
         not looked at), 'packed': the uint8 buffer all four are views of}."""
+        return self._boxes_launch(binary, dest_map, shapes, bitmap)[0]
+
+    def _boxes_launch(self, binary, dest_map, shapes, bitmap, front=0):
+        """`boxes_on_device` with `front` free bytes (a multiple of 8) in front of the packed results: (its dict, the workspace
+        mr_db_boxes left its labels, extremes and candidates in, dest on the device, (N, H, W, K))."""
         require_cuda(binary)
         prob, seg, thr = self._maps(binary, dest_map, bitmap)
         N, H, W = prob.shape[0], prob.shape[2], prob.shape[3]
@@ -86,12 +91,59 @@ class SegDetectorRepresenter(object):
         dest = [(shapes[n][1], shapes[n][0]) if self.resize else (W, H) for n in range(N)]
         dest = torch.tensor(dest, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
         ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
-        packed = torch.empty((N * K * 68 + N * 8,), dtype=torch.uint8, device=dev)
-        out = self._views(packed, N, K)
+        packed = torch.empty((front + N * K * 68 + N * 8,), dtype=torch.uint8, device=dev)
+        out = self._views(packed[front:], N, K)
         call("mr_db_boxes", ptr(prob), ptr(seg), thr, ptr(dest), N, H, W, K, float(self.box_thresh), float(self.min_size),
              ptr(ws), ptr(out['boxes']), ptr(out['scores']), ptr(out['count']), ptr(out['components']), 0, 0, 0)
         out['packed'] = packed
+        return out, ws, dest, (N, H, W, K)
+
+    def ribbons_on_device(self, binary, dest_map, shapes, slabs=8, bitmap=None):
+        """`boxes_on_device`, then `mr_db_ribbons` on the same workspace and stream: beside every box the curve its component
+        follows (structure/ribbon.py), nothing copied, nothing waited for.  Returns what `boxes_on_device` returns and 'ribbons':
+        f64 [N, K, 18, 2, 2] (knot, top / bottom, x / y; zeros behind the used knots), 'knots': i32 [N, K] (0: no ribbon, the box
+        stands), 'why': i32 [N, K] (0 ribbon, 1 short, 2 empty slab, 3 steep, 4 folded), all views of 'packed'.  The box score is
+        the mean over the RECTANGLE, of which a curved word fills a part: read curved text with a lower `box_thresh`."""
+        if not 3 <= int(slabs) <= 16:
+            raise ValueError("slabs must be in [3, 16] (MR_RIBBON_MAX_SLABS), got %r" % (slabs,))
+        N, K = binary.shape[0], int(self.max_candidates)
+        front = N * K * (self.RIBBON_KNOTS * 32 + 8)             # ribbons | knots | why in front of the boxes' results
+        out, ws, dest, (N, H, W, K) = self._boxes_launch(binary, dest_map, shapes, bitmap, front=front)
+        rbytes = ctypes.c_longlong(0)
+        if load().mr_db_ribbons_ws_bytes(N, K, ctypes.byref(rbytes)) != 0:
+            raise RuntimeError("mr_db_ribbons_ws_bytes failed: %s" % load().mr_last_error().decode())
+        rws = torch.empty((rbytes.value,), dtype=torch.uint8, device=ws.device)
+        out.update(self._ribbon_views(out['packed'][:front], N, K))
+        call("mr_db_ribbons", ptr(dest), N, H, W, K, int(slabs), 1.5, ptr(ws), ptr(rws), ptr(out['ribbons']), ptr(out['knots']),
+             ptr(out['why']))
         return out
+
+    RIBBON_KNOTS = 18            # MR_RIBBON_MAX_KNOTS
+
+    @classmethod
+    def _ribbon_views(cls, packed, N, K):
+        """The three results of mr_db_ribbons as views of one byte buffer: ribbons | knots | why."""
+        o1, o2 = N * K * cls.RIBBON_KNOTS * 32, N * K * (cls.RIBBON_KNOTS * 32 + 4)
+        return {'ribbons': packed[:o1].view(torch.float64).view(N, K, cls.RIBBON_KNOTS, 2, 2),
+                'knots': packed[o1:o2].view(torch.int32).view(N, K), 'why': packed[o2:].view(torch.int32).view(N, K)}
+
+    def represent_ribbons(self, batch, _pred, slabs=8):
+        """`represent_scored` with a ribbon beside every box: (boxes_batch, scores_batch, ribbons_batch), per image a `Ribbon` in
+        photo coordinates or None (the box stands) for every box.  Always the device path, as `represent_scored`; ONE
+        device-to-host copy of one packed buffer."""
+        from .ribbon import Ribbon
+        shapes = [tuple(int(v) for v in s) for s in batch['shape']]
+        out = self.ribbons_on_device(_pred['binary'], _pred[self.dest], shapes, slabs=slabs)
+        N, K = out['scores'].shape
+        host = out['packed'].cpu()
+        front = N * K * (self.RIBBON_KNOTS * 32 + 8)
+        box, rib = self._views(host[front:], N, K), self._ribbon_views(host[:front], N, K)
+        counts = box['count'].tolist()
+        knots, curves = rib['knots'].tolist(), rib['ribbons'].numpy()
+        ribbons = [[Ribbon(curves[n, j, :knots[n][j], 0], curves[n, j, :knots[n][j], 1]) if knots[n][j] else None
+                    for j in range(counts[n])] for n in range(N)]
+        return ([box['boxes'][n, :counts[n]].tolist() for n in range(N)],
+                [box['scores'][n, :counts[n]].tolist() for n in range(N)], ribbons)
 
     @staticmethod
     def _views(packed, N, K):
