@@ -691,6 +691,33 @@ int mr_quad_iou(const double* gt, const int* gt_count, const double* det, const 
 int mr_quad_match(const int* gt_valid, const int* det_valid, const int* gt_ignore, const double* det_area, const double* inter,
                   const double* iou, int N, int G, int D, double iou_constraint, double area_precision_constraint, int* counts,
                   double* scores, int* match_det, int* gt_dontcare, int* det_dontcare, hipStream_t stream);
+/* mr_poly_iou: the tables of mr_quad_iou for SIMPLE POLYGONS of 3 .. V vertices each (curved text: a ribbon's outline, the 14
+ * points of CTW1500, Total-Text), so that mr_quad_match runs on them unchanged.  gt f64 [N][G][V][2], gt_verts i32 [N][G] = vertices of
+ * each polygon (those at and beyond it are padding), gt_count i32 [N] = used slots; det / det_verts / det_count alike with D.
+ * 3 <= V <= MR_POLY_MAX_VERTS: MR_ERR_ARG below, MR_ERR_UNSUPPORTED above (refused, not truncated).  All arithmetic float64, every
+ * product and sum rounded on its own (tests/_poly_eval_ref.py restates it).  Every element of the six outputs is written; padding
+ * slots, polygons that are not valid and pairs with such a member get 0.
+ * Validity (shapely's `is_valid and is_simple` restated for a ring of m vertices, edge e = v_e -> v_(e+1 mod m)): m in 3 .. V, and
+ *   1. A2 = sum over e = 0, 1, ... of x_e*y_(e+1) - x_(e+1)*y_e, added in that order from 0, has 0 < |A2| < inf (area = |A2| / 2);
+ *   2. no two vertices are equal;
+ *   3. no two NON-ADJACENT edges share a point (closed segments: crossing, touching or overlapping);
+ *   4. no edge folds back onto the one before it: not (orient2(v_e, v_(e+1), v_(e+2)) == 0 and
+ *      (v_e - v_(e+1)) . (v_(e+2) - v_(e+1)) > 0) -- the shared vertex is the only point two adjacent edges may have in common.
+ *   For m = 4 this is mr_quad_iou's rule (a fold or a repeated vertex of a 4-gon puts a vertex on the opposite edge).
+ * Intersection area, exact for every pair of valid polygons, convex or not, either orientation, any start vertex; a pair whose
+ * bounding boxes are disjoint is exactly 0 and nothing more is computed:
+ *   1. translate: P_i = p_i - p_0 (gt), Q_j = q_j - p_0 (det), BOTH by the gt's first vertex, before any product;
+ *   2. fans: S_i = (P_0, P_(i+1), P_(i+2)), i = 0 .. m-3, C_j = (Q_0, Q_(j+1), Q_(j+2)), j = 0 .. n-3; o = orient2 of the triangle
+ *      as listed; o == 0: the triangle is skipped; o < 0: its last two vertices are swapped (stored counter-clockwise);
+ *   3. term t = i*(n-2) + j: sign(o_i)*sign(o_j) * area(S_i and C_j), the area by clipping S_i with the three edges of C_j
+ *      (Sutherland-Hodgman, as for quads); 0 without clipping when the triangles' boxes are disjoint.  The signed fans add up to each
+ *      polygon's indicator times its orientation, and the absolute value below removes the product of the two orientations;
+ *   4. order: a_l = the terms t = l, l + 64, l + 128, ... added in that order from 0, l = 0 .. 63; then for step = 32, 16, 8, 4, 2, 1:
+ *      a_l = a_l + a_(l + step) for l < step; inter = |a_0|; iou = inter / (gt_area + det_area - inter). */
+#define MR_POLY_MAX_VERTS 64
+int mr_poly_iou(const double* gt, const int* gt_verts, const int* gt_count, const double* det, const int* det_verts,
+                const int* det_count, int N, int G, int D, int V, int* gt_valid, int* det_valid, double* gt_area,
+                double* det_area, double* inter, double* iou, hipStream_t stream);
 
 /* ---- DB detector training targets (data/processes/make_seg_detection_data.py:21-99 `MakeSegDetectionData` and
  * data/processes/make_border_map.py:24-120 `MakeBorderMap` for quadrilaterals; the batch of decoders/seg_detector_loss.py).

@@ -4,6 +4,7 @@ from .measurers import SequenceRecognitionMeasurer  # noqa: F401,E402
 from .quad_measurer import QuadMeasurer  # noqa: F401,E402
 from .seg_detector_representer import SegDetectorRepresenter  # noqa: F401,E402
 from .ribbon import Ribbon  # noqa: F401,E402
+from .polygon_measurer import PolygonMeasurer  # noqa: F401,E402
 
 
 def member_from_config(obj, cmd=None):

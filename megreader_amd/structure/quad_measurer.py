@@ -10,7 +10,8 @@ Parity unpinned: shapely / GEOS is not a dependency and cannot b
   * results at exact ties (an IoU or a covered fraction equal to its constraint to the last bit) are not pinned: GEOS
     rounds differently from the triangle clipping used here.  Away from ties the areas are exact to float64 rounding
     (tests/test_quad_measure_gpu.py: within 1e-6 px^2 of a float64 restatement at coordinates up to 2048).
-Only quadrilaterals are measured (polygons with more points: ICDARDetectionMeasurer in the reference, not mirrored).
+Only quadrilaterals are measured here; polygons with more points (curved text: 14-point annotations, ribbon outlines) go
+through `PolygonMeasurer` (structure/polygon_measurer.py), which has this class's contract.
 `iouMat` of an image without valid ground truths or without valid detections is `[]`; the reference returns an
 uninitialised 1 x 1 array there."""
 import numpy as np
