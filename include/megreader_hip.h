@@ -408,13 +408,16 @@ int mr_maxpool_bwd(int dtype, const void* dy, const unsigned char* idx, const vo
  * replaces cnn.conv0 / relu0 / pooling0 of reference backbones/crnn.py:17-19,48-55 in one pass each way.
  * x: fp32 NCHW contiguous [N,Cin,H,W] (Cin 1 or 3, even H and W); w: fp32 [64,Cin,3,3] with element strides
  * wsk,wsc,wsr,wss; y: pooled activation NHWC [N,H/2,W/2,64] of `dtype`; code: one byte per pooled element
- * (bits 0-1 = first-maximum position in the 2x2 window, bit 2 = maximum > 0).
+ * (bits 0-1 = first-maximum position in the 2x2 window, bit 2 = maximum > 0).  code == NULL in mr_stem_fwd means
+ * "do not write the codes" (inference: only mr_stem_bwd reads them); y is the same either way.
  * mr_stem_bwd ACCUMULATES into dw (strides dsk..dss) and dbias (either may be null); workspace must hold
- * mr_stem_bwd_workspace(Cin) floats.  The layer's input gradient is not produced (the input is the image). */
+ * mr_stem_bwd_workspace(Cin) floats and need not be initialised (every float that is read was written by the same
+ * call).  The layer's input gradient is not produced (the input is the image). */
 long long mr_stem_bwd_workspace(int Cin);
 /* wpack (bf16 [64][32], k = (dr*3+ds)*Cin + c, zero padded): the filter bank pre-packed for the bf16 MFMA kernel by
  * mr_stem_pack / an MR_PREP_STEM job.  When it is null (or dtype is f32, or W/2 is not a multiple of 16) mr_stem_fwd
- * runs the generic FMA kernel straight from w. */
+ * runs the generic FMA kernel straight from w.  The MFMA kernels read x with 16-byte loads when x is 16-byte aligned
+ * (dword loads otherwise); mr_stem_bwd takes its MFMA path only when dy is 8-byte and code 4-byte aligned. */
 int mr_stem_pack(const float* w, long long wsk, long long wsc, long long wsr, long long wss, void* wpack, int Cin,
                  hipStream_t stream);
 int mr_stem_fwd(int dtype, const float* x, const float* w, long long wsk, long long wsc, long long wsr,

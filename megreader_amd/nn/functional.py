@@ -617,7 +617,9 @@ class StemConvReluPoolFn(Function):
             x = x.float().contiguous()
         N, C, H, W = x.shape
         y = torch.empty((N, H // 2, W // 2, 64), dtype=dtype, device=x.device)
-        code = torch.empty((N, H // 2, W // 2, 64), dtype=torch.uint8, device=x.device)
+        # the arg-max / ReLU codes are only backward's input: without a gradient to compute they are not written at all
+        needs_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]     # (all false under torch.no_grad())
+        code = torch.empty((N, H // 2, W // 2, 64), dtype=torch.uint8, device=x.device) if needs_grad else None
         sk, sc, sr, ss = weight.stride()
         wpack = None
         if dtype == torch.bfloat16:  # filter bank pre-packed for the MFMA kernel (regenerated with the other images)
